@@ -29,21 +29,28 @@ configs[4] to the letter); ranks never exchange data on the path; the histograms
 the timed region -- torch.distributed's all_reduce (RCCL) by default; --allreduce gf2: gf2_hist_allreduce, libgf2hip's own RCCL
 communicator, from the device buffer the kernels accumulate into, on the compute context's stream, set up under a time limit
 (guarded_comm: a rank whose communicator does not come up leaves, the launcher starts fresh ranks with --allreduce torch).
-value = K * (samples of all ranks per step) / max-over-ranks time.
+value = K * (samples of all ranks per step) / max-over-ranks time; ms_per_step = that time / K.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the line.  The JSON line also carries
   roofline      the path against the HBM roofline: algorithmic bytes per launch (n/8 read [+ r/8
                 written when syndromes are stored] per sample and component) / mean launch time, measured live
                 with HIP events; traffic = PMC HBM bytes per launch from the committed rocprofv3 passes
                 (profiles/traffic.json).  With two streams a launch is one step (both components; events on the
                 main stream around the timed region, the side stream joined before the stop event); with one
                 stream it is one library call, timed on the context's stream (secondary.one_stream).
+With --full, rank 0 also checks a prefix of the resident batch through the timed path against the C oracle before the
+timed region, and the line carries in addition
+  roofline      the per-call durations of a few further two-stream steps, and the chip's streaming read ceiling
+                measured in the run (plain 16-byte loads over the resident errors).
   cpu_baseline  the reference's NumPy path (oracle/cpu_ref.py restatement of css_code.py:728) timed on this
-                host, 1 core, on a bounded sample of the same workload.
+                host, 1 core, on a bounded sample of the same workload (--no-cpu-baseline: not).
   secondary     (rank 0, N = 1) the end-to-end Monte-Carlo (sampler included), the other syndrome kernels (column gather,
                 dense table) on the same workload, configs[1] and configs[2] (Steane, Reed-Muller), and RREF GB/s
                 (2 * m * ceil(n/64) * 8 bytes / time) for one and for 256 resident 2048 x 4096 matrices, for one
-                32768 x 65536 matrix, and for 256 MiB of 64 x 512 and of 128 x 512 matrices.
+                32768 x 65536 matrix, and for 256 MiB of 64 x 512 and of 128 x 512 matrices (--no-secondary: not).
+
+--dump-outputs DIR writes what a caller of the timed path receives from its last step (dump_outputs), so that two builds
+can be compared output for output: the inputs are the same in every run with the same arguments.
 """
 import argparse
 import hashlib
@@ -303,7 +310,28 @@ def roofline_of_steps(path, gpu_s, steps, per_call_s, calls):
             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
             "traffic_source": source,
             "algorithmic_bytes_per_launch": alg_bytes, "mean_launch_ms": gpu_s / steps * 1e3, "launches": steps,
-            "mean_call_ms_on_its_stream": per_call_s * 1e3, "calls": calls}
+            "mean_call_ms_on_its_stream": per_call_s * 1e3 if calls else None, "calls": calls}
+
+
+def dump_outputs(out_dir, path, hist_z, hist_x, steps, window=1024):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as .npy files in out_dir --
+    hist_z.npy, hist_x.npy  the syndrome-weight histograms of H1.e_z and H2.e_x (float64, exact; summed over the ranks).  Every
+                            step runs over the same samples and the timed steps accumulate, so the last step's are the sum / steps.
+    syndromes_z.npy, syndromes_x.npy (--algo dense, which stores the syndromes as well) those of `window` consecutive samples
+                            from a fixed, seeded place of the batch, one 0 / 1 per check (float32, samples x checks)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, hist in (("hist_z", hist_z), ("hist_x", hist_x)):
+        assert not (hist % np.uint64(steps)).any(), "the timed steps' histograms are not %d equal ones" % steps
+        np.save(os.path.join(out_dir, name + ".npy"), (hist // np.uint64(steps)).astype(np.float64))
+    if path.algo == "dense":
+        count = min(window, path.batch)
+        first = int(np.random.default_rng(SEED).integers(0, path.batch - count + 1))
+        for name, buf, words, rows in (("syndromes_z", path.s1, path.ls1, R1), ("syndromes_x", path.s2, path.ls2, R2)):
+            # slab-major: word w of sample b at w * batch + b
+            packed = np.stack([buf.view((w * path.batch + first) * 8, count * 8).download((count,), "<u8") for w in range(words)],
+                              axis=1)
+            bits = np.unpackbits(packed.view(np.uint8), axis=1, bitorder="little")[:, :rows]
+            np.save(os.path.join(out_dir, name + ".npy"), bits.astype(np.float32))
 
 
 def rref_numbers(ctx):
@@ -606,9 +634,14 @@ def main():
     ap.add_argument("--batch-log2", type=int, default=27,
                     help="samples per GPU per step (2^k); 2^27 = 128 GiB of packed errors resident in HBM, 38 ms per step: the "
                          "driver's 20 steps are a timed region of 0.75 s (round 2 ran 2^24 = 16 GiB, 0.09 s; same rate)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the oracle check of the timed path, the roofline's per-call durations and measured "
+                         "read ceiling, the CPU baseline and the secondary measurements (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-settle", action="store_true", help="skip the 0.1 s of untimed steps before the warm-up steps")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other syndrome kernel and the RREF timings")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the other syndrome kernel and the RREF timings")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
                     help="gloo lets several ranks share one GPU to rehearse the multi-process path (histograms are "
                          "then all-reduced on the host); the driver's runs use nccl = RCCL")
@@ -633,6 +666,8 @@ def main():
     ap.add_argument("--one-stream", action="store_true",
                     help="issue both components of a step on one HIP stream (default: H2.e_x goes to a second context)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # without a launcher this process only supervises: N > 1 ranks, and also the single rank of an explicit --allreduce gf2,
     # which must be able to leave (guarded_comm) and be started afresh
@@ -692,7 +727,7 @@ def main():
             if c is not None:
                 c.set_option(int(kv.split("=")[0]), int(kv.split("=")[1]))
     path = Path(ctx, args.algo, chk1, chk2, batch, first, ctx2)
-    if rank == 0:
+    if rank == 0 and args.full:
         path.check_against_oracle(h1, h2, first)        # correctness of what is about to be timed
 
     def fence():
@@ -753,7 +788,9 @@ def main():
         elapsed = float(t.item())
     total = args.steps * total_per_step
     assert int(hist_z.sum()) == total and int(hist_x.sum()) == total
-    if not call_events:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, path, hist_z, hist_x, args.steps)
+    if not call_events and args.full:
         for c in path.contexts():
             c.profile(True)
             c.profile_reset()
@@ -784,13 +821,14 @@ def main():
     if rank == 0:
         roof = (roofline_of_steps(path, gpu_ms / 1e3, args.steps, syn_ms / 1e3 / max(1, syn_n), syn_n)
                 if path.ctx2 is not None else roofline(path, syn_ms / 1e3 / max(1, syn_n), syn_n))
-        # the chip's streaming ceiling measured in this run (plain 16-byte loads over the resident errors), next to the
-        # 8 TB/s specification the fraction is quoted against
-        probe_bytes = min(batch * 512, 1 << 32)
-        measured = ctx.membw_probe(path.ex, probe_bytes)
         roof["traffic_stale"] = traffic_stale()
-        roof["measured_read_peak_GBs"] = measured
-        roof["frac_of_measured_peak"] = roof["achieved"] / measured
+        if args.full:
+            # the chip's streaming ceiling measured in this run (plain 16-byte loads over the resident errors), next to the
+            # 8 TB/s specification the fraction is quoted against
+            probe_bytes = min(batch * 512, 1 << 32)
+            measured = ctx.membw_probe(path.ex, probe_bytes)
+            roof["measured_read_peak_GBs"] = measured
+            roof["frac_of_measured_peak"] = roof["achieved"] / measured
         # integer work of the algorithm as it is run: per sample and component (w + 2) * r / 32 32-bit XOR
         # and popcount lane-operations, w = expected listed columns (n - r)(p_x + p_y); peak = CUs x 64 lanes x 2.4 GHz
         w_mean = (N_QUBITS - R1) * (2.0 * P_TOTAL / 3.0)
@@ -822,15 +860,16 @@ def main():
             "shards": shards,
             "checks": {"histogram_total": int(hist_z.sum()), "expected_total": int(total),
                        "histogram_sha256": hashlib.sha256(hist_z.tobytes() + hist_x.tobytes()).hexdigest(),
-                       "oracle_prefix": "512 samples of this rank's batch through the timed path == oracle/gf2_oracle.c",
+                       "oracle_prefix": "512 samples of this rank's batch through the timed path == oracle/gf2_oracle.c"
+                                        if args.full else None,
                        "inputs": "H1, H2, both standard forms and logical operators == digests of the reference's own "
                                  "constructor (tests/golden/config4_golden.npz)"},
             "kernel_ms": {"syndrome_calls": syn_ms, "syndrome_calls_counted": syn_n, "histogram": hist_ms,
                           "stream_total": gpu_ms},
         }
-        if world == 1 and not args.no_cpu_baseline:               # timed on rank 0 at N = 1 only
+        if args.full and world == 1 and not args.no_cpu_baseline:     # timed on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(code, h1, h2)          # (h1, h2: the packed standard forms)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             single_z = (hist_z // np.uint64(args.steps)).astype(np.uint64)      # same batch every step
             # end to end: nothing resident, gf2_mc_run draws the errors itself (record sampler, then gather / combine / misfits per
             # component, in line on one stream); its histogram over this rank's batch must be the timed path's

@@ -1,4 +1,4 @@
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
 for cfg in "" "--opt 1=64" "--opt 1=32" "--opt 1=96" "" "--opt 1=64"; do
   echo -n "[$cfg] "
   timeout -k 10 200 $B $cfg 2>/dev/null | python -c "

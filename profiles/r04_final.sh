@@ -3,7 +3,7 @@
 root=$(pwd); out=$root/gpurun_out/r04; mkdir -p $out
 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/final_smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $out/final_smoke.log
 timeout -k 10 1100 python3 -m pytest tests -x -q -m gpu > $out/final_tests.log 2>&1; echo "tests rc=$?" >> $out/final_tests.log; tail -3 $out/final_tests.log
-python3 bench.py --steps 20 --warmup 3 > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"
+python3 bench.py --full --steps 20 --warmup 3 > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"
 : > $out/final_runs.txt
 for i in 1 2 3 4 5; do
   for v in "" "--one-stream"; do

@@ -6,6 +6,7 @@ packing round trips of tests/test_abi.py on arrays large enough for several thre
 message buffer is thread-local), and through the out-of-threads fallback (a test hook of the sanitizer builds makes the
 k-th std::thread of a call fail).
 """
+import ctypes
 import glob
 import os
 import subprocess
@@ -79,6 +80,19 @@ print("host packing ok")
 """
 
 
+def without_aslr():
+    """preexec_fn of the sanitizer child: address-space randomisation off for that process alone (personality(2) with
+    ADDR_NO_RANDOMIZE, what `setarch -R` does; set between fork and exec, so the sanitizer runtime never starts with it on).
+    The sanitizer runtimes of this gcc expect the program where a kernel with 28 bits of mmap randomisation puts it; a kernel
+    that randomises over more bits maps it elsewhere ("FATAL: ThreadSanitizer: unexpected memory mapping").  Where the flag
+    cannot be set, the child runs as it is."""
+    personality = ctypes.CDLL(None).personality
+    personality.argtypes, personality.restype = [ctypes.c_ulong], ctypes.c_int
+    current = personality(0xFFFFFFFF)                       # (0xffffffff: query)
+    if current != -1:
+        personality(current | 0x0040000)                    # ADDR_NO_RANDOMIZE
+
+
 def runtime_of(kind):
     out = subprocess.run(["g++", "-print-file-name=lib%s.so" % kind], capture_output=True, text=True).stdout.strip()
     if out and os.path.isabs(out) and os.path.exists(out):
@@ -103,7 +117,8 @@ def test_host_packing_under_sanitizer(kind, target, marker, tmp_path):
                UBSAN_OPTIONS="halt_on_error=1 print_stacktrace=1")
     script = tmp_path / "child.py"
     script.write_text(CHILD)
-    run = subprocess.run([sys.executable, str(script), lib], env=env, capture_output=True, text=True, timeout=600)
+    run = subprocess.run([sys.executable, str(script), lib], env=env, capture_output=True, text=True, timeout=600,
+                         preexec_fn=without_aslr)
     report = run.stdout[-2000:] + run.stderr[-4000:]
     assert run.returncode == 0, report
     assert "host packing ok" in run.stdout
