@@ -305,6 +305,61 @@ int gf2_mc_decode_hashed(gf2_ctx* ctx, int64_t n, int64_t ld, const uint64_t* h1
                          uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z,
                          uint64_t* counts_out);
 
+/* ---- circuit-level faults of a Clifford circuit -------------------------------------------------------
+ * [build-defined; the question the docstrings of noisy_encode_zero / noisy_encode_plus raise, css_code.py:203-312: "any
+ * physical errors that occur during preparation may create many correlated errors in the code block"]  A Pauli-frame
+ * Monte-Carlo over the fault locations of a gate list (DESIGN.md "Circuit faults").  Gates are rows (kind, a, b) as
+ * gf2_conjugate_gates takes them, plus GF2_GATE_IDLE (no action on qubit a, one fault location; b ignored), which only these
+ * entry points accept.  Locations in gate order: H and IDLE give one, (g, a); CNOT two, (g, a) then (g, b); L = their number.
+ * Sample i draws its faults from the Monte-Carlo sampler with n := L -- every operand of a gate fails independently, a CNOT has
+ * no correlated two-qubit fault, a qubit no gate touches has none.  The frame starts at zero; each gate acts (H: swap e_x[a],
+ * e_z[a]; CNOT: e_x[b] ^= e_x[a], e_z[a] ^= e_z[b]), then its locations' faults are XOR-ed in.  An outcome row (row_x, row_z)
+ * has the value row_x . e_x ^ row_z . e_z on the final frame. */
+#define GF2_GATE_H     0
+#define GF2_GATE_CNOT  1
+#define GF2_GATE_IDLE  2
+#define GF2_CIRCUIT_MAX_N          8192         /* gf2_circuit_effects: qubits                                    */
+#define GF2_CIRCUIT_MAX_ROWS       16384        /* gf2_circuit_effects: outcome rows (identity(2n) up to n = 8192) */
+#define GF2_CIRCUIT_MAX_LOCATIONS  (1 << 20)    /* gf2_circuit_create: fault locations                            */
+#define GF2_CIRCUIT_MAX_LDR        8            /* gf2_circuit_create: words per effect (512 outcome rows)        */
+typedef struct gf2_circuit gf2_circuit;         /* an effect table on the device */
+
+/* Effect table (pure host code, no GPU needed).  rows_x / rows_z: nrows packed rows of ld words (n bits each).  *nloc_out = L.
+ * eff_out[(2 l + c) * ldr + w]: bit r of the ldr-word vector = outcome r flips under an X (c = 0) or Z (c = 1) fault at
+ * location l (a Y fault flips the XOR of both); pad bits zero.  locations_out (may be null): L pairs (gate, qubit).  Both are
+ * written only if capacity >= L (capacity 0 just counts).  GF2_E_ARG: unknown kind, qubit outside [0, n), CNOT with a == b. */
+int gf2_circuit_effects(const int32_t* gates, int64_t ngates, int64_t n, const uint64_t* rows_x, const uint64_t* rows_z,
+                        int64_t nrows, int64_t ld, uint64_t* eff_out, int64_t ldr, int64_t capacity, int64_t* locations_out,
+                        int64_t* nloc_out);
+
+/* Uploads an effect table (host, 2 L ldr words).  1 <= L <= GF2_CIRCUIT_MAX_LOCATIONS, 1 <= ldr <= GF2_CIRCUIT_MAX_LDR. */
+int gf2_circuit_create(gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int64_t ldr, gf2_circuit** circuit_out);
+int gf2_circuit_destroy(gf2_ctx* ctx, gf2_circuit* circuit);
+
+/* Outcome words of samples first_sample .. first_sample + count - 1: out_dev is count x ldo (ldo >= ldr), sample-major; words
+ * past ldr are left as they were.  Asynchronous on the context's stream. */
+int gf2_circuit_outcomes_dev(gf2_ctx* ctx, const gf2_circuit* circuit, uint64_t seed, int64_t first_sample, int64_t count,
+                             double p_x, double p_y, double p_z, uint64_t* out_dev, int64_t ldo);
+
+/* Syndrome histograms of the final frame, as gf2_mc_run's (same modes, bins and host outputs).  The circuit's outcome words
+ * must be laid out [key_x: kw(r_2)] [key_z: kw(r_1)] [parity: 1] with kw(r) = 1 word for r <= 63, else 2 (low word first):
+ * key_x = vec_to_int(parity_check_c2 . e_x), key_z = vec_to_int(parity_check_c1 . e_z) (row 0 = most significant bit), parity
+ * bit 0 = z_operator . e_x, bit 1 = x_operator . e_z; ldr = kw(r_2) + kw(r_1) + 1.  GF2_HIST_FULL needs r_1, r_2 <= 24; a
+ * weight is the population count of the key.  1 <= r_1, r_2 <= 127. */
+int gf2_mc_circuit_run(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, int64_t r2, uint64_t seed, int64_t first_sample,
+                       int64_t count, double p_x, double p_y, double p_z, int mode, uint64_t* hist_z, int64_t nbins_z,
+                       uint64_t* hist_x, int64_t nbins_x);
+
+/* Table decode + logical tally of the final frame by gf2_mc_decode_hashed's rule (css_code.py:649-685, :640-646), same outcome
+ * layout.  keys: vec_to_int(syndrome) of every table entry as gf2_mc_decode_hashed takes them; flips: one byte per entry,
+ * z_operator . correction for C2's table (keys2, X errors), x_operator . correction for C1's.  A key found: the logical flip is
+ * the parity bit XOR the entry's byte; not found: the parity bit, and the sample counts as uncorrectable.  counts_out[5] as
+ * gf2_mc_decode's.  GF2_E_ARG if a key occurs twice. */
+int gf2_mc_circuit_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                          int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                          uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z,
+                          uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

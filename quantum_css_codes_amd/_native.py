@@ -19,6 +19,8 @@ GF2_OK, GF2_E_ARG, GF2_E_COLUMNS, GF2_E_DEPENDENT, GF2_E_HIP, GF2_E_NOMEM, GF2_E
 COMM_ID_BYTES = 128
 LAYOUT_SAMPLE_MAJOR, LAYOUT_BIT_SLICED, LAYOUT_TILED = 0, 1, 2
 HIST_FULL, HIST_WEIGHT = 0, 1
+GATE_H, GATE_CNOT, GATE_IDLE = 0, 1, 2
+CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 K_SYNDROME, K_HIST, K_SAMPLER, K_ELIM = 0, 1, 2, 3
 # routing flags of a context and its tunables: the few a caller needs are in include/gf2hip.h (F_MC_DENSE, F_RREF_SEQUENTIAL,
 # F_NORMALIZE_SEQUENTIAL, OPT_SLAB_PASS_LOG2, OPT_MC_CHUNK_LOG2), the rest -- routes for the parity tests and the A/B scripts -- in
@@ -105,6 +107,14 @@ SIGNATURES = {
                              ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
     "gf2_mc_run": [_p, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                    ctypes.c_int, _p, _c_i64, _p, _c_i64],
+    "gf2_circuit_effects": [_p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _c_i64, _c_i64, _p, ctypes.POINTER(_c_i64)],
+    "gf2_circuit_create": [_p, _p, _c_i64, _c_i64, _pp],
+    "gf2_circuit_destroy": [_p, _p],
+    "gf2_circuit_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p, _c_i64],
+    "gf2_mc_circuit_run": [_p, _p, _c_i64, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                           ctypes.c_int, _p, _c_i64, _p, _c_i64],
+    "gf2_mc_circuit_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double,
+                              ctypes.c_double, ctypes.c_double, _p],
     "gf2_comm_unique_id": [_p, ctypes.c_size_t],
     "gf2_comm_create": [_p, _p, ctypes.c_int, ctypes.c_int, _pp],
     "gf2_comm_create_all": [_pp, ctypes.c_int, _pp],
@@ -270,6 +280,28 @@ def _ptr(arr):
     return arr.ctypes.data_as(ctypes.c_void_p)
 
 
+def circuit_effects(gates, n, rows_x, rows_z, ldr=None):
+    """gf2_circuit_effects (host code, no GPU): gates (g, 3) int32 rows (kind, a, b) with kind GATE_H / GATE_CNOT / GATE_IDLE;
+    rows_x / rows_z: packed outcome rows (nrows x words(n)).  Returns (eff, locations): eff[l, c] = the ldr packed words of the
+    outcomes an X (c = 0) / Z (c = 1) fault at location l flips; locations (L, 2) int64 rows (gate, qubit)."""
+    gates = np.ascontiguousarray(gates, dtype=np.int32).reshape(-1, 3)
+    rows_x = np.ascontiguousarray(rows_x, dtype="<u8")
+    rows_z = np.ascontiguousarray(rows_z, dtype="<u8")
+    if rows_x.ndim != 2 or rows_x.shape != rows_z.shape:
+        raise ValueError("rows_x and rows_z must be packed 2-D arrays of one shape")
+    nrows = rows_x.shape[0]
+    ldr = max(1, words_for(nrows)) if ldr is None else int(ldr)
+    count = _c_i64(0)
+    args = (_ptr(gates) if len(gates) else None, len(gates), int(n), _ptr(rows_x) if nrows else None,
+            _ptr(rows_z) if nrows else None, nrows, rows_x.shape[1])
+    check(lib().gf2_circuit_effects(*args, None, ldr, 0, None, ctypes.byref(count)))
+    total = int(count.value)
+    eff = np.zeros((max(1, total), 2, ldr), dtype="<u8")
+    locations = np.zeros((max(1, total), 2), dtype=np.int64)
+    check(lib().gf2_circuit_effects(*args, _ptr(eff), ldr, total, _ptr(locations), ctypes.byref(count)))
+    return eff[:total], locations[:total]
+
+
 # ---- context ----------------------------------------------------------------------------------------------
 
 class DeviceBuffer(object):
@@ -358,6 +390,32 @@ class Check(object):
         try:
             if self.handle and self.ctx.handle:
                 lib().gf2_check_destroy(self.ctx.handle, self.handle)
+        except Exception:
+            pass
+
+
+class Circuit(object):
+    """The effect table of a circuit's fault locations on the device (gf2_circuit_create).  eff: (L, 2, ldr) packed words."""
+
+    def __init__(self, ctx, eff):
+        self.ctx = ctx
+        eff = np.ascontiguousarray(eff, dtype="<u8")
+        if eff.ndim != 3 or eff.shape[1] != 2:
+            raise ValueError("effects must be an (L, 2, ldr) array")
+        self.locations, self.ldr = int(eff.shape[0]), int(eff.shape[2])
+        out = ctypes.c_void_p()
+        check(lib().gf2_circuit_create(ctx.handle, _ptr(eff), self.locations, self.ldr, ctypes.byref(out)))
+        self.handle = out.value
+
+    def free(self):
+        if self.handle:
+            check(lib().gf2_circuit_destroy(self.ctx.handle, self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            if self.handle and self.ctx.handle:
+                lib().gf2_circuit_destroy(self.ctx.handle, self.handle)
         except Exception:
             pass
 
@@ -588,6 +646,44 @@ class Context(object):
         check(lib().gf2_mc_decode_hashed(self.handle, n, h1.shape[1], _ptr(h1), r1, _ptr(arrays[0]), _ptr(arrays[1]), len(arrays[1]),
                                          _ptr(h2), r2, _ptr(arrays[2]), _ptr(arrays[3]), len(arrays[3]), _ptr(arrays[4]),
                                          _ptr(arrays[5]), seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, _ptr(counts)))
+        return counts
+
+    # -- circuit-level faults -----------------------------------------------------------------------------
+    def circuit_create(self, eff):
+        return Circuit(self, eff)
+
+    def circuit_outcomes_dev(self, circ, seed, first, count, p_x, p_y, p_z, out_buf, ldo):
+        check(lib().gf2_circuit_outcomes_dev(self.handle, circ.handle, seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z,
+                                             out_buf.ptr, ldo))
+
+    def mc_circuit_run(self, circ, r1, r2, seed, first, count, p_x, p_y, p_z, mode):
+        """gf2_mc_circuit_run: returns (hist_z, hist_x) as uint64 arrays."""
+        if mode == HIST_FULL:
+            if r1 > 24 or r2 > 24:
+                raise ValueError("full histograms need r_1, r_2 <= 24")
+            nz, nx = 1 << r1, 1 << r2
+        else:
+            nz, nx = r1 + 1, r2 + 1
+        hist_z = np.zeros(nz, dtype=np.uint64)
+        hist_x = np.zeros(nx, dtype=np.uint64)
+        check(lib().gf2_mc_circuit_run(self.handle, circ.handle, r1, r2, seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z,
+                                       mode, _ptr(hist_z), nz, _ptr(hist_x), nx))
+        return hist_z, hist_x
+
+    def mc_circuit_decode(self, circ, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z):
+        """gf2_mc_circuit_decode: keys (entries x 1 or 2 words), flips (entries bytes; None with keys = a null table).  Returns
+        the five counts."""
+        counts = np.zeros(5, dtype=np.uint64)
+        tables = []
+        for keys, flips in ((keys1, flips1), (keys2, flips2)):
+            keys = np.ascontiguousarray(keys, dtype="<u8")
+            entries = len(keys)
+            flips = None if flips is None else np.ascontiguousarray(flips, dtype=np.uint8)
+            tables.append((keys, flips, entries))
+        (k1, f1, e1), (k2, f2, e2) = tables
+        check(lib().gf2_mc_circuit_decode(self.handle, circ.handle, r1, _ptr(k1) if e1 else None, None if f1 is None or not e1 else _ptr(f1),
+                                          e1, r2, _ptr(k2) if e2 else None, None if f2 is None or not e2 else _ptr(f2), e2,
+                                          seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, _ptr(counts)))
         return counts
 
     # -- syndromes ----------------------------------------------------------------------------------------

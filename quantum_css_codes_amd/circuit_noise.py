@@ -1,0 +1,194 @@
+"""
+Circuit-level fault Monte-Carlo [build-defined; DESIGN.md "Circuit faults"].
+
+The reference warns that its encoders are not fault tolerant: "any physical errors that occur during preparation may create
+many correlated errors in the code block" (noisy_encode_zero / noisy_encode_plus, css_code.py:203-312).  This module answers
+what a fault INSIDE such a circuit does to the block.  A gate list -- rows (kind, a, b): GATE_H on a, GATE_CNOT control a target
+b, GATE_IDLE on a (no action) -- has one fault location per gate operand, in gate order (CNOT: control, then target).  Every
+location fails independently with a Pauli X, Y or Z (p_x, p_y, p_z): a CNOT has no correlated two-qubit fault, and a qubit no
+gate touches has no fault (IDLE gates model input or memory noise).  Sample i draws its faults from the Monte-Carlo sampler of
+DESIGN.md "Sampler" run over the L locations instead of n qubits.  The Pauli frame starts at zero, every gate acts on it (H:
+swap e_x[a], e_z[a]; CNOT: e_x[b] ^= e_x[a], e_z[a] ^= e_z[b]) and then its locations' faults are XOR-ed in.
+
+Frame propagation is linear over GF(2), so the syndromes and logical parities of the final frame are the XOR of one
+precomputed effect per fault (gf2_circuit_effects, host code); the device kernels gather those and never store a frame.
+
+After encode_zero only `logical_x` (a flipped logical Z measurement) is physical -- Z-type operators act trivially on |0_L> --
+and after encode_plus only `logical_z`; both are reported as statistics of the frame.
+"""
+import numpy as np
+
+from . import _native
+from . import montecarlo
+
+GATE_H, GATE_CNOT, GATE_IDLE = _native.GATE_H, _native.GATE_CNOT, _native.GATE_IDLE
+MAX_LOCATIONS = _native.CIRCUIT_MAX_LOCATIONS
+MAX_ROWS = 64 * _native.CIRCUIT_MAX_LDR
+
+
+def _gates(gates):
+    gates = np.ascontiguousarray(gates, dtype=np.int32)
+    if gates.size == 0:
+        return gates.reshape(0, 3)
+    if gates.ndim != 2 or gates.shape[1] != 3:
+        raise ValueError("gates must be rows (kind, a, b)")
+    return gates
+
+
+def fault_locations(gates):
+    """The fault locations of a gate list as an (L, 2) int64 array of (gate index, qubit): H and IDLE give one, (g, a); CNOT
+    two, (g, a) then (g, b)."""
+    gates = _gates(gates)
+    if np.any((gates[:, 0] < GATE_H) | (gates[:, 0] > GATE_IDLE)):
+        raise ValueError("unknown gate kind (0 = H, 1 = CNOT, 2 = IDLE)")
+    index = np.arange(len(gates), dtype=np.int64)
+    two = gates[:, 0] == GATE_CNOT
+    order = np.concatenate((2 * index, 2 * index[two] + 1))
+    rows = np.concatenate((np.stack((index, gates[:, 1].astype(np.int64)), axis=1),
+                           np.stack((index[two], gates[two, 2].astype(np.int64)), axis=1)))
+    return rows[np.argsort(order, kind='stable')]
+
+
+def _key_words(r):
+    return 1 if r <= 63 else 2
+
+
+def _parity_bytes(words, operator):
+    """operator . row (mod 2) for every row of packed `words` (entries x w) as uint8."""
+    masked = np.ascontiguousarray(words & operator[None, :words.shape[1]])
+    return (np.unpackbits(masked.view(np.uint8), axis=1).sum(axis=1) & 1).astype(np.uint8)
+
+
+class FaultCircuit(object):
+    """
+    A gate list on n qubits with outcome rows, prepared for the Monte-Carlo: the effect table (host) and, on first use, its
+    device copy.  FaultCircuit(gates, n, rows_x, rows_z) takes any outcome rows (dense 0/1 arrays, at most 512 rows; row r is
+    bit r & 63 of word r >> 6 of a sample's outcome words); FaultCircuit.for_code(code, gates) lays out the syndromes and the two
+    logical parities of a CSSCode's final frame the way `monte_carlo` and `logical_error_rates` read them:
+        [key_x: kw(r_2) words] [key_z: kw(r_1) words] [parity: 1 word],  kw(r) = 1 for r <= 63, else 2 (low word first),
+    key_x = vec_to_int(parity_check_c2 . e_x), key_z = vec_to_int(parity_check_c1 . e_z), parity bit 0 = z_operator . e_x,
+    bit 1 = x_operator . e_z.
+    """
+
+    def __init__(self, gates, n, rows_x, rows_z, code=None):
+        self.gates = _gates(gates)
+        self.n = int(n)
+        rows_x, rows_z = np.asarray(rows_x), np.asarray(rows_z)
+        if rows_x.ndim != 2 or rows_x.shape != rows_z.shape or rows_x.shape[1] != self.n:
+            raise ValueError("rows_x and rows_z must be (rows, n) arrays of one shape")
+        if self.n < 1 or self.n > _native.CIRCUIT_MAX_N:
+            raise ValueError("circuit faults need 1 <= n <= %d qubits" % _native.CIRCUIT_MAX_N)
+        if not 1 <= rows_x.shape[0] <= MAX_ROWS:
+            raise ValueError("circuit faults need 1 to %d outcome rows (ldr <= %d words per sample)" % (MAX_ROWS, _native.CIRCUIT_MAX_LDR))
+        self.rows = int(rows_x.shape[0])
+        self.code = code
+        self.effects, self.locations = _native.circuit_effects(self.gates, self.n, _native.pack_rows(rows_x), _native.pack_rows(rows_z))
+        self.ldr = int(self.effects.shape[2])
+        self._device = None
+
+    @classmethod
+    def for_code(cls, code, gates):
+        r_1, r_2, n = code.r_1, code.r_2, code.n
+        if min(r_1, r_2) < 1 or max(r_1, r_2) > 127:
+            raise ValueError("the Monte-Carlo layout of a circuit's outcomes needs 1 <= r_1, r_2 <= 127")
+        kwx, kwz = _key_words(r_2), _key_words(r_1)
+        rows_x = np.zeros((64 * (kwx + kwz + 1), n), dtype=np.uint8)
+        rows_z = np.zeros_like(rows_x)
+        rows_x[r_2 - 1 - np.arange(r_2)] = code.parity_check_c2                 # vec_to_int: row 0 is the most significant bit
+        rows_z[64 * kwx + r_1 - 1 - np.arange(r_1)] = code.parity_check_c1
+        rows_x[64 * (kwx + kwz)] = code.z_operator_matrix()[0]
+        rows_z[64 * (kwx + kwz) + 1] = code.x_operator_matrix()[0]
+        return cls(gates, n, rows_x, rows_z, code=code)
+
+    @property
+    def num_locations(self):
+        return len(self.locations)
+
+    def device(self):
+        if self._device is None:
+            if not 1 <= self.num_locations <= MAX_LOCATIONS:
+                raise ValueError("the Monte-Carlo needs 1 <= L <= %d (2^20) fault locations, the circuit has %d"
+                                 % (MAX_LOCATIONS, self.num_locations))
+            self._device = _native.default_context().circuit_create(self.effects)
+        return self._device
+
+    def outcomes(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """The outcome words of samples [first_sample, first_sample + num_samples): a (num_samples, ldr) uint64 array."""
+        ctx = _native.default_context()
+        circ = self.device()
+        count = int(num_samples)
+        buf = ctx.alloc(max(1, count) * self.ldr * 8)
+        ctx.circuit_outcomes_dev(circ, int(seed), int(first_sample), count, float(p_x), float(p_y), float(p_z), buf, self.ldr)
+        out = buf.download((count, self.ldr), np.uint64)
+        buf.free()
+        return out
+
+    def _need_code(self):
+        if self.code is None:
+            raise ValueError("histograms and the table decode need a circuit made by FaultCircuit.for_code")
+        return self.code
+
+    def monte_carlo(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, mode=None):
+        """Histograms of the final frame's syndromes, shaped like CSSCode.monte_carlo's."""
+        code = self._need_code()
+        mode = montecarlo.pick_mode(code.r_1, code.r_2, mode)
+        hist_z, hist_x = _native.default_context().mc_circuit_run(
+            self.device(), code.r_1, code.r_2, int(seed), int(first_sample), int(num_samples), float(p_x), float(p_y), float(p_z),
+            _native.HIST_FULL if mode == 'full' else _native.HIST_WEIGHT)
+        return {'hist_z': hist_z, 'hist_x': hist_x, 'mode': mode}
+
+    def _tables(self):
+        """Keys (as gf2_mc_decode_hashed takes them) and one flip byte per entry, cached on the code object like decode_local's."""
+        code = self.code
+        cached = getattr(code, "_hashed_table_arrays", None)
+        if cached is None or cached[0] is not code._c1_syndromes or cached[1] is not code._c2_syndromes:
+            cached = (code._c1_syndromes, code._c2_syndromes, montecarlo.table_entries(code._c1_syndromes, code.r_1, code.n),
+                      montecarlo.table_entries(code._c2_syndromes, code.r_2, code.n))
+            code._hashed_table_arrays = cached
+        flips = getattr(code, "_circuit_flip_arrays", None)
+        if flips is None or flips[0] is not cached:
+            two = lambda vec: np.pad(_native.pack_rows(np.asarray(vec).reshape(1, -1))[0], (0, 2))[:2]
+            flips = (cached, _parity_bytes(cached[2][1], two(code.x_operator_matrix()[0])),
+                     _parity_bytes(cached[3][1], two(code.z_operator_matrix()[0])))
+            code._circuit_flip_arrays = flips
+        return cached[2][0], flips[1], cached[3][0], flips[2]
+
+    def logical_error_rates(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """Table decode + logical tally of the final frame by CSSCode.logical_error_rates' rule; the same dict of counts."""
+        code = self._need_code()
+        if code.n > 128:
+            raise ValueError("the table decode of a circuit's final frame needs n <= 128 (where the syndrome tables exist)")
+        keys1, flips1, keys2, flips2 = self._tables()
+        counts = _native.default_context().mc_circuit_decode(
+            self.device(), code.r_1, keys1, flips1, code.r_2, keys2, flips2, int(seed), int(first_sample), int(num_samples),
+            float(p_x), float(p_y), float(p_z))
+        out = {name: int(v) for name, v in zip(montecarlo.DECODE_FIELDS, counts)}
+        out['samples'] = int(num_samples)
+        return out
+
+    # The two with montecarlo.run_sharded's / decode_sharded's local_fn signature (the code argument must be this circuit's).
+    def run_local(self, code, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, mode=None):
+        if code is not self.code:
+            raise ValueError("this circuit was made for another code object")
+        return self.monte_carlo(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample, mode=mode)
+
+    def decode_local(self, code, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        if code is not self.code:
+            raise ValueError("this circuit was made for another code object")
+        return self.logical_error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample)
+
+
+def circuit_for(code, gates):
+    """FaultCircuit.for_code(code, gates), cached on the code object by the gate list's contents."""
+    gates = _gates(gates)
+    cache = code.__dict__.setdefault("_fault_circuits", {})
+    key = gates.tobytes()
+    if key not in cache:
+        cache[key] = FaultCircuit.for_code(code, gates)
+    return cache[key]
+
+
+def encoder_gates(code, state):
+    if state not in ('zero', 'plus'):
+        raise ValueError("state must be 'zero' or 'plus'")
+    return code.encode_zero_gates() if state == 'zero' else code.encode_plus_gates()

@@ -1,0 +1,382 @@
+// Circuit-level fault Monte-Carlo (DESIGN.md "Circuit faults"): a Pauli-frame simulation of a gate list (H, CNOT, IDLE) whose
+// every fault location fails independently -- the question the docstrings of noisy_encode_zero / noisy_encode_plus raise
+// (css_code.py:203-312: "any physical errors that occur during preparation may create many correlated errors in the code block").
+//
+// Frame propagation through H and CNOT is linear over GF(2), so what the final frame does to a set of outcome rows (syndrome bits,
+// logical parities) is the XOR, over the faults of a sample, of one precomputed vector per (location, X or Z): the effect table
+// gf2_circuit_effects makes on the host (gf2_host.cpp).  The frame itself is never stored.  One kernel template, lane = sample as in
+// decode_hash_kernel (gf2_table.hip): the Monte-Carlo sampler (gf2_sampler.h, unchanged) runs over the L LOCATIONS instead of the n
+// qubits, segment by segment, and every fault XORs its effect into LDR register words.  Three epilogues: store the words, bin the
+// two syndrome keys (gf2_mc_run's histograms), or look the keys up in the hashed syndrome tables and tally (gf2_mc_decode_hashed's
+// counts).
+//
+// LDS per workgroup of 256 lanes: the sampler's two inverse-CDF tables (8 KiB), the effect table when it fits CIRC_EFF_LDS_BYTES
+// (otherwise every fault reads its effect through L2), one 512-bit "taken" map per lane for Floyd's rule (17 dwords apart: the odd
+// stride keeps the lanes of a wavefront on different banks), and the privatised bins or the five counts.  The map is only touched
+// by samples with at least two faults in a segment: a segment's first fault can meet no earlier one.
+#include <new>
+
+#include "gf2_internal.h"
+#include "gf2_hash_dev.h"
+#include "gf2_sampler.h"
+
+#define CIRC_THREADS 256
+#define CIRC_TAKEN_STRIDE 17                   // dwords per lane: 16 hold the 512 bits
+#define CIRC_EFF_LDS_BYTES 20480               // effect tables up to this size are staged in LDS
+#define CIRC_BINS_LDS 4096                     // both histograms together, privatised in LDS up to this many bins
+
+struct gf2_circuit {
+    int64_t locations, ldr;
+    u64* eff_dev;                              // 2 * locations * ldr words
+    u64 any[GF2_CIRCUIT_MAX_LDR];              // OR of all effects, word by word: which outcome bits can be set at all
+};
+
+enum { CIRC_STORE = 0, CIRC_HIST = 1, CIRC_TALLY = 2 };
+
+struct CircuitArgs {
+    const u64* eff;
+    int locations;
+    u64 seed;
+    int64_t first_sample, count;
+    SegTables th;
+    // store
+    u64* out;
+    int64_t ldo;
+    // histograms and tally: the words are [key_x: kwx] [key_z: kwz] [parity]
+    int kwx, kwz;
+    int mode, nbz, nbx, priv;
+    u64* hist_z;
+    u64* hist_x;
+    HashTab tab[2];                            // [0]: parity_check_c2's table (key_x), [1]: parity_check_c1's (key_z)
+    const unsigned char* flips[2];             // operator . correction of every table entry
+    u64* counts;
+};
+
+template <int LDR, int EPI, bool STAGED>
+__global__ __launch_bounds__(CIRC_THREADS) void circuit_kernel(CircuitArgs a) {
+    extern __shared__ u64 circ_lds[];
+    u64* cdf_lds = circ_lds;                                                       // [2][GF2_SEG_CDF]
+    u64* eff_lds = circ_lds + 2 * GF2_SEG_CDF;
+    unsigned int* taken = (unsigned int*)(eff_lds + (STAGED ? 2 * a.locations * LDR : 0));
+    unsigned int* bins = taken + CIRC_THREADS * CIRC_TAKEN_STRIDE;                  // histograms: nbz + nbx; tally: 5
+    for (int i = threadIdx.x; i < 2 * GF2_SEG_CDF; i += blockDim.x)
+        if (a.th.nseg > 1 || i >= GF2_SEG_CDF) cdf_lds[i] = a.th.cdf[i];            // (one segment: only the last one's table is read)
+    if (STAGED)
+        for (int i = threadIdx.x; i < 2 * a.locations * LDR; i += blockDim.x) eff_lds[i] = a.eff[i];
+    if (EPI == CIRC_HIST && a.priv)
+        for (int i = threadIdx.x; i < a.nbz + a.nbx; i += blockDim.x) bins[i] = 0;
+    if (EPI == CIRC_TALLY && threadIdx.x < 5) bins[threadIdx.x] = 0;
+    __syncthreads();
+    const u64* eff = STAGED ? eff_lds : a.eff;
+    unsigned int* mine = taken + threadIdx.x * CIRC_TAKEN_STRIDE;
+    unsigned int local[5] = {0, 0, 0, 0, 0};
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += stride) {
+        const u64 ks = sample_key(a.seed, (u64)(a.first_sample + i));
+        u64 out[LDR];
+#pragma unroll
+        for (int w = 0; w < LDR; ++w) out[w] = 0;
+        for (int s = 0; s < a.th.nseg; ++s) {
+            const bool last = s == a.th.nseg - 1;
+            const int nb = last ? a.th.nb_last : GF2_SEG_BITS;
+            const u64 d = segment_draw(ks, (u64)s);
+            const int K = error_count(d, nb, cdf_lds + (last ? GF2_SEG_CDF : 0));
+            if (K > 1)
+                for (int w = 0; w < (nb + 31) >> 5; ++w) mine[w] = 0;
+            for (int k = 0; k < K; ++k) {
+                unsigned int t, kind;
+                error_draw(d, k, K, nb, a.th.t_1, a.th.t_2, &t, &kind);
+                unsigned int pos = t;
+                if (K > 1) {                                                       // Floyd's rule: a candidate already taken -> j
+                    if ((mine[t >> 5] >> (t & 31u)) & 1u) pos = (unsigned int)(nb - K + k);
+                    mine[pos >> 5] |= 1u << (pos & 31u);
+                }
+                const u64* e = eff + (size_t)(2 * (s * GF2_SEG_BITS + (int)pos)) * LDR;   // pos < nb: a location below L
+                if (kind & 1u) {
+#pragma unroll
+                    for (int w = 0; w < LDR; ++w) out[w] ^= e[w];
+                }
+                if (kind & 2u) {
+#pragma unroll
+                    for (int w = 0; w < LDR; ++w) out[w] ^= e[LDR + w];
+                }
+            }
+        }
+        if constexpr (EPI == CIRC_STORE) {
+#pragma unroll
+            for (int w = 0; w < LDR; ++w) a.out[i * a.ldo + w] = out[w];
+        } else {
+            // (constant indices and selects: a run-time index into out[] would put it into scratch)
+            const u64 x_lo = out[0], x_hi = a.kwx == 2 ? out[1] : 0ull;
+            const u64 z_lo = a.kwx == 1 ? out[1] : out[2];
+            const u64 z_hi = a.kwz == 2 ? (a.kwx == 1 ? out[2] : out[LDR >= 4 ? 3 : 0]) : 0ull;
+            const u64 parity = out[LDR - 1];
+            if constexpr (EPI == CIRC_HIST) {
+                const bool full = a.mode == GF2_HIST_FULL;
+                const unsigned int bx = full ? (unsigned int)x_lo : (unsigned int)(__popcll(x_lo) + __popcll(x_hi));
+                const unsigned int bz = full ? (unsigned int)z_lo : (unsigned int)(__popcll(z_lo) + __popcll(z_hi));
+                if (bz < (unsigned int)a.nbz && bx < (unsigned int)a.nbx) {        // (the host has checked the table: always)
+                    if (a.priv) {
+                        atomicAdd(&bins[bz], 1u);
+                        atomicAdd(&bins[a.nbz + bx], 1u);
+                    } else {
+                        atomicAdd(&a.hist_z[bz], 1ull);
+                        atomicAdd(&a.hist_x[bx], 1ull);
+                    }
+                }
+            } else {
+                bool flip[2], miss[2];
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const u64 lo = c ? z_lo : x_lo, hi = c ? z_hi : x_hi;
+                    const int kw = c ? a.kwz : a.kwx;
+                    const u64 slot = kw == 1 ? hash_find<1>(a.tab[c], 0ull, lo) : hash_find<2>(a.tab[c], hi, lo);
+                    miss[c] = slot == ~0ull;
+                    flip[c] = (parity >> c) & 1ull;
+                    if (!miss[c]) flip[c] = flip[c] != (bool)(a.flips[c][a.tab[c].val[slot]] & 1);   // css_code.py:655-657: no match, no correction
+                }
+                local[0] += flip[0];
+                local[1] += flip[1];
+                local[2] += flip[0] | flip[1];
+                local[3] += miss[0];
+                local[4] += miss[1];
+            }
+        }
+    }
+    if (EPI == CIRC_HIST && a.priv) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < a.nbz; i += blockDim.x)
+            if (bins[i]) atomicAdd(&a.hist_z[i], (u64)bins[i]);
+        for (int i = threadIdx.x; i < a.nbx; i += blockDim.x)
+            if (bins[a.nbz + i]) atomicAdd(&a.hist_x[i], (u64)bins[a.nbz + i]);
+    }
+    if (EPI == CIRC_TALLY) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            if (local[k]) atomicAdd(&bins[k], local[k]);
+        __syncthreads();
+        if (threadIdx.x < 5 && bins[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (u64)bins[threadIdx.x]);
+    }
+}
+
+template <int LDR, int EPI>
+static void circuit_launch_ldr(gf2_ctx* ctx, const CircuitArgs& a, bool staged, unsigned blocks, size_t lds) {
+    if (staged)
+        hipLaunchKernelGGL((circuit_kernel<LDR, EPI, true>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+    else
+        hipLaunchKernelGGL((circuit_kernel<LDR, EPI, false>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+}
+
+// bins: LDS dwords behind the taken maps.  The histogram and tally epilogues exist for the 3 to 5 words of the Monte-Carlo layout.
+template <int EPI>
+static int circuit_launch(gf2_ctx* ctx, const gf2_circuit* circ, CircuitArgs& a, int bins) {
+    const size_t eff_bytes = (size_t)2 * circ->locations * circ->ldr * 8;
+    const bool staged = eff_bytes <= CIRC_EFF_LDS_BYTES;
+    const size_t lds = (size_t)2 * GF2_SEG_CDF * 8 + (staged ? eff_bytes : 0) + (size_t)CIRC_THREADS * CIRC_TAKEN_STRIDE * 4 + (size_t)bins * 4;
+    a.eff = circ->eff_dev;
+    a.locations = (int)circ->locations;
+    int64_t blocks = gf2_cdiv(a.count, CIRC_THREADS * 16);
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    GF2_TRY(gf2_prof_begin(ctx, GF2_K_SAMPLER));
+    switch (circ->ldr) {
+        case 3: circuit_launch_ldr<3, EPI>(ctx, a, staged, (unsigned)blocks, lds); break;
+        case 4: circuit_launch_ldr<4, EPI>(ctx, a, staged, (unsigned)blocks, lds); break;
+        case 5: circuit_launch_ldr<5, EPI>(ctx, a, staged, (unsigned)blocks, lds); break;
+        default:
+            if (EPI == CIRC_STORE) switch (circ->ldr) {
+                case 1: circuit_launch_ldr<1, CIRC_STORE>(ctx, a, staged, (unsigned)blocks, lds); break;
+                case 2: circuit_launch_ldr<2, CIRC_STORE>(ctx, a, staged, (unsigned)blocks, lds); break;
+                case 6: circuit_launch_ldr<6, CIRC_STORE>(ctx, a, staged, (unsigned)blocks, lds); break;
+                case 7: circuit_launch_ldr<7, CIRC_STORE>(ctx, a, staged, (unsigned)blocks, lds); break;
+                case 8: circuit_launch_ldr<8, CIRC_STORE>(ctx, a, staged, (unsigned)blocks, lds); break;
+            }
+    }
+    GF2_TRY(gf2_prof_end(ctx));
+    GF2_HIP(hipGetLastError());
+    return GF2_OK;
+}
+
+// The Monte-Carlo layout of a circuit's words for checks of r_1 and r_2 rows, tested against what the table can set.
+static int circuit_layout(const char* who, const gf2_circuit* circ, int64_t r1, int64_t r2, CircuitArgs* a) {
+    if (r1 < 1 || r2 < 1 || r1 > 127 || r2 > 127) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 127", who);
+    a->kwx = r2 <= 63 ? 1 : 2;
+    a->kwz = r1 <= 63 ? 1 : 2;
+    if (circ->ldr != a->kwx + a->kwz + 1)
+        GF2_FAIL(GF2_E_ARG, "%s: r_1 = %lld and r_2 = %lld need effects of %d words (key_x, key_z, parity), the circuit has %lld", who,
+                 (long long)r1, (long long)r2, a->kwx + a->kwz + 1, (long long)circ->ldr);
+    auto beyond = [](const u64* words, int kw, int64_t r) {            // a bit at or above r in a key of kw words
+        const int64_t top = r - 64 * (kw - 1);                           // bits of the highest word (1 .. 63)
+        return (words[kw - 1] >> top) != 0;
+    };
+    if (beyond(circ->any, a->kwx, r2) || beyond(circ->any + a->kwx, a->kwz, r1) || (circ->any[circ->ldr - 1] >> 2) != 0)
+        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits or the two parity bits", who);
+    return GF2_OK;
+}
+
+extern "C" {
+
+int gf2_circuit_create(gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int64_t ldr, gf2_circuit** circuit_out) {
+    if (!ctx || !eff || !circuit_out) GF2_FAIL(GF2_E_ARG, "gf2_circuit_create: null argument");
+    *circuit_out = nullptr;
+    if (locations < 1 || locations > GF2_CIRCUIT_MAX_LOCATIONS)
+        GF2_FAIL(GF2_E_ARG, "gf2_circuit_create: needs 1 <= locations <= %d (2^20), got %lld", GF2_CIRCUIT_MAX_LOCATIONS, (long long)locations);
+    if (ldr < 1 || ldr > GF2_CIRCUIT_MAX_LDR)
+        GF2_FAIL(GF2_E_ARG, "gf2_circuit_create: needs 1 <= ldr <= %d words per effect, got %lld", GF2_CIRCUIT_MAX_LDR, (long long)ldr);
+    GF2_TRY(gf2_ctx_activate(ctx));
+    gf2_circuit* circ = new (std::nothrow) gf2_circuit();
+    if (!circ) GF2_FAIL(GF2_E_NOMEM, "gf2_circuit_create: out of host memory");
+    circ->locations = locations;
+    circ->ldr = ldr;
+    circ->eff_dev = nullptr;
+    for (int w = 0; w < GF2_CIRCUIT_MAX_LDR; ++w) circ->any[w] = 0;
+    for (int64_t i = 0; i < 2 * locations; ++i)
+        for (int64_t w = 0; w < ldr; ++w) circ->any[w] |= eff[i * ldr + w];
+    const size_t bytes = (size_t)2 * locations * ldr * 8;
+    int rc = gf2_dev_alloc(ctx, bytes, (void**)&circ->eff_dev);
+    if (rc == GF2_OK) rc = gf2_h2d(ctx, circ->eff_dev, eff, bytes);
+    if (rc != GF2_OK) {
+        if (circ->eff_dev) (void)gf2_dev_free(ctx, circ->eff_dev);
+        delete circ;
+        return rc;
+    }
+    *circuit_out = circ;
+    return GF2_OK;
+}
+
+int gf2_circuit_destroy(gf2_ctx* ctx, gf2_circuit* circuit) {
+    if (!ctx) GF2_FAIL(GF2_E_ARG, "gf2_circuit_destroy: null context");
+    if (!circuit) return GF2_OK;
+    const int rc = gf2_dev_free(ctx, circuit->eff_dev);
+    delete circuit;
+    return rc;
+}
+
+int gf2_circuit_outcomes_dev(gf2_ctx* ctx, const gf2_circuit* circuit, uint64_t seed, int64_t first_sample, int64_t count,
+                             double p_x, double p_y, double p_z, uint64_t* out_dev, int64_t ldo) {
+    if (!ctx || !circuit) GF2_FAIL(GF2_E_ARG, "gf2_circuit_outcomes_dev: null argument");
+    if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "gf2_circuit_outcomes_dev: negative range");
+    if (ldo < circuit->ldr) GF2_FAIL(GF2_E_ARG, "gf2_circuit_outcomes_dev: ldo must be at least the circuit's %lld words", (long long)circuit->ldr);
+    GF2_TRY(check_probabilities(p_x, p_y, p_z));
+    if (count == 0) return GF2_OK;
+    if (!out_dev) GF2_FAIL(GF2_E_ARG, "gf2_circuit_outcomes_dev: null buffer");
+    GF2_TRY(gf2_ctx_activate(ctx));
+    CircuitArgs a = {};
+    GF2_TRY(gf2_seg_tables(ctx, p_x, p_y, p_z, circuit->locations, &a.th));
+    a.seed = seed;
+    a.first_sample = first_sample;
+    a.count = count;
+    a.out = (u64*)out_dev;
+    a.ldo = ldo;
+    return circuit_launch<CIRC_STORE>(ctx, circuit, a, 0);
+}
+
+int gf2_mc_circuit_run(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, int64_t r2, uint64_t seed, int64_t first_sample,
+                       int64_t count, double p_x, double p_y, double p_z, int mode, uint64_t* hist_z, int64_t nbins_z,
+                       uint64_t* hist_x, int64_t nbins_x) {
+    if (!ctx || !circuit || !hist_z || !hist_x) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_run: null argument");
+    if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_run: negative range");
+    if (mode != GF2_HIST_FULL && mode != GF2_HIST_WEIGHT) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_run: unknown mode %d", mode);
+    CircuitArgs a = {};
+    GF2_TRY(circuit_layout("gf2_mc_circuit_run", circuit, r1, r2, &a));
+    if (mode == GF2_HIST_FULL && (r1 > 24 || r2 > 24)) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_run: full histograms need r <= 24");
+    const int64_t want_z = mode == GF2_HIST_FULL ? (1ll << r1) : r1 + 1, want_x = mode == GF2_HIST_FULL ? (1ll << r2) : r2 + 1;
+    if (nbins_z != want_z || nbins_x != want_x)
+        GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_run: expected %lld and %lld bins", (long long)want_z, (long long)want_x);
+    GF2_TRY(check_probabilities(p_x, p_y, p_z));
+    GF2_TRY(gf2_ctx_activate(ctx));
+    const size_t hzb = (size_t)nbins_z * 8, hxb = (size_t)nbins_x * 8;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    GF2_TRY(gf2_ws_reserve(ctx, 0, al(hzb) + al(hxb)));
+    uint64_t* dz = (uint64_t*)ctx->ws[0];
+    uint64_t* dx = (uint64_t*)((char*)ctx->ws[0] + al(hzb));
+    GF2_TRY(gf2_dev_zero(ctx, dz, hzb));
+    GF2_TRY(gf2_dev_zero(ctx, dx, hxb));
+    if (count > 0) {
+        GF2_TRY(gf2_seg_tables(ctx, p_x, p_y, p_z, circuit->locations, &a.th));
+        a.seed = seed;
+        a.first_sample = first_sample;
+        a.count = count;
+        a.mode = mode;
+        a.nbz = (int)nbins_z;
+        a.nbx = (int)nbins_x;
+        a.priv = nbins_z + nbins_x <= CIRC_BINS_LDS;
+        a.hist_z = (u64*)dz;
+        a.hist_x = (u64*)dx;
+        GF2_TRY(circuit_launch<CIRC_HIST>(ctx, circuit, a, a.priv ? (int)(nbins_z + nbins_x) : 0));
+    }
+    GF2_TRY(gf2_d2h(ctx, hist_z, dz, hzb));
+    GF2_TRY(gf2_d2h(ctx, hist_x, dx, hxb));
+    return GF2_OK;
+}
+
+int gf2_mc_circuit_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                          int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                          uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z,
+                          uint64_t* counts_out) {
+    if (!ctx || !circuit || !counts_out) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode: null argument");
+    CircuitArgs a = {};
+    GF2_TRY(circuit_layout("gf2_mc_circuit_decode", circuit, r1, r2, &a));
+    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !flips1)) || (entries2 && (!keys2 || !flips2)))
+        GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode: bad table (a null array with entries > 0, or a negative count)");
+    if (entries1 > (int64_t)TBL_HASH_MAX_ENTRIES || entries2 > (int64_t)TBL_HASH_MAX_ENTRIES)
+        GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode: table too large");
+    if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode: negative range");
+    GF2_TRY(check_probabilities(p_x, p_y, p_z));
+    GF2_TRY(gf2_ctx_activate(ctx));
+    for (int k = 0; k < 5; ++k) counts_out[k] = 0;
+    if (count == 0) return GF2_OK;
+    GF2_TRY(gf2_seg_tables(ctx, p_x, p_y, p_z, circuit->locations, &a.th));
+    a.seed = seed;
+    a.first_sample = first_sample;
+    a.count = count;
+    // side 0: key_x against parity_check_c2's table; side 1: key_z against parity_check_c1's
+    const int64_t es[2] = {entries2, entries1};
+    const uint64_t* ks[2] = {keys2, keys1};
+    const uint8_t* fs[2] = {flips2, flips1};
+    const int kws[2] = {a.kwx, a.kwz};
+    HashAlloc tabs[2] = {HashAlloc(ctx), HashAlloc(ctx)};
+    void* dev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    u64* counts_dev = nullptr;
+    int* flags_dev = nullptr;
+    int rc = gf2_dev_alloc(ctx, 16, (void**)&flags_dev);
+    if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, 40, (void**)&counts_dev);
+    if (rc == GF2_OK && (hipMemsetAsync(flags_dev, 0, 16, ctx->stream) != hipSuccess || hipMemsetAsync(counts_dev, 0, 40, ctx->stream) != hipSuccess))
+        rc = GF2_E_HIP;
+    for (int c = 0; c < 2 && rc == GF2_OK; ++c) {
+        const int kw = kws[c];
+        const size_t ent = (size_t)(es[c] > 0 ? es[c] : 1);
+        rc = gf2_dev_alloc(ctx, ent * 8 * kw, &dev[c][0]);
+        if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, ent, &dev[c][1]);
+        if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][0], ks[c], (size_t)es[c] * 8 * kw);
+        if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][1], fs[c], (size_t)es[c]);
+        if (rc == GF2_OK) rc = tabs[c].make(pow2_at_least((u64)es[c] * 2 + 2), kw);
+        if (rc == GF2_OK && es[c]) {
+            hipLaunchKernelGGL(table_insert_kernel, dim3((unsigned)gf2_cdiv(es[c], 256)), dim3(256), 0, ctx->stream, tabs[c].tab,
+                               (const u64*)dev[c][0], kw, es[c], flags_dev);
+            if (hipGetLastError() != hipSuccess) rc = GF2_E_HIP;
+        }
+        a.tab[c] = tabs[c].tab;
+        a.flips[c] = (const unsigned char*)dev[c][1];
+    }
+    int flags_host[2] = {0, 0};
+    if (rc == GF2_OK && (hipMemcpyAsync(flags_host, flags_dev, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                         hipStreamSynchronize(ctx->stream) != hipSuccess))
+        rc = GF2_E_HIP;
+    if (rc == GF2_OK && (flags_host[0] || flags_host[1])) {
+        gf2_set_error(flags_host[0] ? "gf2_mc_circuit_decode: a syndrome key occurs twice in a table" : "gf2_mc_circuit_decode: the hash table gave up");
+        rc = flags_host[0] ? GF2_E_ARG : GF2_E_HIP;
+    }
+    if (rc == GF2_OK) {
+        a.counts = counts_dev;
+        rc = circuit_launch<CIRC_TALLY>(ctx, circuit, a, 5);
+        if (rc == GF2_OK) rc = gf2_d2h(ctx, counts_out, counts_dev, 40);
+    }
+    for (int c = 0; c < 2; ++c)
+        for (int k = 0; k < 2; ++k) (void)gf2_dev_free(ctx, dev[c][k]);
+    (void)gf2_dev_free(ctx, flags_dev);
+    (void)gf2_dev_free(ctx, counts_dev);
+    return rc;
+}
+
+}  // extern "C"

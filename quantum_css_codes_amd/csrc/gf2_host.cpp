@@ -12,6 +12,7 @@
 #include <new>
 #include <system_error>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "gf2hip.h"
@@ -170,6 +171,66 @@ int gf2_unpack_rows_u8(const uint64_t* src, int64_t m, int64_t n, int64_t ld, ui
 
 int gf2_unpack_rows_i64(const uint64_t* src, int64_t m, int64_t n, int64_t ld, int64_t* dst, int64_t dst_stride) {
     return unpack_rows_host<int64_t>(src, m, n, ld, dst, dst_stride);
+}
+
+// Effect table of a circuit's fault locations (DESIGN.md "Circuit faults"): a serial chain of ngates column operations on two
+// nrows x n bit matrices kept by COLUMN (cx[q], cz[q]: rw words each), walked backwards from the outcome rows.  Pauli-frame
+// propagation is linear over GF(2), so the column of qubit q at the moment just after gate g says which outcomes an X (cx) or
+// a Z (cz) fault on q at that moment flips.
+int gf2_circuit_effects(const int32_t* gates, int64_t ngates, int64_t n, const uint64_t* rows_x, const uint64_t* rows_z,
+                        int64_t nrows, int64_t ld, uint64_t* eff_out, int64_t ldr, int64_t capacity, int64_t* locations_out,
+                        int64_t* nloc_out) {
+    if (!nloc_out || (ngates > 0 && !gates)) GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: null argument");
+    if (ngates < 0 || n < 1 || n > GF2_CIRCUIT_MAX_N || nrows < 0 || nrows > GF2_CIRCUIT_MAX_ROWS || capacity < 0)
+        GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: needs 1 <= n <= %d, nrows <= %d and non-negative counts", GF2_CIRCUIT_MAX_N,
+                 GF2_CIRCUIT_MAX_ROWS);
+    int64_t total = 0;
+    for (int64_t g = 0; g < ngates; ++g) {
+        const int32_t kind = gates[3 * g], a = gates[3 * g + 1], b = gates[3 * g + 2];
+        if (kind != GF2_GATE_H && kind != GF2_GATE_CNOT && kind != GF2_GATE_IDLE)
+            GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: gate %lld has unknown kind %d", (long long)g, (int)kind);
+        if (a < 0 || a >= n || (kind == GF2_GATE_CNOT && (b < 0 || b >= n)))
+            GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: gate %lld acts on a qubit outside [0, %lld)", (long long)g, (long long)n);
+        if (kind == GF2_GATE_CNOT && a == b)
+            GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: gate %lld is a CNOT of qubit %d with itself", (long long)g, (int)a);
+        total += kind == GF2_GATE_CNOT ? 2 : 1;
+    }
+    *nloc_out = total;
+    if (capacity < total) return GF2_OK;                                // (capacity 0 just counts)
+    const int64_t rw = gf2_words(nrows);
+    if (total > 0 && (!eff_out || ldr < rw || ldr < 1)) GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: eff_out needs ldr >= ceil(nrows / 64) words");
+    if (nrows > 0 && (!rows_x || !rows_z || ld < gf2_words(n))) GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: rows need ld >= ceil(n / 64) words");
+    std::vector<uint64_t> cx, cz;
+    try {
+        cx.assign((size_t)(n * rw), 0);
+        cz.assign((size_t)(n * rw), 0);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "gf2_circuit_effects: out of host memory");
+    }
+    for (int64_t r = 0; r < nrows; ++r)
+        for (int64_t q = 0; q < n; ++q) {
+            cx[q * rw + (r >> 6)] |= ((rows_x[r * ld + (q >> 6)] >> (q & 63)) & 1ull) << (r & 63);
+            cz[q * rw + (r >> 6)] |= ((rows_z[r * ld + (q >> 6)] >> (q & 63)) & 1ull) << (r & 63);
+        }
+    int64_t l = total;
+    auto emit = [&](int64_t g, int64_t q) {
+        l -= 1;
+        for (int64_t w = 0; w < ldr; ++w) {
+            eff_out[(2 * l) * ldr + w] = w < rw ? cx[q * rw + w] : 0ull;
+            eff_out[(2 * l + 1) * ldr + w] = w < rw ? cz[q * rw + w] : 0ull;
+        }
+        if (locations_out) locations_out[2 * l] = g, locations_out[2 * l + 1] = q;
+    };
+    for (int64_t g = ngates - 1; g >= 0; --g) {
+        const int32_t kind = gates[3 * g], a = gates[3 * g + 1], b = gates[3 * g + 2];
+        if (kind == GF2_GATE_CNOT) emit(g, b);
+        emit(g, a);
+        if (kind == GF2_GATE_H)
+            for (int64_t w = 0; w < rw; ++w) std::swap(cx[a * rw + w], cz[a * rw + w]);
+        else if (kind == GF2_GATE_CNOT)
+            for (int64_t w = 0; w < rw; ++w) cx[a * rw + w] ^= cx[b * rw + w], cz[b * rw + w] ^= cz[a * rw + w];
+    }
+    return GF2_OK;
 }
 
 }  // extern "C"

@@ -43,6 +43,7 @@ except Exception:                                   # pragma: no cover - pyquil 
 
 
 GATE_H, GATE_CNOT = 0, 1                            # kinds of a gate-array row (kind, a, b)
+GATE_IDLE = 2                                       # no action on qubit a, one fault location: circuit_noise only
 
 
 class CSSCode(QECC):
@@ -296,6 +297,37 @@ class CSSCode(QECC):
         2^r words for n <= 63 and r_1, r_2 <= 20, hash tables on the device beyond).  Returns counts: logical_x, logical_z, logical_any, uncorrectable_x, uncorrectable_z, samples."""
         from . import montecarlo
         return montecarlo.decode_local(self, num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample)
+
+    # -- build-defined: faults inside a circuit (circuit_noise.py) ----------------------------------------------
+    def circuit_monte_carlo(self, gates, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, mode=None):
+        """[build-defined]  `monte_carlo` for the final Pauli frame of a noisy circuit: every operand of every gate of `gates`
+        (rows (kind, a, b): GATE_H, GATE_CNOT, GATE_IDLE) suffers X, Y, Z with probability p_x, p_y, p_z, independently; the
+        faults propagate through the gates that follow.  Same modes and the same dict as `monte_carlo`."""
+        from . import circuit_noise
+        return circuit_noise.circuit_for(self, gates).monte_carlo(num_samples, p_x, p_y, p_z, seed=seed,
+                                                                  first_sample=first_sample, mode=mode)
+
+    def circuit_logical_error_rates(self, gates, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """[build-defined]  `logical_error_rates` for the final Pauli frame of a noisy circuit (see circuit_monte_carlo):
+        the frame's syndromes are looked up in this code's tables and the logical flips tallied by the same rule.  n <= 128."""
+        from . import circuit_noise
+        return circuit_noise.circuit_for(self, gates).logical_error_rates(num_samples, p_x, p_y, p_z, seed=seed,
+                                                                          first_sample=first_sample)
+
+    def encoder_monte_carlo(self, state, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, mode=None):
+        """[build-defined]  circuit_monte_carlo of this code's own encoder: noisy_encode_zero (state 'zero',
+        css_code.py:203-259) or noisy_encode_plus ('plus', css_code.py:261-312) -- the syndrome statistics of a freshly
+        encoded block whose preparation "is not fault tolerant"."""
+        from . import circuit_noise
+        return self.circuit_monte_carlo(circuit_noise.encoder_gates(self, state), num_samples, p_x, p_y, p_z, seed=seed,
+                                        first_sample=first_sample, mode=mode)
+
+    def encoder_logical_error_rates(self, state, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """[build-defined]  circuit_logical_error_rates of this code's own encoder.  After 'zero' only logical_x (a flipped
+        logical Z measurement) is physical, after 'plus' only logical_z; both are reported as statistics of the frame."""
+        from . import circuit_noise
+        return self.circuit_logical_error_rates(circuit_noise.encoder_gates(self, state), num_samples, p_x, p_y, p_z, seed=seed,
+                                                first_sample=first_sample)
 
 
 # -- free functions -----------------------------------------------------------------------------------------
