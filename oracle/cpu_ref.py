@@ -375,15 +375,15 @@ _cdf_cache = {}
 
 def binomial_cdf_table(t_any, nb):
     """cdf[k] = 2^32 * P(Bin(nb, q) <= k) rounded to nearest and clamped to 2^32, q = t_any / 2^32, in IEEE doubles with the
-    operation order of DESIGN.md "Sampler".  The number of errors of a segment is K = #{k < nb : u >= cdf[k]}.  Segments of more
-    than 64 qubits at q > 1/2 take the table from the complementary count nb - K ~ Bin(nb, 1 - q) ((1 - q)^nb underflows)."""
+    operation order of DESIGN.md "Sampler".  The number of errors of a segment is K = #{k < nb : u >= cdf[k]}.  At q > 1/2 the
+    table comes from the complementary count nb - K ~ Bin(nb, 1 - q) ((1 - q)^nb underflows), whatever the segment's length."""
     key = (t_any, nb)
     if key not in _cdf_cache:
-        if nb <= 64 or t_any <= (1 << 31) or t_any >= (1 << 32):
+        if t_any <= (1 << 31) or t_any >= (1 << 32):
             cdf = _binomial_cdf_direct(t_any, nb)
         else:
             other = _binomial_cdf_direct((1 << 32) - t_any, nb)
-            cdf = [1 << 32] * (nb + 1)
+            cdf = [1 << 32] * (max(nb, 64) + 1)
             for k in range(nb):
                 cdf[k] = (1 << 32) - other[nb - k - 1]
         _cdf_cache[key] = cdf

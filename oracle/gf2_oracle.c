@@ -202,10 +202,9 @@ static void binomial_cdf_direct(u64 t_any, int nb, u64* cdf) {
         pmf = pmf * (double)(nb - k) / (double)(k + 1) * q / om;
     }
 }
-/* Segments of more than 64 qubits at q > 1/2: from the complementary count nb - K ~ Bin(nb, 1 - q), whose (1 - q')^nb does
- * not underflow. */
+/* q > 1/2, any segment length: from the complementary count nb - K ~ Bin(nb, 1 - q), whose (1 - q')^nb does not underflow. */
 static void binomial_cdf(u64 t_any, int nb, u64* cdf) {
-    if (nb <= 64 || t_any <= 2147483648ull || t_any >= 4294967296ull) {
+    if (t_any <= 2147483648ull || t_any >= 4294967296ull) {
         binomial_cdf_direct(t_any, nb, cdf);
         return;
     }

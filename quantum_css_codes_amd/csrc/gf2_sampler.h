@@ -135,10 +135,11 @@ static inline void binomial_cdf_direct(uint64_t t_any, int nb, u64* cdf, int cap
         pmf = pmf * (double)(nb - k) / (double)(k + 1) * q / om;
     }
 }
-// Segments of more than 64 qubits at q > 1/2: (1 - q)^nb underflows long before q reaches 1, so the table comes from the
-// complementary count Y = nb - K ~ Bin(nb, 1 - q):  P(K <= k) = 1 - P(Y <= nb - k - 1).
+// q > 1/2, any segment length: (1 - q)^nb underflows long before q reaches 1 (at nb = 64 from q = 1 - 2^-17 on, which made every
+// qubit err with certainty), so the table comes from the complementary count Y = nb - K ~ Bin(nb, 1 - q):
+// P(K <= k) = 1 - P(Y <= nb - k - 1).
 static inline void binomial_cdf_table(uint64_t t_any, int nb, u64* cdf, int cap) {
-    if (nb <= 64 || t_any <= 2147483648ull || t_any >= 4294967296ull) {
+    if (t_any <= 2147483648ull || t_any >= 4294967296ull) {
         binomial_cdf_direct(t_any, nb, cdf, cap);
         return;
     }
