@@ -305,6 +305,31 @@ int gf2_mc_decode_hashed(gf2_ctx* ctx, int64_t n, int64_t ld, const uint64_t* h1
                          uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z,
                          uint64_t* counts_out);
 
+/* ---- weight-stratified Monte-Carlo ------------------------------------------------------------------
+ * [build-defined, DESIGN.md "Strata"]  The sampler above draws the number of errors from a 32-bit table, so an event rarer than
+ * 2^-32 per segment never occurs.  A stratum fixes the number of errors instead: stratified sample i of weight w over nb positions
+ * (the n qubits of a code, the L fault locations of a circuit; always ONE segment) is a pure function of (seed, i, w) --
+ * d = segment_draw(sample_key(seed, i), w), then for k = 0 .. w - 1 the sampler's error_draw(d, k, K := w, nb, t_1, t_2) with Floyd's
+ * rule: a uniformly random w-subset with i.i.d. kinds, X : Y : Z = k_x : k_y : k_z (t_1 = quantise(k_x / s), t_2 =
+ * quantise((k_x + k_y) / s), s = k_x + k_y + k_z > 0; a negative weight or s = 0 is GF2_E_ARG).  The tallies f_w of the strata
+ * combine on the host, in double precision, to P_L(p) = sum_w C(nb, w) p^w (1 - p)^(nb - w) f_w for every p at once. */
+#define GF2_STRATA_MAX                  256     /* strata per call                                                 */
+#define GF2_STRATUM_MAX_POSITIONS  (1 << 20)    /* gf2_stratum_errors: nb                                          */
+
+/* The definition on the host (no GPU needed): packed e_x, e_z rows (lde >= ceil(nb / 64) words each, pad bits zero) of the samples
+ * first_sample .. first_sample + count - 1 of stratum w, 0 <= w <= nb, 1 <= nb <= GF2_STRATUM_MAX_POSITIONS. */
+int gf2_stratum_errors(int64_t nb, int64_t w, uint64_t seed, int64_t first_sample, int64_t count, double k_x, double k_y, double k_z,
+                       uint64_t* ex_out, uint64_t* ez_out, int64_t lde);
+
+/* gf2_mc_decode_hashed over strata: stratum s has weights[s] errors (0 <= w <= n) and samples first_sample .. first_sample +
+ * counts[s] - 1; counts_out is nstrata x 5 words in gf2_mc_decode's field order.  Column keys and hash tables are made once per
+ * call.  Any code of at most 128 qubits with 1 <= r_1, r_2 <= 127 (small ones too); nstrata <= GF2_STRATA_MAX. */
+int gf2_mc_decode_strata(gf2_ctx* ctx, int64_t n, int64_t ld, const uint64_t* h1, int64_t r1, const uint64_t* keys1,
+                         const uint64_t* corr1, int64_t entries1, const uint64_t* h2, int64_t r2, const uint64_t* keys2,
+                         const uint64_t* corr2, int64_t entries2, const uint64_t* x_operator, const uint64_t* z_operator,
+                         uint64_t seed, int64_t first_sample, int64_t nstrata, const int32_t* weights, const int64_t* counts,
+                         double k_x, double k_y, double k_z, uint64_t* counts_out);
+
 /* ---- circuit-level faults of a Clifford circuit -------------------------------------------------------
  * [build-defined; the question the docstrings of noisy_encode_zero / noisy_encode_plus raise, css_code.py:203-312: "any
  * physical errors that occur during preparation may create many correlated errors in the code block"]  A Pauli-frame
@@ -359,6 +384,14 @@ int gf2_mc_circuit_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, 
                           int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
                           uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z,
                           uint64_t* counts_out);
+
+/* gf2_mc_circuit_decode over strata (see "weight-stratified Monte-Carlo"): exactly weights[s] faults among the circuit's L
+ * locations, 0 <= weights[s] <= min(L, GF2_CIRCUIT_STRATUM_MAX_WEIGHT); counts_out is nstrata x 5 words. */
+#define GF2_CIRCUIT_STRATUM_MAX_WEIGHT 16
+int gf2_mc_circuit_decode_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                                 int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                                 uint64_t seed, int64_t first_sample, int64_t nstrata, const int32_t* weights, const int64_t* counts,
+                                 double k_x, double k_y, double k_z, uint64_t* counts_out);
 
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange

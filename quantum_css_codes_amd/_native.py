@@ -21,6 +21,7 @@ LAYOUT_SAMPLE_MAJOR, LAYOUT_BIT_SLICED, LAYOUT_TILED = 0, 1, 2
 HIST_FULL, HIST_WEIGHT = 0, 1
 GATE_H, GATE_CNOT, GATE_IDLE = 0, 1, 2
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
+STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 K_SYNDROME, K_HIST, K_SAMPLER, K_ELIM = 0, 1, 2, 3
 # routing flags of a context and its tunables: the few a caller needs are in include/gf2hip.h (F_MC_DENSE, F_RREF_SEQUENTIAL,
 # F_NORMALIZE_SEQUENTIAL, OPT_SLAB_PASS_LOG2, OPT_MC_CHUNK_LOG2), the rest -- routes for the parity tests and the A/B scripts -- in
@@ -105,6 +106,9 @@ SIGNATURES = {
                       ctypes.c_double, _p],
     "gf2_mc_decode_hashed": [_p, _c_i64, _c_i64, _p, _c_i64, _p, _p, _c_i64, _p, _c_i64, _p, _p, _c_i64, _p, _p, _c_u64, _c_i64, _c_i64,
                              ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
+    "gf2_stratum_errors": [_c_i64, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p, _p, _c_i64],
+    "gf2_mc_decode_strata": [_p, _c_i64, _c_i64, _p, _c_i64, _p, _p, _c_i64, _p, _c_i64, _p, _p, _c_i64, _p, _p, _c_u64, _c_i64, _c_i64,
+                             _p, _p, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
     "gf2_mc_run": [_p, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                    ctypes.c_int, _p, _c_i64, _p, _c_i64],
     "gf2_circuit_effects": [_p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _c_i64, _c_i64, _p, ctypes.POINTER(_c_i64)],
@@ -115,6 +119,8 @@ SIGNATURES = {
                            ctypes.c_int, _p, _c_i64, _p, _c_i64],
     "gf2_mc_circuit_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double,
                               ctypes.c_double, ctypes.c_double, _p],
+    "gf2_mc_circuit_decode_strata": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, _p, _p,
+                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
     "gf2_comm_unique_id": [_p, ctypes.c_size_t],
     "gf2_comm_create": [_p, _p, ctypes.c_int, ctypes.c_int, _pp],
     "gf2_comm_create_all": [_pp, ctypes.c_int, _pp],
@@ -300,6 +306,26 @@ def circuit_effects(gates, n, rows_x, rows_z, ldr=None):
     locations = np.zeros((max(1, total), 2), dtype=np.int64)
     check(lib().gf2_circuit_effects(*args, _ptr(eff), ldr, total, _ptr(locations), ctypes.byref(count)))
     return eff[:total], locations[:total]
+
+
+def stratum_errors(nb, w, count, kinds=(1, 1, 1), seed=0, first=0):
+    """gf2_stratum_errors (host code, no GPU): the packed (e_x, e_z) rows, count x words(nb) each, of samples [first, first + count)
+    of the stratum of weight w over nb positions (DESIGN.md "Strata")."""
+    count = int(count)
+    ld = max(1, words_for(nb))
+    ex = np.zeros((max(1, count), ld), dtype="<u8")
+    ez = np.zeros_like(ex)
+    k_x, k_y, k_z = (float(k) for k in kinds)
+    check(lib().gf2_stratum_errors(int(nb), int(w), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, k_x, k_y, k_z, _ptr(ex), _ptr(ez), ld))
+    return ex[:count], ez[:count]
+
+
+def _strata_arrays(weights, counts):
+    weights = np.ascontiguousarray(weights, dtype=np.int32).reshape(-1)
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if weights.shape != counts.shape:
+        raise ValueError("one sample count per stratum")
+    return weights, counts, np.zeros((len(weights), 5), dtype=np.uint64)
 
 
 # ---- context ----------------------------------------------------------------------------------------------
@@ -648,6 +674,18 @@ class Context(object):
                                          _ptr(arrays[5]), seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, _ptr(counts)))
         return counts
 
+    def mc_decode_strata(self, n, h1, r1, keys1, corr1, h2, r2, keys2, corr2, x_operator, z_operator, seed, first, weights, counts,
+                         k_x, k_y, k_z):
+        """gf2_mc_decode_strata: mc_decode_hashed's arrays; weights and counts per stratum.  Returns the (nstrata, 5) counts."""
+        h1, h2 = np.ascontiguousarray(h1, dtype="<u8"), np.ascontiguousarray(h2, dtype="<u8")
+        arrays = [np.ascontiguousarray(a, dtype="<u8") for a in (keys1, corr1, keys2, corr2, x_operator, z_operator)]
+        weights, counts, out = _strata_arrays(weights, counts)
+        check(lib().gf2_mc_decode_strata(self.handle, n, h1.shape[1], _ptr(h1), r1, _ptr(arrays[0]), _ptr(arrays[1]), len(arrays[1]),
+                                         _ptr(h2), r2, _ptr(arrays[2]), _ptr(arrays[3]), len(arrays[3]), _ptr(arrays[4]),
+                                         _ptr(arrays[5]), seed & 0xFFFFFFFFFFFFFFFF, first, len(weights), _ptr(weights), _ptr(counts),
+                                         k_x, k_y, k_z, _ptr(out)))
+        return out
+
     # -- circuit-level faults -----------------------------------------------------------------------------
     def circuit_create(self, eff):
         return Circuit(self, eff)
@@ -685,6 +723,17 @@ class Context(object):
                                           e1, r2, _ptr(k2) if e2 else None, None if f2 is None or not e2 else _ptr(f2), e2,
                                           seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, _ptr(counts)))
         return counts
+
+    def mc_circuit_decode_strata(self, circ, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x, k_y, k_z):
+        """gf2_mc_circuit_decode_strata: mc_circuit_decode's tables; weights and counts per stratum.  Returns the (nstrata, 5) counts."""
+        k1, k2 = np.ascontiguousarray(keys1, dtype="<u8"), np.ascontiguousarray(keys2, dtype="<u8")
+        f1, f2 = np.ascontiguousarray(flips1, dtype=np.uint8), np.ascontiguousarray(flips2, dtype=np.uint8)
+        weights, counts, out = _strata_arrays(weights, counts)
+        check(lib().gf2_mc_circuit_decode_strata(self.handle, circ.handle, r1, _ptr(k1) if len(k1) else None, _ptr(f1) if len(k1) else None,
+                                                 len(k1), r2, _ptr(k2) if len(k2) else None, _ptr(f2) if len(k2) else None, len(k2),
+                                                 seed & 0xFFFFFFFFFFFFFFFF, first, len(weights), _ptr(weights), _ptr(counts),
+                                                 k_x, k_y, k_z, _ptr(out)))
+        return out
 
     # -- syndromes ----------------------------------------------------------------------------------------
     def check_create(self, packed, r, n):

@@ -166,6 +166,25 @@ class FaultCircuit(object):
         out['samples'] = int(num_samples)
         return out
 
+    def logical_error_strata(self, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0):
+        """The strata of logical_error_rates (DESIGN.md "Strata"): stratum s draws samples [first_sample, first_sample + samples[s])
+        of exactly weights[s] faults among the L locations (at most 16), kinds X : Y : Z = kinds.  Returns a montecarlo.Strata over
+        nb = L, whose rate(p_t) is the logical error rate at fault probability p_t per location."""
+        code = self._need_code()
+        if code.n > 128:
+            raise ValueError("the table decode of a circuit's final frame needs n <= 128 (where the syndrome tables exist)")
+        weights, samples, firsts, kinds = montecarlo._strata_request(weights, samples, kinds, first_sample)
+        limit = min(self.num_locations, _native.CIRCUIT_STRATUM_MAX_WEIGHT)
+        if any(w < 0 or w > limit for w in weights):
+            raise ValueError("a circuit stratum's weight lies in [0, min(L = %d, %d)]" % (self.num_locations, _native.CIRCUIT_STRATUM_MAX_WEIGHT))
+        keys1, flips1, keys2, flips2 = self._tables()
+        ctx, circ = _native.default_context(), self.device()
+        counts = np.zeros((len(weights), len(montecarlo.DECODE_FIELDS)), dtype=np.uint64)
+        for first, rows in montecarlo._strata_calls(firsts):
+            counts[rows] = ctx.mc_circuit_decode_strata(circ, code.r_1, keys1, flips1, code.r_2, keys2, flips2, int(seed), int(first),
+                                                        [weights[s] for s in rows], samples[rows], *kinds)
+        return montecarlo.Strata(self.num_locations, weights, samples, counts, kinds)
+
     # The two with montecarlo.run_sharded's / decode_sharded's local_fn signature (the code argument must be this circuit's).
     def run_local(self, code, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, mode=None):
         if code is not self.code:
@@ -176,6 +195,12 @@ class FaultCircuit(object):
         if code is not self.code:
             raise ValueError("this circuit was made for another code object")
         return self.logical_error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample)
+
+    def strata_local(self, code, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0):
+        """logical_error_strata with montecarlo.strata_sharded's local_fn signature."""
+        if code is not self.code:
+            raise ValueError("this circuit was made for another code object")
+        return self.logical_error_strata(weights, samples, kinds=kinds, seed=seed, first_sample=first_sample)
 
 
 def circuit_for(code, gates):

@@ -14,6 +14,10 @@
 // (otherwise every fault reads its effect through L2), one 512-bit "taken" map per lane for Floyd's rule (17 dwords apart: the odd
 // stride keeps the lanes of a wavefront on different banks), and the privatised bins or the five counts.  The map is only touched
 // by samples with at least two faults in a segment: a segment's first fault can meet no earlier one.
+//
+// STRATUM (DESIGN.md "Strata"): every sample has exactly a.weight <= CIRC_STRATUM_MAX faults in ONE segment over all L locations, so
+// there is no CDF table and no map (512 bits would not cover L anyway): the earlier picks stay in registers, compared with
+// constant indices in a fully unrolled loop whose every trip is guarded by the uniform k < weight.
 #include <new>
 
 #include "gf2_internal.h"
@@ -24,6 +28,7 @@
 #define CIRC_TAKEN_STRIDE 17                   // dwords per lane: 16 hold the 512 bits
 #define CIRC_EFF_LDS_BYTES 20480               // effect tables up to this size are staged in LDS
 #define CIRC_BINS_LDS 4096                     // both histograms together, privatised in LDS up to this many bins
+#define CIRC_STRATUM_MAX GF2_CIRCUIT_STRATUM_MAX_WEIGHT
 
 struct gf2_circuit {
     int64_t locations, ldr;
@@ -39,6 +44,7 @@ struct CircuitArgs {
     u64 seed;
     int64_t first_sample, count;
     SegTables th;
+    int weight;                                // STRATUM only: faults per sample (th carries t_1 and t_2 only)
     // store
     u64* out;
     int64_t ldo;
@@ -52,15 +58,44 @@ struct CircuitArgs {
     u64* counts;
 };
 
-template <int LDR, int EPI, bool STAGED>
+// The faults of a stratified sample XOR-ed into out[]: the at most CIRC_STRATUM_MAX earlier picks in registers (constant indices after
+// unrolling: nothing goes to scratch), every trip guarded by the uniform k < a.weight.
+template <int LDR>
+__device__ __forceinline__ void stratum_faults(const CircuitArgs& a, const u64* eff, u64 ks, u64 (&out)[LDR]) {
+    const u64 d = segment_draw(ks, (u64)a.weight);
+    unsigned int picks[CIRC_STRATUM_MAX];
+#pragma unroll
+    for (int k = 0; k < CIRC_STRATUM_MAX; ++k) {
+        if (k < a.weight) {
+            unsigned int t, kind;
+            error_draw(d, k, a.weight, a.locations, a.th.t_1, a.th.t_2, &t, &kind);
+            bool seen = false;
+#pragma unroll
+            for (int q = 0; q < k; ++q) seen |= picks[q] == t;
+            picks[k] = seen ? (unsigned int)(a.locations - a.weight + k) : t;              // Floyd's rule; below L either way
+            const u64* e = eff + (size_t)(2 * picks[k]) * LDR;
+            if (kind & 1u) {
+#pragma unroll
+                for (int w = 0; w < LDR; ++w) out[w] ^= e[w];
+            }
+            if (kind & 2u) {
+#pragma unroll
+                for (int w = 0; w < LDR; ++w) out[w] ^= e[LDR + w];
+            }
+        }
+    }
+}
+
+template <int LDR, int EPI, bool STAGED, bool STRATUM = false>
 __global__ __launch_bounds__(CIRC_THREADS) void circuit_kernel(CircuitArgs a) {
     extern __shared__ u64 circ_lds[];
-    u64* cdf_lds = circ_lds;                                                       // [2][GF2_SEG_CDF]
-    u64* eff_lds = circ_lds + 2 * GF2_SEG_CDF;
+    u64* cdf_lds = circ_lds;                                                       // [2][GF2_SEG_CDF]  (STRATUM: neither tables nor maps)
+    u64* eff_lds = circ_lds + (STRATUM ? 0 : 2 * GF2_SEG_CDF);
     unsigned int* taken = (unsigned int*)(eff_lds + (STAGED ? 2 * a.locations * LDR : 0));
-    unsigned int* bins = taken + CIRC_THREADS * CIRC_TAKEN_STRIDE;                  // histograms: nbz + nbx; tally: 5
-    for (int i = threadIdx.x; i < 2 * GF2_SEG_CDF; i += blockDim.x)
-        if (a.th.nseg > 1 || i >= GF2_SEG_CDF) cdf_lds[i] = a.th.cdf[i];            // (one segment: only the last one's table is read)
+    unsigned int* bins = taken + (STRATUM ? 0 : CIRC_THREADS * CIRC_TAKEN_STRIDE);  // histograms: nbz + nbx; tally: 5
+    if (!STRATUM)
+        for (int i = threadIdx.x; i < 2 * GF2_SEG_CDF; i += blockDim.x)
+            if (a.th.nseg > 1 || i >= GF2_SEG_CDF) cdf_lds[i] = a.th.cdf[i];        // (one segment: only the last one's table is read)
     if (STAGED)
         for (int i = threadIdx.x; i < 2 * a.locations * LDR; i += blockDim.x) eff_lds[i] = a.eff[i];
     if (EPI == CIRC_HIST && a.priv)
@@ -76,7 +111,8 @@ __global__ __launch_bounds__(CIRC_THREADS) void circuit_kernel(CircuitArgs a) {
         u64 out[LDR];
 #pragma unroll
         for (int w = 0; w < LDR; ++w) out[w] = 0;
-        for (int s = 0; s < a.th.nseg; ++s) {
+        if constexpr (STRATUM) stratum_faults<LDR>(a, eff, ks, out);
+        for (int s = 0; s < (STRATUM ? 0 : a.th.nseg); ++s) {
             const bool last = s == a.th.nseg - 1;
             const int nb = last ? a.th.nb_last : GF2_SEG_BITS;
             const u64 d = segment_draw(ks, (u64)s);
@@ -160,7 +196,16 @@ __global__ __launch_bounds__(CIRC_THREADS) void circuit_kernel(CircuitArgs a) {
 }
 
 template <int LDR, int EPI>
-static void circuit_launch_ldr(gf2_ctx* ctx, const CircuitArgs& a, bool staged, unsigned blocks, size_t lds) {
+static void circuit_launch_ldr(gf2_ctx* ctx, const CircuitArgs& a, bool staged, bool stratum, unsigned blocks, size_t lds) {
+    if constexpr (EPI == CIRC_TALLY && LDR >= 3 && LDR <= 5) {
+        if (stratum) {
+            if (staged)
+                hipLaunchKernelGGL((circuit_kernel<LDR, EPI, true, true>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+            else
+                hipLaunchKernelGGL((circuit_kernel<LDR, EPI, false, true>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+            return;
+        }
+    }
     if (staged)
         hipLaunchKernelGGL((circuit_kernel<LDR, EPI, true>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
     else
@@ -168,11 +213,13 @@ static void circuit_launch_ldr(gf2_ctx* ctx, const CircuitArgs& a, bool staged, 
 }
 
 // bins: LDS dwords behind the taken maps.  The histogram and tally epilogues exist for the 3 to 5 words of the Monte-Carlo layout.
+// (stratum: the tally epilogue only)
 template <int EPI>
-static int circuit_launch(gf2_ctx* ctx, const gf2_circuit* circ, CircuitArgs& a, int bins) {
+static int circuit_launch(gf2_ctx* ctx, const gf2_circuit* circ, CircuitArgs& a, int bins, bool stratum = false) {
     const size_t eff_bytes = (size_t)2 * circ->locations * circ->ldr * 8;
     const bool staged = eff_bytes <= CIRC_EFF_LDS_BYTES;
-    const size_t lds = (size_t)2 * GF2_SEG_CDF * 8 + (staged ? eff_bytes : 0) + (size_t)CIRC_THREADS * CIRC_TAKEN_STRIDE * 4 + (size_t)bins * 4;
+    const size_t lds = (stratum ? 0 : (size_t)2 * GF2_SEG_CDF * 8 + (size_t)CIRC_THREADS * CIRC_TAKEN_STRIDE * 4) + (staged ? eff_bytes : 0) +
+                       (size_t)bins * 4;
     a.eff = circ->eff_dev;
     a.locations = (int)circ->locations;
     int64_t blocks = gf2_cdiv(a.count, CIRC_THREADS * 16);
@@ -180,16 +227,16 @@ static int circuit_launch(gf2_ctx* ctx, const gf2_circuit* circ, CircuitArgs& a,
     if (blocks < 1) blocks = 1;
     GF2_TRY(gf2_prof_begin(ctx, GF2_K_SAMPLER));
     switch (circ->ldr) {
-        case 3: circuit_launch_ldr<3, EPI>(ctx, a, staged, (unsigned)blocks, lds); break;
-        case 4: circuit_launch_ldr<4, EPI>(ctx, a, staged, (unsigned)blocks, lds); break;
-        case 5: circuit_launch_ldr<5, EPI>(ctx, a, staged, (unsigned)blocks, lds); break;
+        case 3: circuit_launch_ldr<3, EPI>(ctx, a, staged, stratum, (unsigned)blocks, lds); break;
+        case 4: circuit_launch_ldr<4, EPI>(ctx, a, staged, stratum, (unsigned)blocks, lds); break;
+        case 5: circuit_launch_ldr<5, EPI>(ctx, a, staged, stratum, (unsigned)blocks, lds); break;
         default:
             if (EPI == CIRC_STORE) switch (circ->ldr) {
-                case 1: circuit_launch_ldr<1, CIRC_STORE>(ctx, a, staged, (unsigned)blocks, lds); break;
-                case 2: circuit_launch_ldr<2, CIRC_STORE>(ctx, a, staged, (unsigned)blocks, lds); break;
-                case 6: circuit_launch_ldr<6, CIRC_STORE>(ctx, a, staged, (unsigned)blocks, lds); break;
-                case 7: circuit_launch_ldr<7, CIRC_STORE>(ctx, a, staged, (unsigned)blocks, lds); break;
-                case 8: circuit_launch_ldr<8, CIRC_STORE>(ctx, a, staged, (unsigned)blocks, lds); break;
+                case 1: circuit_launch_ldr<1, CIRC_STORE>(ctx, a, staged, false, (unsigned)blocks, lds); break;
+                case 2: circuit_launch_ldr<2, CIRC_STORE>(ctx, a, staged, false, (unsigned)blocks, lds); break;
+                case 6: circuit_launch_ldr<6, CIRC_STORE>(ctx, a, staged, false, (unsigned)blocks, lds); break;
+                case 7: circuit_launch_ldr<7, CIRC_STORE>(ctx, a, staged, false, (unsigned)blocks, lds); break;
+                case 8: circuit_launch_ldr<8, CIRC_STORE>(ctx, a, staged, false, (unsigned)blocks, lds); break;
             }
     }
     GF2_TRY(gf2_prof_end(ctx));
@@ -213,6 +260,68 @@ static int circuit_layout(const char* who, const gf2_circuit* circ, int64_t r1, 
         GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits or the two parity bits", who);
     return GF2_OK;
 }
+
+static int circuit_check_tables(const char* who, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, const uint64_t* keys2,
+                                const uint8_t* flips2, int64_t entries2) {
+    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !flips1)) || (entries2 && (!keys2 || !flips2)))
+        GF2_FAIL(GF2_E_ARG, "%s: bad table (a null array with entries > 0, or a negative count)", who);
+    if (entries1 > (int64_t)TBL_HASH_MAX_ENTRIES || entries2 > (int64_t)TBL_HASH_MAX_ENTRIES) GF2_FAIL(GF2_E_ARG, "%s: table too large", who);
+    return GF2_OK;
+}
+
+// The device side of the tally's tables (a.kwx and a.kwz set): keys in hash tables, one flip byte per entry, zeroed counts.
+// Side 0: key_x against parity_check_c2's table; side 1: key_z against parity_check_c1's.  Freed with the object.
+struct CircuitTables {
+    gf2_ctx* ctx;
+    HashAlloc tabs[2];
+    void* dev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    u64* counts_dev = nullptr;
+    int* flags_dev = nullptr;
+    explicit CircuitTables(gf2_ctx* c) : ctx(c), tabs{HashAlloc(c), HashAlloc(c)} {}
+    ~CircuitTables() {
+        for (int c = 0; c < 2; ++c)
+            for (int k = 0; k < 2; ++k) (void)gf2_dev_free(ctx, dev[c][k]);
+        (void)gf2_dev_free(ctx, flags_dev);
+        (void)gf2_dev_free(ctx, counts_dev);
+    }
+    int make(const char* who, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, const uint64_t* keys2, const uint8_t* flips2,
+             int64_t entries2, int64_t ncounts, CircuitArgs* a) {
+        const int64_t es[2] = {entries2, entries1};
+        const uint64_t* ks[2] = {keys2, keys1};
+        const uint8_t* fs[2] = {flips2, flips1};
+        const int kws[2] = {a->kwx, a->kwz};
+        int rc = gf2_dev_alloc(ctx, 16, (void**)&flags_dev);
+        if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, (size_t)ncounts * 8, (void**)&counts_dev);
+        if (rc == GF2_OK && (hipMemsetAsync(flags_dev, 0, 16, ctx->stream) != hipSuccess ||
+                             hipMemsetAsync(counts_dev, 0, (size_t)ncounts * 8, ctx->stream) != hipSuccess))
+            rc = GF2_E_HIP;
+        for (int c = 0; c < 2 && rc == GF2_OK; ++c) {
+            const int kw = kws[c];
+            const size_t ent = (size_t)(es[c] > 0 ? es[c] : 1);
+            rc = gf2_dev_alloc(ctx, ent * 8 * kw, &dev[c][0]);
+            if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, ent, &dev[c][1]);
+            if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][0], ks[c], (size_t)es[c] * 8 * kw);
+            if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][1], fs[c], (size_t)es[c]);
+            if (rc == GF2_OK) rc = tabs[c].make(pow2_at_least((u64)es[c] * 2 + 2), kw);
+            if (rc == GF2_OK && es[c]) {
+                hipLaunchKernelGGL(table_insert_kernel, dim3((unsigned)gf2_cdiv(es[c], 256)), dim3(256), 0, ctx->stream, tabs[c].tab,
+                                   (const u64*)dev[c][0], kw, es[c], flags_dev);
+                if (hipGetLastError() != hipSuccess) rc = GF2_E_HIP;
+            }
+            a->tab[c] = tabs[c].tab;
+            a->flips[c] = (const unsigned char*)dev[c][1];
+        }
+        int flags_host[2] = {0, 0};
+        if (rc == GF2_OK && (hipMemcpyAsync(flags_host, flags_dev, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                             hipStreamSynchronize(ctx->stream) != hipSuccess))
+            rc = GF2_E_HIP;
+        if (rc == GF2_OK && (flags_host[0] || flags_host[1])) {
+            gf2_set_error(flags_host[0] ? "%s: a syndrome key occurs twice in a table" : "%s: the hash table gave up", who);
+            rc = flags_host[0] ? GF2_E_ARG : GF2_E_HIP;
+        }
+        return rc;
+    }
+};
 
 extern "C" {
 
@@ -317,10 +426,7 @@ int gf2_mc_circuit_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, 
     if (!ctx || !circuit || !counts_out) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode: null argument");
     CircuitArgs a = {};
     GF2_TRY(circuit_layout("gf2_mc_circuit_decode", circuit, r1, r2, &a));
-    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !flips1)) || (entries2 && (!keys2 || !flips2)))
-        GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode: bad table (a null array with entries > 0, or a negative count)");
-    if (entries1 > (int64_t)TBL_HASH_MAX_ENTRIES || entries2 > (int64_t)TBL_HASH_MAX_ENTRIES)
-        GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode: table too large");
+    GF2_TRY(circuit_check_tables("gf2_mc_circuit_decode", keys1, flips1, entries1, keys2, flips2, entries2));
     if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode: negative range");
     GF2_TRY(check_probabilities(p_x, p_y, p_z));
     GF2_TRY(gf2_ctx_activate(ctx));
@@ -330,53 +436,48 @@ int gf2_mc_circuit_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, 
     a.seed = seed;
     a.first_sample = first_sample;
     a.count = count;
-    // side 0: key_x against parity_check_c2's table; side 1: key_z against parity_check_c1's
-    const int64_t es[2] = {entries2, entries1};
-    const uint64_t* ks[2] = {keys2, keys1};
-    const uint8_t* fs[2] = {flips2, flips1};
-    const int kws[2] = {a.kwx, a.kwz};
-    HashAlloc tabs[2] = {HashAlloc(ctx), HashAlloc(ctx)};
-    void* dev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    u64* counts_dev = nullptr;
-    int* flags_dev = nullptr;
-    int rc = gf2_dev_alloc(ctx, 16, (void**)&flags_dev);
-    if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, 40, (void**)&counts_dev);
-    if (rc == GF2_OK && (hipMemsetAsync(flags_dev, 0, 16, ctx->stream) != hipSuccess || hipMemsetAsync(counts_dev, 0, 40, ctx->stream) != hipSuccess))
-        rc = GF2_E_HIP;
-    for (int c = 0; c < 2 && rc == GF2_OK; ++c) {
-        const int kw = kws[c];
-        const size_t ent = (size_t)(es[c] > 0 ? es[c] : 1);
-        rc = gf2_dev_alloc(ctx, ent * 8 * kw, &dev[c][0]);
-        if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, ent, &dev[c][1]);
-        if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][0], ks[c], (size_t)es[c] * 8 * kw);
-        if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][1], fs[c], (size_t)es[c]);
-        if (rc == GF2_OK) rc = tabs[c].make(pow2_at_least((u64)es[c] * 2 + 2), kw);
-        if (rc == GF2_OK && es[c]) {
-            hipLaunchKernelGGL(table_insert_kernel, dim3((unsigned)gf2_cdiv(es[c], 256)), dim3(256), 0, ctx->stream, tabs[c].tab,
-                               (const u64*)dev[c][0], kw, es[c], flags_dev);
-            if (hipGetLastError() != hipSuccess) rc = GF2_E_HIP;
-        }
-        a.tab[c] = tabs[c].tab;
-        a.flips[c] = (const unsigned char*)dev[c][1];
+    CircuitTables tables(ctx);
+    GF2_TRY(tables.make("gf2_mc_circuit_decode", keys1, flips1, entries1, keys2, flips2, entries2, 5, &a));
+    a.counts = tables.counts_dev;
+    GF2_TRY(circuit_launch<CIRC_TALLY>(ctx, circuit, a, 5));
+    return gf2_d2h(ctx, counts_out, tables.counts_dev, 40);
+}
+
+int gf2_mc_circuit_decode_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                                 int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                                 uint64_t seed, int64_t first_sample, int64_t nstrata, const int32_t* weights, const int64_t* counts,
+                                 double k_x, double k_y, double k_z, uint64_t* counts_out) {
+    if (!ctx || !circuit || !counts_out) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode_strata: null argument");
+    CircuitArgs a = {};
+    GF2_TRY(circuit_layout("gf2_mc_circuit_decode_strata", circuit, r1, r2, &a));
+    GF2_TRY(circuit_check_tables("gf2_mc_circuit_decode_strata", keys1, flips1, entries1, keys2, flips2, entries2));
+    if (nstrata < 0 || nstrata > GF2_STRATA_MAX || (nstrata && (!weights || !counts)))
+        GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode_strata: needs 0 <= nstrata <= %d and their weights and counts", GF2_STRATA_MAX);
+    if (first_sample < 0) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode_strata: negative range");
+    int64_t total = 0;
+    for (int64_t s = 0; s < nstrata; ++s) {
+        if (weights[s] < 0 || weights[s] > CIRC_STRATUM_MAX || weights[s] > circuit->locations)
+            GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode_strata: stratum %lld has weight %d outside [0, min(L = %lld, %d)]", (long long)s,
+                     (int)weights[s], (long long)circuit->locations, CIRC_STRATUM_MAX);
+        if (counts[s] < 0) GF2_FAIL(GF2_E_ARG, "gf2_mc_circuit_decode_strata: stratum %lld has a negative sample count", (long long)s);
+        total += counts[s] > 0;
     }
-    int flags_host[2] = {0, 0};
-    if (rc == GF2_OK && (hipMemcpyAsync(flags_host, flags_dev, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                         hipStreamSynchronize(ctx->stream) != hipSuccess))
-        rc = GF2_E_HIP;
-    if (rc == GF2_OK && (flags_host[0] || flags_host[1])) {
-        gf2_set_error(flags_host[0] ? "gf2_mc_circuit_decode: a syndrome key occurs twice in a table" : "gf2_mc_circuit_decode: the hash table gave up");
-        rc = flags_host[0] ? GF2_E_ARG : GF2_E_HIP;
+    GF2_TRY(stratum_thresholds("gf2_mc_circuit_decode_strata", k_x, k_y, k_z, &a.th.t_1, &a.th.t_2));
+    GF2_TRY(gf2_ctx_activate(ctx));
+    for (int64_t k = 0; k < 5 * nstrata; ++k) counts_out[k] = 0;
+    if (total == 0) return GF2_OK;
+    a.seed = seed;
+    a.first_sample = first_sample;
+    CircuitTables tables(ctx);
+    GF2_TRY(tables.make("gf2_mc_circuit_decode_strata", keys1, flips1, entries1, keys2, flips2, entries2, 5 * nstrata, &a));
+    for (int64_t s = 0; s < nstrata; ++s) {
+        if (counts[s] == 0) continue;
+        a.weight = (int)weights[s];
+        a.count = counts[s];
+        a.counts = tables.counts_dev + 5 * s;
+        GF2_TRY(circuit_launch<CIRC_TALLY>(ctx, circuit, a, 5, true));
     }
-    if (rc == GF2_OK) {
-        a.counts = counts_dev;
-        rc = circuit_launch<CIRC_TALLY>(ctx, circuit, a, 5);
-        if (rc == GF2_OK) rc = gf2_d2h(ctx, counts_out, counts_dev, 40);
-    }
-    for (int c = 0; c < 2; ++c)
-        for (int k = 0; k < 2; ++k) (void)gf2_dev_free(ctx, dev[c][k]);
-    (void)gf2_dev_free(ctx, flags_dev);
-    (void)gf2_dev_free(ctx, counts_dev);
-    return rc;
+    return gf2_d2h(ctx, counts_out, tables.counts_dev, (size_t)nstrata * 40);
 }
 
 }  // extern "C"

@@ -233,5 +233,53 @@ int gf2_circuit_effects(const int32_t* gates, int64_t ngates, int64_t n, const u
     return GF2_OK;
 }
 
+// A stratum's errors (DESIGN.md "Strata"), the host statement of what decode_strata_kernel and circuit_kernel's stratum mode draw:
+// the generator of gf2_sampler.h written out once more in plain C++ (that header is device code).
+static inline uint64_t host_mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+static inline uint64_t host_quantise(double x) {                          // threshold in [0, 2^32]
+    const double t = __builtin_floor(x * 4294967296.0 + 0.5);
+    if (!(t > 0.0)) return 0;
+    if (t >= 4294967296.0) return 4294967296ull;
+    return (uint64_t)t;
+}
+
+int gf2_stratum_errors(int64_t nb, int64_t w, uint64_t seed, int64_t first_sample, int64_t count, double k_x, double k_y, double k_z,
+                       uint64_t* ex_out, uint64_t* ez_out, int64_t lde) {
+    if (nb < 1 || nb > GF2_STRATUM_MAX_POSITIONS)
+        GF2_FAIL(GF2_E_ARG, "gf2_stratum_errors: needs 1 <= nb <= %d (2^20) positions, got %lld", GF2_STRATUM_MAX_POSITIONS, (long long)nb);
+    if (w < 0 || w > nb) GF2_FAIL(GF2_E_ARG, "gf2_stratum_errors: weight %lld outside [0, nb = %lld]", (long long)w, (long long)nb);
+    if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "gf2_stratum_errors: negative range");
+    if (lde < gf2_words(nb)) GF2_FAIL(GF2_E_ARG, "gf2_stratum_errors: lde must be at least ceil(nb / 64) words");
+    const double s = k_x + k_y + k_z;
+    if (!(k_x >= 0.0) || !(k_y >= 0.0) || !(k_z >= 0.0) || !(s > 0.0) || !(s < __builtin_inf()))
+        GF2_FAIL(GF2_E_ARG, "gf2_stratum_errors: the kind weights must be non-negative and finite with a positive sum");
+    if (count > 0 && (!ex_out || !ez_out)) GF2_FAIL(GF2_E_ARG, "gf2_stratum_errors: null buffer");
+    const uint64_t t_1 = host_quantise(k_x / s), t_2 = host_quantise((k_x + k_y) / s);
+    const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
+    for (int64_t i = 0; i < count; ++i) {
+        uint64_t* const ex = ex_out + i * lde;
+        uint64_t* const ez = ez_out + i * lde;
+        for (int64_t q = 0; q < lde; ++q) ex[q] = 0, ez[q] = 0;
+        const uint64_t ks = host_mix64(seed + golden * ((uint64_t)(first_sample + i) + 1));
+        const uint64_t d = host_mix64(ks + stream * ((uint64_t)w + 1));          // the segment slot carries the weight
+        for (int64_t k = 0; k < w; ++k) {
+            const uint64_t v = host_mix64(d + golden * (uint64_t)(k + 1));
+            const uint64_t j = (uint64_t)(nb - w + k);
+            const uint64_t t = ((v >> 32) * (j + 1)) >> 32;                       // Floyd: a candidate in [0, j]
+            const bool taken = ((ex[t >> 6] | ez[t >> 6]) >> (t & 63)) & 1ull;    // (every kind sets e_x or e_z)
+            const uint64_t pos = taken ? j : t;
+            const uint64_t c = v & 0xFFFFFFFFull;
+            if (c < t_2) ex[pos >> 6] |= 1ull << (pos & 63);
+            if (c >= t_1) ez[pos >> 6] |= 1ull << (pos & 63);
+        }
+    }
+    return GF2_OK;
+}
+
 }  // extern "C"
 

@@ -168,5 +168,20 @@ static inline int make_thresholds(double p_x, double p_y, double p_z, int64_t n,
     return GF2_OK;
 }
 
+// Strata (DESIGN.md "Strata"): stratified sample i of weight w over nb positions has exactly w errors -- ONE segment, however large
+// nb is, whose slot carries the weight: d = mix64(ks + M (w + 1)), then error_draw(d, k, K := w, nb, t_1, t_2) for k = 0 .. w - 1 with
+// Floyd's rule as above.  No CDF table; the strata of one seed are independent streams.
+__host__ __device__ static inline u64 stratum_draw(u64 seed, u64 sample, int w) { return segment_draw(sample_key(seed, sample), (u64)w); }
+
+// Only the ratios of the kind weights matter: t_1 = quantise(k_x / s), t_2 = quantise((k_x + k_y) / s), s = k_x + k_y + k_z > 0.
+static inline int stratum_thresholds(const char* who, double k_x, double k_y, double k_z, u64* t_1, u64* t_2) {
+    const double s = k_x + k_y + k_z;
+    if (!(k_x >= 0.0) || !(k_y >= 0.0) || !(k_z >= 0.0) || !(s > 0.0) || !(s < __builtin_inf()))
+        GF2_FAIL(GF2_E_ARG, "%s: the kind weights must be non-negative and finite with a positive sum", who);
+    *t_1 = gf2_quantise(k_x / s);
+    *t_2 = gf2_quantise((k_x + k_y) / s);
+    return GF2_OK;
+}
+
 // Any n: thresholds, and the two segment tables in the context's device buffer (uploaded when the rates or n change).
 int gf2_seg_tables(gf2_ctx* ctx, double p_x, double p_y, double p_z, int64_t n, SegTables* out);

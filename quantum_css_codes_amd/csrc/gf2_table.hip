@@ -734,6 +734,54 @@ struct DecodeHashArgs {
     u64* counts;
 };
 
+// One sample from its draw d and error count K on: Floyd's positions, both syndrome keys, the two lookups, residuals and parities.
+__device__ __forceinline__ void decode_hash_sample(const DecodeHashArgs& a, const u64 (&ck)[2][128 * 2], u64 d, int K, unsigned int* local) {
+    const int nb = a.n;
+    u64 e[2][2] = {{0, 0}, {0, 0}}, chosen[2] = {0, 0};              // e[0]: X component, e[1]: Z component
+    u64 key[2][2] = {{0, 0}, {0, 0}};
+    for (int k = 0; k < K; ++k) {
+        unsigned int t, kind;
+        error_draw(d, k, K, nb, a.th.t_1, a.th.t_2, &t, &kind);
+        const unsigned int j = (unsigned int)(nb - K + k);
+        const unsigned int pos = (((t >> 6 ? chosen[1] : chosen[0]) >> (t & 63u)) & 1ull) ? j : t;
+        const u64 bit = 1ull << (pos & 63u);
+        if (pos >> 6) chosen[1] |= bit; else chosen[0] |= bit;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if ((kind >> c) & 1u) {
+                if (pos >> 6) e[c][1] |= bit; else e[c][0] |= bit;
+                key[c][0] ^= ck[c][pos * a.kw[c]];
+                if (a.kw[c] == 2) key[c][1] ^= ck[c][pos * 2 + 1];
+            }
+    }
+    bool flip[2], miss[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const u64 slot = a.kw[c] == 1 ? hash_find<1>(a.tab[c], 0ull, key[c][0]) : hash_find<2>(a.tab[c], key[c][1], key[c][0]);
+        miss[c] = slot == ~0ull;
+        u64 r0 = e[c][0], r1 = e[c][1];
+        if (!miss[c]) {                                             // css_code.py:655-657: no match leaves the error as it is
+            const u64 idx = a.tab[c].val[slot];
+            r0 ^= a.corr[c][2 * idx];
+            r1 ^= a.corr[c][2 * idx + 1];
+        }
+        flip[c] = (__popcll(a.op[c][0] & r0) + __popcll(a.op[c][1] & r1)) & 1;
+    }
+    local[0] += flip[0];
+    local[1] += flip[1];
+    local[2] += flip[0] | flip[1];
+    local[3] += miss[0];
+    local[4] += miss[1];
+}
+
+__device__ __forceinline__ void decode_hash_flush(const unsigned int* local, unsigned int* acc, u64* counts) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        if (local[k]) atomicAdd(&acc[k], local[k]);
+    __syncthreads();
+    if (threadIdx.x < 5 && acc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (u64)acc[threadIdx.x]);
+}
+
 __global__ __launch_bounds__(256) void decode_hash_kernel(DecodeHashArgs a) {
     __shared__ unsigned int acc[5];
     __shared__ u64 cdf_lds[GF2_SEG_CDF];
@@ -744,52 +792,116 @@ __global__ __launch_bounds__(256) void decode_hash_kernel(DecodeHashArgs a) {
         for (int i = threadIdx.x; i < a.n * a.kw[c]; i += blockDim.x) ck[c][i] = a.colkey[c][i];
     __syncthreads();
     unsigned int local[5] = {0, 0, 0, 0, 0};
-    const int nb = a.n;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += stride) {
         const u64 d = segment_draw(sample_key(a.seed, (u64)(a.first_sample + i)), 0);
-        const int K = error_count(d, nb, cdf_lds);
-        u64 e[2][2] = {{0, 0}, {0, 0}}, chosen[2] = {0, 0};          // e[0]: X component, e[1]: Z component
-        u64 key[2][2] = {{0, 0}, {0, 0}};
-        for (int k = 0; k < K; ++k) {
-            unsigned int t, kind;
-            error_draw(d, k, K, nb, a.th.t_1, a.th.t_2, &t, &kind);
-            const unsigned int j = (unsigned int)(nb - K + k);
-            const unsigned int pos = (((t >> 6 ? chosen[1] : chosen[0]) >> (t & 63u)) & 1ull) ? j : t;
-            const u64 bit = 1ull << (pos & 63u);
-            if (pos >> 6) chosen[1] |= bit; else chosen[0] |= bit;
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-                if ((kind >> c) & 1u) {
-                    if (pos >> 6) e[c][1] |= bit; else e[c][0] |= bit;
-                    key[c][0] ^= ck[c][pos * a.kw[c]];
-                    if (a.kw[c] == 2) key[c][1] ^= ck[c][pos * 2 + 1];
-                }
-        }
-        bool flip[2], miss[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const u64 slot = a.kw[c] == 1 ? hash_find<1>(a.tab[c], 0ull, key[c][0]) : hash_find<2>(a.tab[c], key[c][1], key[c][0]);
-            miss[c] = slot == ~0ull;
-            u64 r0 = e[c][0], r1 = e[c][1];
-            if (!miss[c]) {                                         // css_code.py:655-657: no match leaves the error as it is
-                const u64 idx = a.tab[c].val[slot];
-                r0 ^= a.corr[c][2 * idx];
-                r1 ^= a.corr[c][2 * idx + 1];
-            }
-            flip[c] = (__popcll(a.op[c][0] & r0) + __popcll(a.op[c][1] & r1)) & 1;
-        }
-        local[0] += flip[0];
-        local[1] += flip[1];
-        local[2] += flip[0] | flip[1];
-        local[3] += miss[0];
-        local[4] += miss[1];
+        decode_hash_sample(a, ck, d, error_count(d, a.n, cdf_lds), local);
     }
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-        if (local[k]) atomicAdd(&acc[k], local[k]);
+    decode_hash_flush(local, acc, a.counts);
+}
+
+// Stratum w (DESIGN.md "Strata"): every sample has exactly w errors, so the trip count is the same scalar for every lane of the grid
+// and there is no CDF table to stage or walk.  (a.th carries t_1 and t_2 only.)
+__global__ __launch_bounds__(256) void decode_strata_kernel(DecodeHashArgs a, int w) {
+    __shared__ unsigned int acc[5];
+    __shared__ u64 ck[2][128 * 2];
+    if (threadIdx.x < 5) acc[threadIdx.x] = 0;
+    for (int c = 0; c < 2; ++c)
+        for (int i = threadIdx.x; i < a.n * a.kw[c]; i += blockDim.x) ck[c][i] = a.colkey[c][i];
     __syncthreads();
-    if (threadIdx.x < 5 && acc[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (u64)acc[threadIdx.x]);
+    unsigned int local[5] = {0, 0, 0, 0, 0};
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.count; i += stride)
+        decode_hash_sample(a, ck, stratum_draw(a.seed, (u64)(a.first_sample + i), w), w, local);
+    decode_hash_flush(local, acc, a.counts);
+}
+
+// The device side of a table decode's arguments: column keys of both checks, the tables' entries in hash tables, the corrections,
+// the operators.  Side 0: X errors against parity_check_c2; side 1: Z errors against parity_check_c1.  Freed with the object.
+struct DecodeHashSetup {
+    gf2_ctx* ctx;
+    HashAlloc tabs[2];
+    u64* dev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    u64* counts_dev = nullptr;
+    int* flags_dev = nullptr;
+    explicit DecodeHashSetup(gf2_ctx* c) : ctx(c), tabs{HashAlloc(c), HashAlloc(c)} {}
+    ~DecodeHashSetup() {
+        for (int c = 0; c < 2; ++c)
+            for (int k = 0; k < 3; ++k) (void)gf2_dev_free(ctx, dev[c][k]);
+        (void)gf2_dev_free(ctx, flags_dev);
+        (void)gf2_dev_free(ctx, counts_dev);
+    }
+    // ncounts: words of counts_dev (zeroed).  Fills a->tab, corr, colkey, kw, op, n.
+    int make(const char* who, int64_t n, int64_t ld, const uint64_t* h1, int64_t r1, const uint64_t* keys1, const uint64_t* corr1,
+             int64_t entries1, const uint64_t* h2, int64_t r2, const uint64_t* keys2, const uint64_t* corr2, int64_t entries2,
+             const uint64_t* x_operator, const uint64_t* z_operator, int64_t ncounts, DecodeHashArgs* a) {
+        a->n = (int)n;
+        for (int w = 0; w < 2; ++w) {
+            a->op[0][w] = w < ld ? z_operator[w] : 0ull;
+            a->op[1][w] = w < ld ? x_operator[w] : 0ull;
+        }
+        const uint64_t* hs[2] = {h2, h1};
+        const int64_t rs[2] = {r2, r1}, es[2] = {entries2, entries1};
+        const uint64_t* ks[2] = {keys2, keys1};
+        const uint64_t* cs[2] = {corr2, corr1};
+        int rc = gf2_dev_alloc(ctx, 16, (void**)&flags_dev);
+        if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, (size_t)ncounts * 8, (void**)&counts_dev);
+        if (rc == GF2_OK && (hipMemsetAsync(flags_dev, 0, 16, ctx->stream) != hipSuccess ||
+                             hipMemsetAsync(counts_dev, 0, (size_t)ncounts * 8, ctx->stream) != hipSuccess))
+            rc = GF2_E_HIP;
+        for (int c = 0; c < 2 && rc == GF2_OK; ++c) {
+            const int kw = rs[c] <= 63 ? 1 : 2;
+            a->kw[c] = kw;
+            std::vector<u64> colkey;
+            column_keys(hs[c], rs[c], n, ld, kw, &colkey);
+            rc = gf2_dev_alloc(ctx, colkey.size() * 8, (void**)&dev[c][0]);
+            if (rc == GF2_OK) rc = gf2_h2d(ctx, dev[c][0], colkey.data(), colkey.size() * 8);
+            const size_t ent = (size_t)(es[c] > 0 ? es[c] : 1);
+            if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, ent * 8 * kw, (void**)&dev[c][1]);
+            if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, ent * 16, (void**)&dev[c][2]);
+            if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][1], ks[c], (size_t)es[c] * 8 * kw);
+            if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][2], cs[c], (size_t)es[c] * 16);
+            if (rc == GF2_OK) rc = tabs[c].make(pow2_at_least((u64)es[c] * 2 + 2), kw);
+            if (rc == GF2_OK && es[c]) {
+                hipLaunchKernelGGL(table_insert_kernel, dim3((unsigned)gf2_cdiv(es[c], 256)), dim3(256), 0, ctx->stream, tabs[c].tab,
+                                   (const u64*)dev[c][1], kw, es[c], flags_dev);
+                if (hipGetLastError() != hipSuccess) rc = GF2_E_HIP;
+            }
+            a->tab[c] = tabs[c].tab;
+            a->corr[c] = dev[c][2];
+            a->colkey[c] = dev[c][0];
+        }
+        int flags_host[2] = {0, 0};
+        if (rc == GF2_OK && (hipMemcpyAsync(flags_host, flags_dev, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                             hipStreamSynchronize(ctx->stream) != hipSuccess))
+            rc = GF2_E_HIP;
+        if (rc == GF2_OK && (flags_host[0] || flags_host[1])) {
+            gf2_set_error(flags_host[0] ? "%s: a syndrome key occurs twice in a table" : "%s: the hash table gave up", who);
+            rc = flags_host[0] ? GF2_E_ARG : GF2_E_HIP;
+        }
+        return rc;
+    }
+};
+
+static int decode_hash_check_args(const char* who, gf2_ctx* ctx, int64_t n, int64_t ld, const uint64_t* h1, int64_t r1,
+                                  const uint64_t* keys1, const uint64_t* corr1, int64_t entries1, const uint64_t* h2, int64_t r2,
+                                  const uint64_t* keys2, const uint64_t* corr2, int64_t entries2, const uint64_t* x_operator,
+                                  const uint64_t* z_operator, const uint64_t* counts_out) {
+    if (!ctx || !h1 || !h2 || !x_operator || !z_operator || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (n < 1 || n > 128 || ld < gf2_words(n) || r1 < 1 || r2 < 1 || r1 > 127 || r2 > 127)
+        GF2_FAIL(GF2_E_ARG, "%s: needs n <= 128 and 1 <= r_1, r_2 <= 127", who);
+    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !corr1)) || (entries2 && (!keys2 || !corr2)))
+        GF2_FAIL(GF2_E_ARG, "%s: bad table", who);
+    if (entries1 > (int64_t)TBL_HASH_MAX_ENTRIES || entries2 > (int64_t)TBL_HASH_MAX_ENTRIES)
+        GF2_FAIL(GF2_E_ARG, "%s: table too large", who);
+    return GF2_OK;
+}
+
+static unsigned decode_blocks(int64_t count) {
+    int64_t blocks = gf2_cdiv(count, 256 * 16);
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    return (unsigned)blocks;
 }
 
 // h1 / h2: packed rows of the two checks (ld words each); keys: kw words per entry (kw = 1 for r <= 63, else 2; word 0 low),
@@ -799,85 +911,67 @@ extern "C" int gf2_mc_decode_hashed(gf2_ctx* ctx, int64_t n, int64_t ld, const u
                                     const uint64_t* corr2, int64_t entries2, const uint64_t* x_operator, const uint64_t* z_operator,
                                     uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z,
                                     uint64_t* counts_out) {
-    if (!ctx || !h1 || !h2 || !x_operator || !z_operator || !counts_out) GF2_FAIL(GF2_E_ARG, "gf2_mc_decode_hashed: null argument");
-    if (n < 1 || n > 128 || ld < gf2_words(n) || r1 < 1 || r2 < 1 || r1 > 127 || r2 > 127)
-        GF2_FAIL(GF2_E_ARG, "gf2_mc_decode_hashed: needs n <= 128 and 1 <= r_1, r_2 <= 127");
-    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !corr1)) || (entries2 && (!keys2 || !corr2)))
-        GF2_FAIL(GF2_E_ARG, "gf2_mc_decode_hashed: bad table");
-    if (entries1 > (int64_t)TBL_HASH_MAX_ENTRIES || entries2 > (int64_t)TBL_HASH_MAX_ENTRIES)
-        GF2_FAIL(GF2_E_ARG, "gf2_mc_decode_hashed: table too large");
+    GF2_TRY(decode_hash_check_args("gf2_mc_decode_hashed", ctx, n, ld, h1, r1, keys1, corr1, entries1, h2, r2, keys2, corr2, entries2,
+                                   x_operator, z_operator, counts_out));
     if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "gf2_mc_decode_hashed: negative range");
     GF2_TRY(gf2_ctx_activate(ctx));
     for (int k = 0; k < 5; ++k) counts_out[k] = 0;
     if (count == 0) return GF2_OK;
     DecodeHashArgs a;
     GF2_TRY(gf2_seg_tables(ctx, p_x, p_y, p_z, n, &a.th));
-    a.n = (int)n;
     a.seed = seed;
     a.first_sample = first_sample;
     a.count = count;
-    for (int w = 0; w < 2; ++w) {
-        a.op[0][w] = w < ld ? z_operator[w] : 0ull;
-        a.op[1][w] = w < ld ? x_operator[w] : 0ull;
+    DecodeHashSetup setup(ctx);
+    GF2_TRY(setup.make("gf2_mc_decode_hashed", n, ld, h1, r1, keys1, corr1, entries1, h2, r2, keys2, corr2, entries2, x_operator,
+                       z_operator, 5, &a));
+    a.counts = setup.counts_dev;
+    GF2_TRY(gf2_prof_begin(ctx, GF2_K_SAMPLER));
+    hipLaunchKernelGGL(decode_hash_kernel, dim3(decode_blocks(count)), dim3(256), 0, ctx->stream, a);
+    GF2_TRY(gf2_prof_end(ctx));
+    GF2_HIP(hipGetLastError());
+    return gf2_d2h(ctx, counts_out, setup.counts_dev, 40);
+}
+
+// The strata of gf2_mc_decode_hashed (DESIGN.md "Strata"): tables and column keys made once, one launch per stratum on the
+// context's stream, one copy back of the nstrata x 5 counts.
+extern "C" int gf2_mc_decode_strata(gf2_ctx* ctx, int64_t n, int64_t ld, const uint64_t* h1, int64_t r1, const uint64_t* keys1,
+                                    const uint64_t* corr1, int64_t entries1, const uint64_t* h2, int64_t r2, const uint64_t* keys2,
+                                    const uint64_t* corr2, int64_t entries2, const uint64_t* x_operator, const uint64_t* z_operator,
+                                    uint64_t seed, int64_t first_sample, int64_t nstrata, const int32_t* weights, const int64_t* counts,
+                                    double k_x, double k_y, double k_z, uint64_t* counts_out) {
+    GF2_TRY(decode_hash_check_args("gf2_mc_decode_strata", ctx, n, ld, h1, r1, keys1, corr1, entries1, h2, r2, keys2, corr2, entries2,
+                                   x_operator, z_operator, counts_out));
+    if (nstrata < 0 || nstrata > GF2_STRATA_MAX || (nstrata && (!weights || !counts)))
+        GF2_FAIL(GF2_E_ARG, "gf2_mc_decode_strata: needs 0 <= nstrata <= %d and their weights and counts", GF2_STRATA_MAX);
+    if (first_sample < 0) GF2_FAIL(GF2_E_ARG, "gf2_mc_decode_strata: negative range");
+    int64_t total = 0;
+    for (int64_t s = 0; s < nstrata; ++s) {
+        if (weights[s] < 0 || weights[s] > n)
+            GF2_FAIL(GF2_E_ARG, "gf2_mc_decode_strata: stratum %lld has weight %d outside [0, n = %lld]", (long long)s, (int)weights[s],
+                     (long long)n);
+        if (counts[s] < 0) GF2_FAIL(GF2_E_ARG, "gf2_mc_decode_strata: stratum %lld has a negative sample count", (long long)s);
+        total += counts[s] > 0;
     }
-    // side 0: X errors against parity_check_c2; side 1: Z errors against parity_check_c1
-    const uint64_t* hs[2] = {h2, h1};
-    const int64_t rs[2] = {r2, r1}, es[2] = {entries2, entries1};
-    const uint64_t* ks[2] = {keys2, keys1};
-    const uint64_t* cs[2] = {corr2, corr1};
-    HashAlloc tabs[2] = {HashAlloc(ctx), HashAlloc(ctx)};
-    u64 *dev[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}, *counts_dev = nullptr;
-    int* flags_dev = nullptr;
-    int rc = gf2_dev_alloc(ctx, 16, (void**)&flags_dev);
-    if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, 40, (void**)&counts_dev);
-    if (rc == GF2_OK && (hipMemsetAsync(flags_dev, 0, 16, ctx->stream) != hipSuccess || hipMemsetAsync(counts_dev, 0, 40, ctx->stream) != hipSuccess))
-        rc = GF2_E_HIP;
-    for (int c = 0; c < 2 && rc == GF2_OK; ++c) {
-        const int kw = rs[c] <= 63 ? 1 : 2;
-        a.kw[c] = kw;
-        std::vector<u64> colkey;
-        column_keys(hs[c], rs[c], n, ld, kw, &colkey);
-        rc = gf2_dev_alloc(ctx, colkey.size() * 8, (void**)&dev[c][0]);
-        if (rc == GF2_OK) rc = gf2_h2d(ctx, dev[c][0], colkey.data(), colkey.size() * 8);
-        const size_t ent = (size_t)(es[c] > 0 ? es[c] : 1);
-        if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, ent * 8 * kw, (void**)&dev[c][1]);
-        if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, ent * 16, (void**)&dev[c][2]);
-        if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][1], ks[c], (size_t)es[c] * 8 * kw);
-        if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][2], cs[c], (size_t)es[c] * 16);
-        if (rc == GF2_OK) rc = tabs[c].make(pow2_at_least((u64)es[c] * 2 + 2), kw);
-        if (rc == GF2_OK && es[c]) {
-            hipLaunchKernelGGL(table_insert_kernel, dim3((unsigned)gf2_cdiv(es[c], 256)), dim3(256), 0, ctx->stream, tabs[c].tab,
-                               (const u64*)dev[c][1], kw, es[c], flags_dev);
-            if (hipGetLastError() != hipSuccess) rc = GF2_E_HIP;
-        }
-        a.tab[c] = tabs[c].tab;
-        a.corr[c] = dev[c][2];
-        a.colkey[c] = dev[c][0];
+    DecodeHashArgs a;
+    a.th = SegTables();
+    GF2_TRY(stratum_thresholds("gf2_mc_decode_strata", k_x, k_y, k_z, &a.th.t_1, &a.th.t_2));
+    GF2_TRY(gf2_ctx_activate(ctx));
+    for (int64_t k = 0; k < 5 * nstrata; ++k) counts_out[k] = 0;
+    if (total == 0) return GF2_OK;
+    a.seed = seed;
+    a.first_sample = first_sample;
+    DecodeHashSetup setup(ctx);
+    GF2_TRY(setup.make("gf2_mc_decode_strata", n, ld, h1, r1, keys1, corr1, entries1, h2, r2, keys2, corr2, entries2, x_operator,
+                       z_operator, 5 * nstrata, &a));
+    for (int64_t s = 0; s < nstrata; ++s) {
+        if (counts[s] == 0) continue;
+        a.count = counts[s];
+        a.counts = setup.counts_dev + 5 * s;
+        GF2_TRY(gf2_prof_begin(ctx, GF2_K_SAMPLER));
+        hipLaunchKernelGGL(decode_strata_kernel, dim3(decode_blocks(counts[s])), dim3(256), 0, ctx->stream, a, (int)weights[s]);
+        GF2_TRY(gf2_prof_end(ctx));
+        GF2_HIP(hipGetLastError());
     }
-    int flags_host[2] = {0, 0};
-    if (rc == GF2_OK && (hipMemcpyAsync(flags_host, flags_dev, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                         hipStreamSynchronize(ctx->stream) != hipSuccess))
-        rc = GF2_E_HIP;
-    if (rc == GF2_OK && (flags_host[0] || flags_host[1])) {
-        gf2_set_error(flags_host[0] ? "gf2_mc_decode_hashed: a syndrome key occurs twice in a table" : "gf2_mc_decode_hashed: the hash table gave up");
-        rc = flags_host[0] ? GF2_E_ARG : GF2_E_HIP;
-    }
-    if (rc == GF2_OK) {
-        a.counts = counts_dev;
-        int64_t blocks = gf2_cdiv(count, 256 * 16);
-        if (blocks > 4096) blocks = 4096;
-        if (blocks < 1) blocks = 1;
-        rc = gf2_prof_begin(ctx, GF2_K_SAMPLER);
-        if (rc == GF2_OK) {
-            hipLaunchKernelGGL(decode_hash_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, a);
-            rc = gf2_prof_end(ctx);
-        }
-        if (rc == GF2_OK && hipGetLastError() != hipSuccess) rc = GF2_E_HIP;
-        if (rc == GF2_OK) rc = gf2_d2h(ctx, counts_out, counts_dev, 40);
-    }
-    for (int c = 0; c < 2; ++c)
-        for (int k = 0; k < 3; ++k) (void)gf2_dev_free(ctx, dev[c][k]);
-    (void)gf2_dev_free(ctx, flags_dev);
-    (void)gf2_dev_free(ctx, counts_dev);
-    return rc;
+    return gf2_d2h(ctx, counts_out, setup.counts_dev, (size_t)nstrata * 40);
 }

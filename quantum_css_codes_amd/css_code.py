@@ -298,6 +298,15 @@ class CSSCode(QECC):
         from . import montecarlo
         return montecarlo.decode_local(self, num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample)
 
+    def logical_error_strata(self, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0):
+        """[build-defined, DESIGN.md "Strata"]  `logical_error_rates` stratified by error weight: stratum s draws `samples`
+        (one number, or one per stratum) errors of exactly weights[s] qubits -- a uniformly random subset, kinds X : Y : Z =
+        kinds -- and tallies the same five counts.  Returns a montecarlo.Strata; its rate(p_t) combines the strata with binomial
+        weights in double precision, for every p_t at once and with no floor at 2^-32 (logical_error_rates returns 0 flips for
+        the Steane code at p_t = 1e-6; rate(1e-6) gives 1.63e-11)."""
+        from . import montecarlo
+        return montecarlo.strata_local(self, weights, samples, kinds=kinds, seed=seed, first_sample=first_sample)
+
     # -- build-defined: faults inside a circuit (circuit_noise.py) ----------------------------------------------
     def circuit_monte_carlo(self, gates, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, mode=None):
         """[build-defined]  `monte_carlo` for the final Pauli frame of a noisy circuit: every operand of every gate of `gates`
@@ -328,6 +337,19 @@ class CSSCode(QECC):
         from . import circuit_noise
         return self.circuit_logical_error_rates(circuit_noise.encoder_gates(self, state), num_samples, p_x, p_y, p_z, seed=seed,
                                                 first_sample=first_sample)
+
+    def circuit_logical_error_strata(self, gates, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0):
+        """[build-defined]  `logical_error_strata` over the fault locations of a noisy circuit (see circuit_monte_carlo): exactly
+        weights[s] <= 16 faults per sample; rate(p_t) of the result is per fault location."""
+        from . import circuit_noise
+        return circuit_noise.circuit_for(self, gates).logical_error_strata(weights, samples, kinds=kinds, seed=seed,
+                                                                           first_sample=first_sample)
+
+    def encoder_logical_error_strata(self, state, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0):
+        """[build-defined]  circuit_logical_error_strata of this code's own encoder ('zero' or 'plus')."""
+        from . import circuit_noise
+        return self.circuit_logical_error_strata(circuit_noise.encoder_gates(self, state), weights, samples, kinds=kinds, seed=seed,
+                                                 first_sample=first_sample)
 
 
 # -- free functions -----------------------------------------------------------------------------------------

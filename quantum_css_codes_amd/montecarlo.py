@@ -7,6 +7,9 @@ data path.  The only collective is the final sum of the histograms: one all-redu
 (r_1 + 1) + (r_2 + 1) uint64 bins (about 32 KiB at n = 4096) -- RCCL over xGMI when torch.distributed
 runs on the "nccl" backend, gloo on CPU.  The result is identical for every number of shards.
 """
+import collections
+import math
+
 import numpy as np
 
 from . import _native
@@ -200,3 +203,133 @@ def decode_sharded(code, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, gro
     out = {name: int(v) for name, v in zip(DECODE_FIELDS, total)}
     out['samples'] = int(num_samples)
     return out
+
+
+# ---- weight-stratified Monte-Carlo (DESIGN.md "Strata") -------------------------------------------------------------------
+
+def binomial_weights(nb, p_t):
+    """B_w = C(nb, w) p_t^w (1 - p_t)^(nb - w) for w = 0 .. nb as float64, in log space (log C(nb, w) as a running sum of
+    log((nb - i) / (i + 1)), log1p for the complement), so that B_w keeps its relative accuracy at p_t = 1e-12 and below."""
+    nb, p_t = int(nb), float(p_t)
+    if nb < 0 or not 0.0 <= p_t <= 1.0:
+        raise ValueError("binomial weights need nb >= 0 and 0 <= p_t <= 1")
+    out = np.zeros(nb + 1)
+    if p_t == 0.0 or p_t == 1.0:
+        out[0 if p_t == 0.0 else nb] = 1.0
+        return out
+    w = np.arange(nb + 1, dtype=np.float64)
+    log_c = np.concatenate(([0.0], np.cumsum(np.log((nb - w[:-1]) / (w[:-1] + 1.0)))))
+    return np.exp(log_c + w * np.log(p_t) + (nb - w) * np.log1p(-p_t))
+
+
+# Strata.rate's result: the logical error rate lies in [estimate, estimate + truncation] up to the statistical error `stderr`.
+StratifiedRate = collections.namedtuple('StratifiedRate', ('estimate', 'stderr', 'truncation'))
+
+
+class Strata(object):
+    """Tallies of a stratified run over `nb` positions (the qubits of a code, the fault locations of a circuit): `weights`
+    (nstrata, distinct), `samples` (N_w per stratum) and `counts` (nstrata x 5 in DECODE_FIELDS order).  One set of strata serves
+    every physical rate: rate(p_t) combines them with binomial weights computed in double precision on the host, so nothing
+    is lost below 2^-32."""
+
+    def __init__(self, nb, weights, samples, counts, kinds=(1, 1, 1)):
+        self.nb = int(nb)
+        self.weights = np.asarray(weights, dtype=np.int64).reshape(-1).copy()
+        self.samples = np.asarray(samples, dtype=np.int64).reshape(-1).copy()
+        self.counts = np.asarray(counts, dtype=np.uint64).reshape(len(self.weights), len(DECODE_FIELDS)).copy()
+        self.kinds = tuple(float(k) for k in kinds)
+        if self.samples.shape != self.weights.shape:
+            raise ValueError("one sample count per stratum")
+        if len(set(self.weights.tolist())) != len(self.weights):
+            raise ValueError("the weights of the strata must be distinct")
+        if len(self.weights) and (self.weights.min() < 0 or self.weights.max() > self.nb):
+            raise ValueError("a stratum's weight lies in [0, nb]")
+
+    def fractions(self, field='logical_any'):
+        """f_w estimates: counts / samples per stratum (0 where a stratum has no samples)."""
+        col = self.counts[:, DECODE_FIELDS.index(field)].astype(np.float64)
+        return np.divide(col, self.samples, out=np.zeros(len(col)), where=self.samples > 0)
+
+    def rate(self, p_t, field='logical_any'):
+        """The rate of `field` at total physical error probability p_t per position (kinds in the ratio the strata were drawn
+        with): estimate sum_w B_w f_w, its standard error sqrt(sum_w B_w^2 f_w (1 - f_w) / N_w), and `truncation`, the binomial
+        mass of the weights without samples -- a rigorous additive upper bound, since every f_w <= 1."""
+        b_all = binomial_weights(self.nb, p_t)
+        live = self.samples > 0
+        b = b_all[self.weights[live]]
+        f = self.fractions(field)[live]
+        sampled = np.zeros(self.nb + 1, dtype=bool)
+        sampled[self.weights[live]] = True
+        return StratifiedRate(math.fsum(b * f), math.sqrt(math.fsum(b * b * f * (1.0 - f) / self.samples[live])),
+                              math.fsum(b_all[~sampled]))
+
+    def curve(self, p_values, field='logical_any'):
+        """rate() at every p of p_values: (estimates, stderrs, truncations) as arrays."""
+        rows = np.array([self.rate(p, field) for p in p_values], dtype=np.float64).reshape(-1, 3)
+        return rows[:, 0], rows[:, 1], rows[:, 2]
+
+    def as_dicts(self):
+        return [dict(zip(DECODE_FIELDS, (int(v) for v in row)), weight=int(w), samples=int(n))
+                for w, n, row in zip(self.weights, self.samples, self.counts)]
+
+
+def _strata_request(weights, samples, kinds, first_sample):
+    weights = [int(w) for w in np.asarray(weights).reshape(-1)]
+    samples = np.broadcast_to(np.asarray(samples, dtype=np.int64), (len(weights),)).copy()
+    firsts = np.broadcast_to(np.asarray(first_sample, dtype=np.int64), (len(weights),)).copy()
+    kinds = tuple(float(k) for k in kinds)
+    if len(kinds) != 3 or min(kinds) < 0 or not sum(kinds) > 0:
+        raise ValueError("kinds are three non-negative weights (X, Y, Z) with a positive sum")
+    if samples.size and samples.min() < 0:
+        raise ValueError("negative sample count")
+    return weights, samples, firsts, kinds
+
+
+def _strata_calls(firsts):
+    """Strata grouped by their first sample: one native call (one set of hash tables) per distinct value."""
+    groups = {}
+    for s, first in enumerate(firsts.tolist()):
+        groups.setdefault(first, []).append(s)
+    return groups.items()
+
+
+def strata_local(code, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0):
+    """Stratified table decode on this GPU (gf2_mc_decode_strata): stratum s draws samples [first_sample, first_sample + samples[s])
+    of exactly weights[s] errors on the code's n qubits, kinds X : Y : Z = kinds.  `samples` and `first_sample` are one number for
+    all strata or one per stratum.  Returns a Strata."""
+    if code.n > 128 or max(code.r_1, code.r_2) > 127 or min(code.r_1, code.r_2) < 1:
+        raise ValueError("table decode needs n <= 128 and 1 <= r_1, r_2 <= 127")
+    weights, samples, firsts, kinds = _strata_request(weights, samples, kinds, first_sample)
+    if any(w < 0 or w > code.n for w in weights):
+        raise ValueError("a stratum's weight lies in [0, n = %d]" % code.n)
+    two = lambda vec: np.pad(_native.pack_rows(np.asarray(vec).reshape(1, -1))[0], (0, 2))[:2]
+    cached = getattr(code, "_hashed_table_arrays", None)             # (shared with decode_local)
+    if cached is None or cached[0] is not code._c1_syndromes or cached[1] is not code._c2_syndromes:
+        cached = (code._c1_syndromes, code._c2_syndromes, table_entries(code._c1_syndromes, code.r_1, code.n),
+                  table_entries(code._c2_syndromes, code.r_2, code.n))
+        code._hashed_table_arrays = cached
+    (keys1, corr1), (keys2, corr2) = cached[2], cached[3]
+    ctx = _native.default_context()
+    counts = np.zeros((len(weights), len(DECODE_FIELDS)), dtype=np.uint64)
+    for first, rows in _strata_calls(firsts):
+        counts[rows] = ctx.mc_decode_strata(code.n, _native.pack_rows(code.parity_check_c1), code.r_1, keys1, corr1,
+                                            _native.pack_rows(code.parity_check_c2), code.r_2, keys2, corr2,
+                                            two(code.x_operator_matrix()[0]), two(code.z_operator_matrix()[0]), int(seed), int(first),
+                                            [weights[s] for s in rows], samples[rows], *kinds)
+    return Strata(code.n, weights, samples, counts, kinds)
+
+
+def strata_sharded(code, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0, group=None, local_fn=None):
+    """Every stratum's sample range cut into this rank's shard (shard_range), then one all-reduce of the nstrata x 5 counts.
+    `local_fn` (strata_local's signature; FaultCircuit.strata_local for a circuit) replaces the computation."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+    else:
+        rank, world = 0, 1
+    weights, samples, firsts, kinds = _strata_request(weights, samples, kinds, first_sample)
+    shards = [shard_range(first, count, rank, world) for first, count in zip(firsts.tolist(), samples.tolist())]
+    part = (local_fn or strata_local)(code, weights, [mine for _, mine in shards], kinds=kinds, seed=seed,
+                                      first_sample=[start for start, _ in shards])
+    total, = all_reduce_histograms([part.counts.reshape(-1)], group=group)
+    return Strata(part.nb, weights, samples, total, kinds)
