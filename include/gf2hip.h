@@ -393,6 +393,35 @@ int gf2_mc_circuit_decode_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64
                                  uint64_t seed, int64_t first_sample, int64_t nstrata, const int32_t* weights, const int64_t* counts,
                                  double k_x, double k_y, double k_z, uint64_t* counts_out);
 
+/* ---- exact strata: the low-weight fault configurations counted, not sampled --------------------------
+ * [build-defined, DESIGN.md "Exact strata"]  A configuration of weight w of a circuit with L locations and effect table eff is a
+ * pair (S, kappa): S = {s_0 < ... < s_{w-1}} a subset of [0, L), kappa in {1, 2, 3}^w with the sampler's kind bits (1 = X, 2 = Z,
+ * 3 = Y).  Its outcome words are the XOR over k of eff[s_k][0] if kappa_k & 1 and of eff[s_k][1] if kappa_k & 2; it is decoded and
+ * tallied exactly by gf2_mc_circuit_decode's rule (same outcome layout, same tables and flip bytes, the same five fields).
+ * rank(S) = sum_k C(s_k, k + 1) (the combinatorial number system: a bijection onto [0, C(L, w)), colexicographic order; w = 0
+ * has the single rank 0).  A call covers the subsets of ranks [first_rank, first_rank + count), each with all 3^w kind
+ * assignments.  counts_out[(w + 1)][(w + 1)][5]: entry [n_x][n_y][field] is the tally of `field` over the configurations of the
+ * range with n_x X faults, n_y Y faults and w - n_x - n_y Z faults (entries with n_x + n_y > w are zero).  For kind weights
+ * (k_x, k_y, k_z) of sum s the host then has f_w = sum counts[n_x][n_y] k_x^n_x k_y^n_y k_z^n_z / (s^w C(L, w)), exactly.
+ * 0 <= w <= min(L, GF2_ENUMERATE_MAX_WEIGHT).  GF2_E_ARG if C(L, w) >= 2^63, if count * 3^w >= 2^63, or if the range leaves
+ * [0, C(L, w)). */
+#define GF2_ENUMERATE_MAX_WEIGHT 8
+
+/* The inverse of rank (host code): the w positions, ascending, of the subset of [0, nb) with that rank.  1 <= nb <= 2^20,
+ * 0 <= w <= min(nb, GF2_ENUMERATE_MAX_WEIGHT), 0 <= rank < min(C(nb, w), 2^63). */
+int gf2_subset_unrank(int64_t nb, int64_t w, int64_t rank, int32_t* positions_out);
+
+/* The definition on the host: serial, no GPU needed.  eff: 2 * locations * ldr words as gf2_circuit_effects writes them. */
+int gf2_circuit_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t r1, const uint64_t* keys1,
+                               const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                               int64_t entries2, int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out);
+
+/* The same counts on the device: the hash tables are made once, the range is cut into launches of bounded size, the counts come
+ * back once. */
+int gf2_circuit_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                          int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, int64_t w,
+                          int64_t first_rank, int64_t count, uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

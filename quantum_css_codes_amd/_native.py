@@ -22,6 +22,7 @@ HIST_FULL, HIST_WEIGHT = 0, 1
 GATE_H, GATE_CNOT, GATE_IDLE = 0, 1, 2
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
+ENUMERATE_MAX_WEIGHT = 8
 K_SYNDROME, K_HIST, K_SAMPLER, K_ELIM = 0, 1, 2, 3
 # routing flags of a context and its tunables: the few a caller needs are in include/gf2hip.h (F_MC_DENSE, F_RREF_SEQUENTIAL,
 # F_NORMALIZE_SEQUENTIAL, OPT_SLAB_PASS_LOG2, OPT_MC_CHUNK_LOG2), the rest -- routes for the parity tests and the A/B scripts -- in
@@ -121,6 +122,9 @@ SIGNATURES = {
                               ctypes.c_double, ctypes.c_double, _p],
     "gf2_mc_circuit_decode_strata": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, _p, _p,
                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
+    "gf2_subset_unrank": [_c_i64, _c_i64, _c_i64, _p],
+    "gf2_circuit_enumerate_host": [_p, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
+    "gf2_circuit_enumerate": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
     "gf2_comm_unique_id": [_p, ctypes.c_size_t],
     "gf2_comm_create": [_p, _p, ctypes.c_int, ctypes.c_int, _pp],
     "gf2_comm_create_all": [_pp, ctypes.c_int, _pp],
@@ -326,6 +330,37 @@ def _strata_arrays(weights, counts):
     if weights.shape != counts.shape:
         raise ValueError("one sample count per stratum")
     return weights, counts, np.zeros((len(weights), 5), dtype=np.uint64)
+
+
+def subset_unrank(nb, w, rank):
+    """gf2_subset_unrank (host code): the w positions, ascending, of the subset of [0, nb) whose rank in the combinatorial number
+    system, sum_k C(s_k, k + 1), is `rank` (DESIGN.md "Exact strata")."""
+    if not -(1 << 63) <= int(rank) < (1 << 63):
+        raise GF2Error(GF2_E_ARG, "gf2_subset_unrank: the rank does not fit 63 bits")
+    out = np.zeros(max(1, int(w)), dtype=np.int32)
+    check(lib().gf2_subset_unrank(int(nb), int(w), int(rank), _ptr(out)))
+    return out[:max(0, int(w))]
+
+
+def _enumerate_tables(keys1, flips1, keys2, flips2):
+    k1, k2 = np.ascontiguousarray(keys1, dtype="<u8"), np.ascontiguousarray(keys2, dtype="<u8")
+    f1, f2 = np.ascontiguousarray(flips1, dtype=np.uint8), np.ascontiguousarray(flips2, dtype=np.uint8)
+    return (k1, f1, k2, f2), ((_ptr(k1) if len(k1) else None, _ptr(f1) if len(k1) else None, len(k1)),
+                              (_ptr(k2) if len(k2) else None, _ptr(f2) if len(k2) else None, len(k2)))
+
+
+def circuit_enumerate_host(eff, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
+    """gf2_circuit_enumerate_host (host code, no GPU): the (w + 1, w + 1, 5) uint64 counts [n_x][n_y][field] over the subsets of
+    ranks [first_rank, first_rank + count), each with all 3^w kind assignments.  eff: (L, 2, ldr) as circuit_effects returns it."""
+    eff = np.ascontiguousarray(eff, dtype="<u8")
+    if eff.ndim != 3 or eff.shape[1] != 2:
+        raise ValueError("eff must be (locations, 2, ldr)")
+    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+    side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
+    out = np.zeros((side, side, 5), dtype=np.uint64)
+    check(lib().gf2_circuit_enumerate_host(_ptr(eff), eff.shape[0], eff.shape[2], r1, *t1, r2, *t2, int(w), int(first_rank), int(count),
+                                           _ptr(out)))
+    return out
 
 
 # ---- context ----------------------------------------------------------------------------------------------
@@ -733,6 +768,14 @@ class Context(object):
                                                  len(k1), r2, _ptr(k2) if len(k2) else None, _ptr(f2) if len(k2) else None, len(k2),
                                                  seed & 0xFFFFFFFFFFFFFFFF, first, len(weights), _ptr(weights), _ptr(counts),
                                                  k_x, k_y, k_z, _ptr(out)))
+        return out
+
+    def circuit_enumerate(self, circ, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
+        """gf2_circuit_enumerate: circuit_enumerate_host's counts from the device."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
+        out = np.zeros((side, side, 5), dtype=np.uint64)
+        check(lib().gf2_circuit_enumerate(self.handle, circ.handle, r1, *t1, r2, *t2, int(w), int(first_rank), int(count), _ptr(out)))
         return out
 
     # -- syndromes ----------------------------------------------------------------------------------------

@@ -16,6 +16,8 @@ precomputed effect per fault (gf2_circuit_effects, host code); the device kernel
 After encode_zero only `logical_x` (a flipped logical Z measurement) is physical -- Z-type operators act trivially on |0_L> --
 and after encode_plus only `logical_z`; both are reported as statistics of the frame.
 """
+import math
+
 import numpy as np
 
 from . import _native
@@ -24,6 +26,8 @@ from . import montecarlo
 GATE_H, GATE_CNOT, GATE_IDLE = _native.GATE_H, _native.GATE_CNOT, _native.GATE_IDLE
 MAX_LOCATIONS = _native.CIRCUIT_MAX_LOCATIONS
 MAX_ROWS = 64 * _native.CIRCUIT_MAX_LDR
+# FaultCircuit.enumerate_strata's default budget of configurations: about ten seconds of one MI355X (DESIGN.md "Exact strata")
+ENUMERATE_BUDGET = 1 << 32
 
 
 def _gates(gates):
@@ -185,6 +189,43 @@ class FaultCircuit(object):
                                                         [weights[s] for s in rows], samples[rows], *kinds)
         return montecarlo.Strata(self.num_locations, weights, samples, counts, kinds)
 
+    def enumerate_strata(self, weights, first_rank=None, count=None, max_configurations=None, host=False):
+        """Exact strata (DESIGN.md "Exact strata"): every configuration of exactly weights[s] <= 8 faults -- each subset of the L
+        locations with every assignment of X, Y, Z to its picks -- decoded and tallied by logical_error_rates' rule, counted per
+        kind composition.  Nothing is sampled.  `first_rank` and `count` (one number or one per weight; default: everything)
+        select the subsets of ranks [first_rank, first_rank + count) in the combinatorial number system; the counts of parts add
+        up.  More than `max_configurations` (default ENUMERATE_BUDGET) configurations in all is a ValueError.  host=True runs
+        the serial host statement and needs no GPU.  Returns a montecarlo.ExactStrata over nb = L, which is meaningful as whole
+        strata (fractions, rate) only when the ranges are whole."""
+        code = self._need_code()
+        if code.n > 128:
+            raise ValueError("the table decode of a circuit's final frame needs n <= 128 (where the syndrome tables exist)")
+        weights = [int(w) for w in np.asarray(weights).reshape(-1)]
+        total = self.num_locations
+        limit = min(total, _native.ENUMERATE_MAX_WEIGHT)
+        if any(w < 0 or w > limit for w in weights):
+            raise ValueError("an enumerated stratum's weight lies in [0, min(L = %d, %d)]" % (total, _native.ENUMERATE_MAX_WEIGHT))
+        if not 1 <= total <= MAX_LOCATIONS:
+            raise ValueError("the enumeration needs 1 <= L <= %d (2^20) fault locations, the circuit has %d" % (MAX_LOCATIONS, total))
+        subsets = [math.comb(total, w) for w in weights]
+        firsts = [0] * len(weights) if first_rank is None else [int(v) for v in np.broadcast_to(np.asarray(first_rank, dtype=object), (len(weights),))]
+        counts = ([c - f for c, f in zip(subsets, firsts)] if count is None
+                  else [int(v) for v in np.broadcast_to(np.asarray(count, dtype=object), (len(weights),))])
+        for w, c, f, n in zip(weights, subsets, firsts, counts):
+            if f < 0 or n < 0 or f + n > c:
+                raise ValueError("ranks [%d, %d + %d) leave the range [0, C(%d, %d) = %d)" % (f, f, n, total, w, c))
+        size = sum(n * 3**w for w, n in zip(weights, counts))
+        budget = ENUMERATE_BUDGET if max_configurations is None else int(max_configurations)
+        if size > budget:
+            raise ValueError("%d fault configurations to enumerate, more than max_configurations = %d" % (size, budget))
+        keys1, flips1, keys2, flips2 = self._tables()
+        if host:
+            run = lambda w, f, n: _native.circuit_enumerate_host(self.effects, code.r_1, keys1, flips1, code.r_2, keys2, flips2, w, f, n)
+        else:
+            ctx, circ = _native.default_context(), self.device()
+            run = lambda w, f, n: ctx.circuit_enumerate(circ, code.r_1, keys1, flips1, code.r_2, keys2, flips2, w, f, n)
+        return montecarlo.ExactStrata(total, weights, [run(w, f, n) for w, f, n in zip(weights, firsts, counts)])
+
     # The two with montecarlo.run_sharded's / decode_sharded's local_fn signature (the code argument must be this circuit's).
     def run_local(self, code, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, mode=None):
         if code is not self.code:
@@ -211,6 +252,11 @@ def circuit_for(code, gates):
     if key not in cache:
         cache[key] = FaultCircuit.for_code(code, gates)
     return cache[key]
+
+
+def idle_gates(n):
+    """One IDLE gate per qubit: the circuit whose fault model is the code-capacity model (one independent error per qubit)."""
+    return np.array([(GATE_IDLE, q, 0) for q in range(int(n))], dtype=np.int32).reshape(-1, 3)
 
 
 def encoder_gates(code, state):

@@ -21,20 +21,12 @@
 #include <new>
 
 #include "gf2_internal.h"
-#include "gf2_hash_dev.h"
+#include "gf2_circuit_dev.h"
 #include "gf2_sampler.h"
 
-#define CIRC_THREADS 256
 #define CIRC_TAKEN_STRIDE 17                   // dwords per lane: 16 hold the 512 bits
-#define CIRC_EFF_LDS_BYTES 20480               // effect tables up to this size are staged in LDS
 #define CIRC_BINS_LDS 4096                     // both histograms together, privatised in LDS up to this many bins
 #define CIRC_STRATUM_MAX GF2_CIRCUIT_STRATUM_MAX_WEIGHT
-
-struct gf2_circuit {
-    int64_t locations, ldr;
-    u64* eff_dev;                              // 2 * locations * ldr words
-    u64 any[GF2_CIRCUIT_MAX_LDR];              // OR of all effects, word by word: which outcome bits can be set at all
-};
 
 enum { CIRC_STORE = 0, CIRC_HIST = 1, CIRC_TALLY = 2 };
 
@@ -243,85 +235,6 @@ static int circuit_launch(gf2_ctx* ctx, const gf2_circuit* circ, CircuitArgs& a,
     GF2_HIP(hipGetLastError());
     return GF2_OK;
 }
-
-// The Monte-Carlo layout of a circuit's words for checks of r_1 and r_2 rows, tested against what the table can set.
-static int circuit_layout(const char* who, const gf2_circuit* circ, int64_t r1, int64_t r2, CircuitArgs* a) {
-    if (r1 < 1 || r2 < 1 || r1 > 127 || r2 > 127) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 127", who);
-    a->kwx = r2 <= 63 ? 1 : 2;
-    a->kwz = r1 <= 63 ? 1 : 2;
-    if (circ->ldr != a->kwx + a->kwz + 1)
-        GF2_FAIL(GF2_E_ARG, "%s: r_1 = %lld and r_2 = %lld need effects of %d words (key_x, key_z, parity), the circuit has %lld", who,
-                 (long long)r1, (long long)r2, a->kwx + a->kwz + 1, (long long)circ->ldr);
-    auto beyond = [](const u64* words, int kw, int64_t r) {            // a bit at or above r in a key of kw words
-        const int64_t top = r - 64 * (kw - 1);                           // bits of the highest word (1 .. 63)
-        return (words[kw - 1] >> top) != 0;
-    };
-    if (beyond(circ->any, a->kwx, r2) || beyond(circ->any + a->kwx, a->kwz, r1) || (circ->any[circ->ldr - 1] >> 2) != 0)
-        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits or the two parity bits", who);
-    return GF2_OK;
-}
-
-static int circuit_check_tables(const char* who, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, const uint64_t* keys2,
-                                const uint8_t* flips2, int64_t entries2) {
-    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !flips1)) || (entries2 && (!keys2 || !flips2)))
-        GF2_FAIL(GF2_E_ARG, "%s: bad table (a null array with entries > 0, or a negative count)", who);
-    if (entries1 > (int64_t)TBL_HASH_MAX_ENTRIES || entries2 > (int64_t)TBL_HASH_MAX_ENTRIES) GF2_FAIL(GF2_E_ARG, "%s: table too large", who);
-    return GF2_OK;
-}
-
-// The device side of the tally's tables (a.kwx and a.kwz set): keys in hash tables, one flip byte per entry, zeroed counts.
-// Side 0: key_x against parity_check_c2's table; side 1: key_z against parity_check_c1's.  Freed with the object.
-struct CircuitTables {
-    gf2_ctx* ctx;
-    HashAlloc tabs[2];
-    void* dev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    u64* counts_dev = nullptr;
-    int* flags_dev = nullptr;
-    explicit CircuitTables(gf2_ctx* c) : ctx(c), tabs{HashAlloc(c), HashAlloc(c)} {}
-    ~CircuitTables() {
-        for (int c = 0; c < 2; ++c)
-            for (int k = 0; k < 2; ++k) (void)gf2_dev_free(ctx, dev[c][k]);
-        (void)gf2_dev_free(ctx, flags_dev);
-        (void)gf2_dev_free(ctx, counts_dev);
-    }
-    int make(const char* who, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, const uint64_t* keys2, const uint8_t* flips2,
-             int64_t entries2, int64_t ncounts, CircuitArgs* a) {
-        const int64_t es[2] = {entries2, entries1};
-        const uint64_t* ks[2] = {keys2, keys1};
-        const uint8_t* fs[2] = {flips2, flips1};
-        const int kws[2] = {a->kwx, a->kwz};
-        int rc = gf2_dev_alloc(ctx, 16, (void**)&flags_dev);
-        if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, (size_t)ncounts * 8, (void**)&counts_dev);
-        if (rc == GF2_OK && (hipMemsetAsync(flags_dev, 0, 16, ctx->stream) != hipSuccess ||
-                             hipMemsetAsync(counts_dev, 0, (size_t)ncounts * 8, ctx->stream) != hipSuccess))
-            rc = GF2_E_HIP;
-        for (int c = 0; c < 2 && rc == GF2_OK; ++c) {
-            const int kw = kws[c];
-            const size_t ent = (size_t)(es[c] > 0 ? es[c] : 1);
-            rc = gf2_dev_alloc(ctx, ent * 8 * kw, &dev[c][0]);
-            if (rc == GF2_OK) rc = gf2_dev_alloc(ctx, ent, &dev[c][1]);
-            if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][0], ks[c], (size_t)es[c] * 8 * kw);
-            if (rc == GF2_OK && es[c]) rc = gf2_h2d(ctx, dev[c][1], fs[c], (size_t)es[c]);
-            if (rc == GF2_OK) rc = tabs[c].make(pow2_at_least((u64)es[c] * 2 + 2), kw);
-            if (rc == GF2_OK && es[c]) {
-                hipLaunchKernelGGL(table_insert_kernel, dim3((unsigned)gf2_cdiv(es[c], 256)), dim3(256), 0, ctx->stream, tabs[c].tab,
-                                   (const u64*)dev[c][0], kw, es[c], flags_dev);
-                if (hipGetLastError() != hipSuccess) rc = GF2_E_HIP;
-            }
-            a->tab[c] = tabs[c].tab;
-            a->flips[c] = (const unsigned char*)dev[c][1];
-        }
-        int flags_host[2] = {0, 0};
-        if (rc == GF2_OK && (hipMemcpyAsync(flags_host, flags_dev, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                             hipStreamSynchronize(ctx->stream) != hipSuccess))
-            rc = GF2_E_HIP;
-        if (rc == GF2_OK && (flags_host[0] || flags_host[1])) {
-            gf2_set_error(flags_host[0] ? "%s: a syndrome key occurs twice in a table" : "%s: the hash table gave up", who);
-            rc = flags_host[0] ? GF2_E_ARG : GF2_E_HIP;
-        }
-        return rc;
-    }
-};
 
 extern "C" {
 

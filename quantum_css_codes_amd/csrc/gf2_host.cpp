@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <atomic>
 #include <new>
 #include <system_error>
@@ -283,3 +284,155 @@ int gf2_stratum_errors(int64_t nb, int64_t w, uint64_t seed, int64_t first_sampl
 
 }  // extern "C"
 
+// ---- exact strata (DESIGN.md "Exact strata") ---------------------------------------------------------------------------------
+// C(s, k) for k <= 8, saturated at 2^63: c_i = C(s - k + i, i) grows with i, so a partial product at or above 2^63 settles it.
+static uint64_t binom_sat(int64_t s, int k) {
+    if (s < k) return 0;
+    unsigned __int128 c = 1;
+    for (int i = 0; i < k; ++i) {
+        c = c * (unsigned __int128)(s - k + 1 + i) / (unsigned)(i + 1);
+        if (c >> 63) return 1ull << 63;
+    }
+    return (uint64_t)c;
+}
+
+// The subset of rank `rank` in the combinatorial number system: from the top pick down, the largest s below the pick above with
+// C(s, k) <= what is left of the rank.
+static void subset_unrank(int64_t nb, int w, uint64_t rank, int32_t* pos) {
+    int64_t hi = nb;
+    for (int k = w; k >= 1; --k) {
+        int64_t lo = k - 1;                                                 // C(k - 1, k) = 0 <= rank
+        while (hi - lo > 1) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (binom_sat(mid, k) <= rank) lo = mid; else hi = mid;
+        }
+        pos[k - 1] = (int32_t)lo;
+        rank -= binom_sat(lo, k);
+        hi = lo;
+    }
+}
+
+int gf2_enum_check_range(const char* who, int64_t nb, int64_t w, int64_t first_rank, int64_t count) {
+    if (nb < 1 || nb > GF2_CIRCUIT_MAX_LOCATIONS) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= L <= %d (2^20) locations, got %lld", who, GF2_CIRCUIT_MAX_LOCATIONS, (long long)nb);
+    if (w < 0 || w > GF2_ENUMERATE_MAX_WEIGHT || w > nb)
+        GF2_FAIL(GF2_E_ARG, "%s: weight %lld outside [0, min(L = %lld, %d)]", who, (long long)w, (long long)nb, GF2_ENUMERATE_MAX_WEIGHT);
+    const uint64_t total = binom_sat(nb, (int)w);
+    if (total >> 63) GF2_FAIL(GF2_E_ARG, "%s: C(%lld, %lld) subsets do not fit 63 bits", who, (long long)nb, (long long)w);
+    if (first_rank < 0 || count < 0 || (uint64_t)first_rank > total || (uint64_t)count > total - (uint64_t)first_rank)
+        GF2_FAIL(GF2_E_ARG, "%s: ranks [%lld, %lld + %lld) leave the range [0, C(%lld, %lld) = %llu)", who, (long long)first_rank,
+                 (long long)first_rank, (long long)count, (long long)nb, (long long)w, (unsigned long long)total);
+    int64_t pow3 = 1;
+    for (int64_t k = 0; k < w; ++k) pow3 *= 3;
+    if (count > INT64_MAX / pow3) GF2_FAIL(GF2_E_ARG, "%s: %lld subsets of 3^%lld kind assignments do not fit 63 bits", who, (long long)count, (long long)w);
+    return GF2_OK;
+}
+
+namespace {
+struct HostTable {                                                          // sorted (high word, low word) -> flip byte
+    struct Entry { uint64_t hi, lo; uint8_t flip; };
+    std::vector<Entry> entries;
+    static bool less(const Entry& a, const Entry& b) { return a.hi != b.hi ? a.hi < b.hi : a.lo < b.lo; }
+    bool make(const uint64_t* keys, const uint8_t* flips, int64_t count, int kw) {   // false: a key occurs twice
+        entries.resize((size_t)count);
+        for (int64_t i = 0; i < count; ++i) entries[(size_t)i] = Entry{kw == 2 ? keys[2 * i + 1] : 0ull, keys[kw * i], flips[i]};
+        std::sort(entries.begin(), entries.end(), less);
+        for (size_t i = 1; i < entries.size(); ++i)
+            if (!less(entries[i - 1], entries[i])) return false;
+        return true;
+    }
+    int find(uint64_t hi, uint64_t lo) const {                               // the flip byte's low bit, or -1
+        const Entry key{hi, lo, 0};
+        auto it = std::lower_bound(entries.begin(), entries.end(), key, less);
+        return it != entries.end() && it->hi == hi && it->lo == lo ? (it->flip & 1) : -1;
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int gf2_subset_unrank(int64_t nb, int64_t w, int64_t rank, int32_t* positions_out) {
+    if (nb < 1 || nb > GF2_STRATUM_MAX_POSITIONS)
+        GF2_FAIL(GF2_E_ARG, "gf2_subset_unrank: needs 1 <= nb <= %d (2^20) positions, got %lld", GF2_STRATUM_MAX_POSITIONS, (long long)nb);
+    if (w < 0 || w > GF2_ENUMERATE_MAX_WEIGHT || w > nb)
+        GF2_FAIL(GF2_E_ARG, "gf2_subset_unrank: weight %lld outside [0, min(nb = %lld, %d)]", (long long)w, (long long)nb, GF2_ENUMERATE_MAX_WEIGHT);
+    if (rank < 0 || (uint64_t)rank >= binom_sat(nb, (int)w))
+        GF2_FAIL(GF2_E_ARG, "gf2_subset_unrank: rank %lld outside [0, C(%lld, %lld))", (long long)rank, (long long)nb, (long long)w);
+    if (w > 0 && !positions_out) GF2_FAIL(GF2_E_ARG, "gf2_subset_unrank: null buffer");
+    subset_unrank(nb, (int)w, (uint64_t)rank, positions_out);
+    return GF2_OK;
+}
+
+// The definition of gf2_circuit_enumerate, serial: every subset of the rank range (the first unranked, the others by the colexicographic
+// successor), every kind assignment by an odometer over {1, 2, 3}^w, the outcome XOR-ed from scratch, the tables as sorted arrays.
+int gf2_circuit_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                               int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, int64_t w,
+                               int64_t first_rank, int64_t count, uint64_t* counts_out) {
+    const char* who = "gf2_circuit_enumerate_host";
+    if (!eff || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (ldr < 1 || ldr > GF2_CIRCUIT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= ldr <= %d words per effect", who, GF2_CIRCUIT_MAX_LDR);
+    if (r1 < 1 || r2 < 1 || r1 > 127 || r2 > 127) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 127", who);
+    const int kwx = r2 <= 63 ? 1 : 2, kwz = r1 <= 63 ? 1 : 2;
+    if (ldr != kwx + kwz + 1)
+        GF2_FAIL(GF2_E_ARG, "%s: r_1 = %lld and r_2 = %lld need effects of %d words (key_x, key_z, parity), the table has %lld", who,
+                 (long long)r1, (long long)r2, kwx + kwz + 1, (long long)ldr);
+    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !flips1)) || (entries2 && (!keys2 || !flips2)))
+        GF2_FAIL(GF2_E_ARG, "%s: bad table (a null array with entries > 0, or a negative count)", who);
+    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
+    uint64_t any[GF2_CIRCUIT_MAX_LDR] = {0};
+    for (int64_t i = 0; i < 2 * locations; ++i)
+        for (int64_t q = 0; q < ldr; ++q) any[q] |= eff[i * ldr + q];
+    auto beyond = [](const uint64_t* words, int kw, int64_t r) { return (words[kw - 1] >> (r - 64 * (kw - 1))) != 0; };
+    if (beyond(any, kwx, r2) || beyond(any + kwx, kwz, r1) || (any[ldr - 1] >> 2) != 0)
+        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits or the two parity bits", who);
+    const int64_t side = w + 1;
+    for (int64_t k = 0; k < side * side * 5; ++k) counts_out[k] = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];                                                        // [0]: key_x in parity_check_c2's table, [1]: key_z in c1's
+    try {
+        if (!tab[0].make(keys2, flips2, entries2, kwx) || !tab[1].make(keys1, flips1, entries1, kwz))
+            GF2_FAIL(GF2_E_ARG, "%s: a syndrome key occurs twice in a table", who);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    int32_t pos[GF2_ENUMERATE_MAX_WEIGHT] = {0};
+    int kind[GF2_ENUMERATE_MAX_WEIGHT];
+    subset_unrank(locations, (int)w, (uint64_t)first_rank, pos);
+    for (int64_t i = 0; i < count; ++i) {
+        if (i > 0) {                                                        // successor: the lowest pick that can move up does
+            int64_t j = 0;
+            while (j < w - 1 && pos[j] + 1 == pos[j + 1]) pos[j] = (int32_t)j, ++j;
+            pos[j] += 1;
+        }
+        for (int64_t k = 0; k < w; ++k) kind[k] = 1;
+        for (;;) {
+            uint64_t out[GF2_CIRCUIT_MAX_LDR] = {0};
+            int64_t n_x = 0, n_y = 0;
+            for (int64_t k = 0; k < w; ++k) {
+                const uint64_t* e = eff + (size_t)(2 * pos[k]) * ldr;
+                for (int64_t q = 0; q < ldr; ++q) out[q] ^= (kind[k] & 1 ? e[q] : 0ull) ^ (kind[k] & 2 ? e[ldr + q] : 0ull);
+                n_x += kind[k] == 1;
+                n_y += kind[k] == 3;
+            }
+            const uint64_t key[2][2] = {{out[0], kwx == 2 ? out[1] : 0ull}, {out[kwx], kwz == 2 ? out[kwx + 1] : 0ull}};   // (low, high)
+            bool flip[2], miss[2];
+            for (int c = 0; c < 2; ++c) {
+                const int found = tab[c].find(key[c][1], key[c][0]);
+                miss[c] = found < 0;
+                flip[c] = ((out[ldr - 1] >> c) & 1ull) != (uint64_t)(found > 0);
+            }
+            uint64_t* bin = counts_out + (n_x * side + n_y) * 5;
+            bin[0] += flip[0];
+            bin[1] += flip[1];
+            bin[2] += flip[0] | flip[1];
+            bin[3] += miss[0];
+            bin[4] += miss[1];
+            int64_t k = 0;                                                   // odometer over 1, 2, 3
+            while (k < w && kind[k] == 3) kind[k++] = 1;
+            if (k == w) break;
+            kind[k] += 1;
+        }
+    }
+    return GF2_OK;
+}
+
+}  // extern "C"

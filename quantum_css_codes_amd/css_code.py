@@ -351,6 +351,26 @@ class CSSCode(QECC):
         return self.circuit_logical_error_strata(circuit_noise.encoder_gates(self, state), weights, samples, kinds=kinds, seed=seed,
                                                  first_sample=first_sample)
 
+    # -- build-defined: exact strata (DESIGN.md "Exact strata") ---------------------------------------------------
+    def logical_error_strata_exact(self, weights, **options):
+        """[build-defined]  The strata of `logical_error_strata` counted instead of sampled: every error of exactly weights[s] <= 8
+        qubits with every assignment of X, Y, Z, through the circuit of n IDLE gates (whose strata are this code's).  Returns a
+        montecarlo.ExactStrata: exact f_w for every kind ratio, rate(p_t) without statistical error.  Options as
+        FaultCircuit.enumerate_strata's."""
+        from . import circuit_noise
+        return self.circuit_logical_error_strata_exact(circuit_noise.idle_gates(self.n), weights, **options)
+
+    def circuit_logical_error_strata_exact(self, gates, weights, **options):
+        """[build-defined]  Every configuration of exactly weights[s] <= 8 faults among the locations of a noisy circuit (see
+        circuit_monte_carlo), counted per kind composition: FaultCircuit.enumerate_strata."""
+        from . import circuit_noise
+        return circuit_noise.circuit_for(self, gates).enumerate_strata(weights, **options)
+
+    def encoder_logical_error_strata_exact(self, state, weights, **options):
+        """[build-defined]  circuit_logical_error_strata_exact of this code's own encoder ('zero' or 'plus')."""
+        from . import circuit_noise
+        return self.circuit_logical_error_strata_exact(circuit_noise.encoder_gates(self, state), weights, **options)
+
 
 # -- free functions -----------------------------------------------------------------------------------------
 

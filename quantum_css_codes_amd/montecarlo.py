@@ -8,7 +8,9 @@ data path.  The only collective is the final sum of the histograms: one all-redu
 runs on the "nccl" backend, gloo on CPU.  The result is identical for every number of shards.
 """
 import collections
+import fractions as _fractions
 import math
+import numbers
 
 import numpy as np
 
@@ -333,3 +335,155 @@ def strata_sharded(code, weights, samples, kinds=(1, 1, 1), seed=0, first_sample
                                       first_sample=[start for start, _ in shards])
     total, = all_reduce_histograms([part.counts.reshape(-1)], group=group)
     return Strata(part.nb, weights, samples, total, kinds)
+
+
+# ---- exact strata (DESIGN.md "Exact strata") --------------------------------------------------------------------------------
+
+def _kind_ratio(kinds):
+    kinds = tuple(kinds)
+    if len(kinds) != 3 or min(kinds) < 0 or not sum(kinds) > 0:
+        raise ValueError("kinds are three non-negative weights (X, Y, Z) with a positive sum")
+    return kinds
+
+
+def _same_ratio(a, b):
+    """Kind weights that differ by a positive factor only."""
+    sa, sb = sum(a), sum(b)
+    return all(abs(float(x) * float(sb) - float(y) * float(sa)) <= 1e-12 * float(sa) * float(sb) for x, y in zip(a, b))
+
+
+class ExactStrata(object):
+    """Whole strata counted, not sampled: `weights` (distinct) over `nb` positions and, per weight w, the (w + 1, w + 1, 5) uint64
+    counts [n_x][n_y][field] of FaultCircuit.enumerate_strata over ALL C(nb, w) subsets (the sum of the parts of a sharded or
+    windowed enumeration).  The counts are kept per kind composition, so one enumeration serves every physical rate and every
+    X : Y : Z ratio:  f_w = sum counts[n_x][n_y] k_x^n_x k_y^n_y k_z^n_z / (s^w C(nb, w)),  s = k_x + k_y + k_z."""
+
+    def __init__(self, nb, weights, counts):
+        self.nb = int(nb)
+        self.weights = [int(w) for w in np.asarray(weights).reshape(-1)]
+        if len(set(self.weights)) != len(self.weights):
+            raise ValueError("the weights of the strata must be distinct")
+        if any(w < 0 or w > self.nb for w in self.weights):
+            raise ValueError("a stratum's weight lies in [0, nb]")
+        counts = list(counts)
+        if len(counts) != len(self.weights):
+            raise ValueError("one array of counts per weight")
+        self.counts = [np.asarray(c, dtype=np.uint64).reshape(w + 1, w + 1, len(DECODE_FIELDS)).copy() for w, c in zip(self.weights, counts)]
+
+    def configurations(self):
+        """3^w C(nb, w) per weight."""
+        return [3**w * math.comb(self.nb, w) for w in self.weights]
+
+    def fractions(self, kinds=(1, 1, 1), field='logical_any'):
+        """f_w per enumerated weight for kinds X : Y : Z = kinds: exact fractions.Fraction when the three are integers or Fractions,
+        floats otherwise."""
+        kinds = _kind_ratio(kinds)
+        exact = all(isinstance(k, numbers.Rational) for k in kinds)
+        k_x, k_y, k_z = (_fractions.Fraction(k) for k in kinds) if exact else (float(k) for k in kinds)
+        col, s, out = DECODE_FIELDS.index(field), k_x + k_y + k_z, []
+        for w, counts in zip(self.weights, self.counts):
+            total = 0
+            for n_x in range(w + 1):
+                for n_y in range(w + 1 - n_x):
+                    c = int(counts[n_x, n_y, col])
+                    if c:
+                        total += c * k_x**n_x * k_y**n_y * k_z**(w - n_x - n_y)
+            out.append(total / (s**w * math.comb(self.nb, w)))
+        return out
+
+    def rate(self, p_t, kinds=(1, 1, 1), field='logical_any'):
+        """sum_w B_w f_w over the enumerated weights: no statistical error, and `truncation` is the binomial mass of the others."""
+        b_all = binomial_weights(self.nb, p_t)
+        have = np.zeros(self.nb + 1, dtype=bool)
+        have[self.weights] = True
+        f = [float(v) for v in self.fractions(kinds, field)]
+        return StratifiedRate(math.fsum(b_all[w] * v for w, v in zip(self.weights, f)), 0.0, math.fsum(b_all[~have]))
+
+    def leading_order(self, kinds=(1, 1, 1), field='logical_any'):
+        """(w*, c): the smallest enumerated weight with f_w* > 0 and the coefficient c = C(nb, w*) f_w* of p^w* in the rate; None
+        when every enumerated stratum is clean."""
+        f = dict(zip(self.weights, self.fractions(kinds, field)))
+        for w in sorted(f):
+            if f[w] > 0:
+                return w, math.comb(self.nb, w) * f[w]
+        return None
+
+    def merged(self, strata, kinds=None):
+        """These strata with the sampled ones of `strata` (a Strata or several): see MergedStrata."""
+        return MergedStrata(self, [strata] if isinstance(strata, Strata) else list(strata), kinds)
+
+
+class MergedStrata(object):
+    """Strata's interface over exact and sampled strata together: the exact f_w where there is one (no variance, and the weight
+    counts as covered for `truncation`), the sampled estimate elsewhere.  The sampled strata must cover the same nb positions and
+    all be drawn with one kind ratio (that of `kinds`, when given), which is then the ratio of the exact fractions too."""
+
+    def __init__(self, exact, sampled, kinds=None):
+        self.exact, self.sampled, self.nb = exact, list(sampled), exact.nb
+        if kinds is None:
+            if not self.sampled:
+                raise ValueError("kinds are needed when there are no sampled strata")
+            kinds = self.sampled[0].kinds
+        self.kinds = _kind_ratio(kinds)
+        seen = set()
+        for part in self.sampled:
+            if part.nb != self.nb:
+                raise ValueError("sampled strata over %d positions, exact ones over %d" % (part.nb, self.nb))
+            if not _same_ratio(part.kinds, self.kinds):
+                raise ValueError("sampled strata drawn with kinds %r do not match %r" % (part.kinds, self.kinds))
+            live = set(part.weights[part.samples > 0].tolist())
+            if live & seen:
+                raise ValueError("two sampled strata of one weight")
+            seen |= live
+        self.weights = np.array(sorted(set(exact.weights) | seen), dtype=np.int64)
+
+    def _parts(self, field):
+        """weight -> (f_w, N_w), N_w = 0 for an exact stratum."""
+        out = {}
+        for part in self.sampled:
+            for w, n, f in zip(part.weights.tolist(), part.samples.tolist(), part.fractions(field)):
+                if n > 0:
+                    out[w] = (float(f), n)
+        for w, f in zip(self.exact.weights, self.exact.fractions(self.kinds, field)):
+            out[w] = (float(f), 0)
+        return out
+
+    def fractions(self, field='logical_any'):
+        parts = self._parts(field)
+        return np.array([parts[w][0] for w in self.weights.tolist()])
+
+    def rate(self, p_t, field='logical_any'):
+        b_all = binomial_weights(self.nb, p_t)
+        parts = self._parts(field)
+        have = np.zeros(self.nb + 1, dtype=bool)
+        have[self.weights] = True
+        return StratifiedRate(math.fsum(b_all[w] * f for w, (f, n) in parts.items()),
+                              math.sqrt(math.fsum(b_all[w]**2 * f * (1.0 - f) / n for w, (f, n) in parts.items() if n > 0)),
+                              math.fsum(b_all[~have]))
+
+    def curve(self, p_values, field='logical_any'):
+        rows = np.array([self.rate(p, field) for p in p_values], dtype=np.float64).reshape(-1, 3)
+        return rows[:, 0], rows[:, 1], rows[:, 2]
+
+
+def enumerate_sharded(circuit, weights, group=None, local_fn=None):
+    """The whole strata `weights` of a FaultCircuit over the ranks of a process group: every weight's rank range [0, C(L, w)) is cut
+    by shard_range, this rank enumerates its part, and one all-reduce sums the counts.  `local_fn(circuit, weights, first_rank,
+    count)` replaces circuit.enumerate_strata (the CPU tests pass the host statement).  Returns an ExactStrata."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+    else:
+        rank, world = 0, 1
+    weights = [int(w) for w in np.asarray(weights).reshape(-1)]
+    shards = [shard_range(0, math.comb(circuit.num_locations, w), rank, world) for w in weights]
+    fn = local_fn or (lambda circ, ws, first_rank, count: circ.enumerate_strata(ws, first_rank=first_rank, count=count))
+    part = fn(circuit, weights, [start for start, _ in shards], [mine for _, mine in shards])
+    total, = all_reduce_histograms([np.concatenate([c.reshape(-1) for c in part.counts]) if weights else np.zeros(0, dtype=np.uint64)],
+                                   group=group)
+    counts, at = [], 0
+    for w in weights:
+        size = (w + 1) * (w + 1) * len(DECODE_FIELDS)
+        counts.append(total[at:at + size])
+        at += size
+    return ExactStrata(circuit.num_locations, weights, counts)
