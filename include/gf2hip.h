@@ -422,6 +422,47 @@ int gf2_circuit_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t r1, 
                           int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, int64_t w,
                           int64_t first_rank, int64_t count, uint64_t* counts_out);
 
+/* ---- the error-correction cycle: Steane's gadget under circuit-level faults ---------------------------
+ * [build-defined, DESIGN.md "Error-correction cycle"; CSSCode.error_correct, css_code.py:436-470]  Two additions to the frame model,
+ * accepted by gf2_circuit_effects_timed only.  GF2_GATE_RESET on a clears the frame of a (e_x[a] = e_z[a] = 0), then its one fault
+ * location (g, a) models a preparation fault.  Every outcome row r has a time row_time[r] in [0, ngates]: its value is
+ * row_x . e_x ^ row_z . e_z on the frame just before gate row_time[r] acts (ngates: the final frame).  A measurement is a set of
+ * timed rows, its error an IDLE gate on every measured qubit immediately before.  With all times = ngates and no RESET the table
+ * is gf2_circuit_effects' bit for bit.  Same limits and errors, plus GF2_E_ARG for a time outside [0, ngates]. */
+#define GF2_GATE_RESET 3
+int gf2_circuit_effects_timed(const int32_t* gates, int64_t ngates, int64_t n, const uint64_t* rows_x, const uint64_t* rows_z,
+                              int64_t nrows, int64_t ld, uint64_t* eff_out, int64_t ldr, int64_t capacity, int64_t* locations_out,
+                              int64_t* nloc_out, const int64_t* row_time);
+
+/* Outcome words of a cycle of `rounds` rounds, ldr = 1 + rounds + F (F >= 1 words of flag rows), 1 <= r_1, r_2 <= 31:
+ *   word 0, the final data frame: bits 0 .. r_2 - 1 key_x = vec_to_int(parity_check_c2 . e_x) (row 0 the most significant of the r_2
+ *     bits), bit 31 z_operator . e_x, bits 32 .. 32 + r_1 - 1 key_z, bit 63 x_operator . e_z;
+ *   words 1 .. rounds: round t's measured key_x in bits 0 .. r_2 - 1 and key_z in bits 32 .. 32 + r_1 - 1;
+ *   words rounds + 1 .. ldr - 1: the flag rows (the verifications of the ancilla preparations), in measurement order.
+ * Tally rule per sample: accepted iff every flag word is zero (repeat-until-success as post-selection).  Accepted, on each side
+ * independently (x: key_x, parity_check_c2's table, flip bytes z_operator . correction; z: key_z, c1's, x_operator . correction),
+ * with K = 0 and P = 0: for t = 1 .. rounds, s = key_t ^ K; found: K ^= s, P ^= the entry's flip byte; not found: nothing is
+ * recorded (css_code.py:655-657) and round_unmatched counts once.  Then s = key_final ^ K, flip = parity_final ^ P; found:
+ * flip ^= the entry's flip byte; not found: uncorrectable counts.  counts[GF2_EC_FIELDS]: accepted, logical_x, logical_z,
+ * logical_any, uncorrectable_x, uncorrectable_z, round_unmatched_x, round_unmatched_z -- all but the first among accepted samples. */
+#define GF2_EC_FIELDS 8
+#define GF2_EC_MAX_ROUNDS 6
+
+/* The rule on the host, serial, no GPU needed: words is count x ldw (ldw >= ldr); keys are one word per entry, tables as
+ * gf2_mc_circuit_decode takes them.  class_out (may be null): one byte per sample, bit 0 accepted, bit 1 flip_x, bit 2 flip_z, bit 3
+ * uncorrectable x, bit 4 uncorrectable z (0 for a rejected sample).  GF2_E_ARG, naming the limit: r > 31, rounds outside
+ * [1, GF2_EC_MAX_ROUNDS], ldr > GF2_CIRCUIT_MAX_LDR, ldr < rounds + 2, a key twice in a table. */
+int gf2_ec_tally_host(const uint64_t* words, int64_t count, int64_t ldw, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                      const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                      int64_t entries2, uint64_t* counts_out, uint8_t* class_out);
+
+/* The same tally of samples first_sample .. first_sample + count - 1 on the device, drawn as gf2_circuit_outcomes_dev draws them;
+ * no outcome word is stored.  The circuit's ldr must be 1 + rounds + F, and its effects may set no bit outside the keys, the two
+ * parity bits and the flag words.  counts_out[GF2_EC_FIELDS] on the host. */
+int gf2_mc_ec_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                     int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed,
+                     int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

@@ -20,6 +20,8 @@ COMM_ID_BYTES = 128
 LAYOUT_SAMPLE_MAJOR, LAYOUT_BIT_SLICED, LAYOUT_TILED = 0, 1, 2
 HIST_FULL, HIST_WEIGHT = 0, 1
 GATE_H, GATE_CNOT, GATE_IDLE = 0, 1, 2
+GATE_RESET = 3                                      # circuit_effects_timed only
+EC_FIELDS_COUNT, EC_MAX_ROUNDS = 8, 6
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 ENUMERATE_MAX_WEIGHT = 8
@@ -113,6 +115,10 @@ SIGNATURES = {
     "gf2_mc_run": [_p, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                    ctypes.c_int, _p, _c_i64, _p, _c_i64],
     "gf2_circuit_effects": [_p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _c_i64, _c_i64, _p, ctypes.POINTER(_c_i64)],
+    "gf2_circuit_effects_timed": [_p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _c_i64, _c_i64, _p, ctypes.POINTER(_c_i64), _p],
+    "gf2_ec_tally_host": [_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _p],
+    "gf2_mc_ec_decode": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double,
+                         ctypes.c_double, ctypes.c_double, _p],
     "gf2_circuit_create": [_p, _p, _c_i64, _c_i64, _pp],
     "gf2_circuit_destroy": [_p, _p],
     "gf2_circuit_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p, _c_i64],
@@ -310,6 +316,43 @@ def circuit_effects(gates, n, rows_x, rows_z, ldr=None):
     locations = np.zeros((max(1, total), 2), dtype=np.int64)
     check(lib().gf2_circuit_effects(*args, _ptr(eff), ldr, total, _ptr(locations), ctypes.byref(count)))
     return eff[:total], locations[:total]
+
+
+def circuit_effects_timed(gates, n, rows_x, rows_z, row_time, ldr=None):
+    """gf2_circuit_effects_timed (host code, no GPU): circuit_effects with GATE_RESET among the kinds and one time per outcome row
+    in [0, len(gates)] -- row r is read on the frame just before gate row_time[r] (DESIGN.md "Error-correction cycle")."""
+    gates = np.ascontiguousarray(gates, dtype=np.int32).reshape(-1, 3)
+    rows_x = np.ascontiguousarray(rows_x, dtype="<u8")
+    rows_z = np.ascontiguousarray(rows_z, dtype="<u8")
+    row_time = np.ascontiguousarray(row_time, dtype=np.int64).reshape(-1)
+    if rows_x.ndim != 2 or rows_x.shape != rows_z.shape or len(row_time) != rows_x.shape[0]:
+        raise ValueError("rows_x and rows_z must be packed 2-D arrays of one shape, with one time per row")
+    nrows = rows_x.shape[0]
+    ldr = max(1, words_for(nrows)) if ldr is None else int(ldr)
+    count = _c_i64(0)
+    args = (_ptr(gates) if len(gates) else None, len(gates), int(n), _ptr(rows_x) if nrows else None,
+            _ptr(rows_z) if nrows else None, nrows, rows_x.shape[1])
+    times = _ptr(row_time) if nrows else None
+    check(lib().gf2_circuit_effects_timed(*args, None, ldr, 0, None, ctypes.byref(count), times))
+    total = int(count.value)
+    eff = np.zeros((max(1, total), 2, ldr), dtype="<u8")
+    locations = np.zeros((max(1, total), 2), dtype=np.int64)
+    check(lib().gf2_circuit_effects_timed(*args, _ptr(eff), ldr, total, _ptr(locations), ctypes.byref(count), times))
+    return eff[:total], locations[:total]
+
+
+def ec_tally_host(words, rounds, r1, keys1, flips1, r2, keys2, flips2, ldr=None, classes=False):
+    """gf2_ec_tally_host (host code, no GPU): the eight counts of the error-correction cycle's tally rule over outcome words
+    (count, ldw); ldr (default ldw) is the cycle's 1 + rounds + F.  classes=True also returns the class byte of every sample."""
+    words = np.ascontiguousarray(words, dtype="<u8")
+    if words.ndim != 2:
+        raise ValueError("words must be (samples, ldw)")
+    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+    counts = np.zeros(EC_FIELDS_COUNT, dtype=np.uint64)
+    cls = np.zeros(max(1, len(words)), dtype=np.uint8)
+    check(lib().gf2_ec_tally_host(_ptr(words) if len(words) else None, len(words), words.shape[1], words.shape[1] if ldr is None else int(ldr),
+                                  int(rounds), int(r1), *t1, int(r2), *t2, _ptr(counts), _ptr(cls) if classes else None))
+    return (counts, cls[:len(words)]) if classes else counts
 
 
 def stratum_errors(nb, w, count, kinds=(1, 1, 1), seed=0, first=0):
@@ -757,6 +800,14 @@ class Context(object):
         check(lib().gf2_mc_circuit_decode(self.handle, circ.handle, r1, _ptr(k1) if e1 else None, None if f1 is None or not e1 else _ptr(f1),
                                           e1, r2, _ptr(k2) if e2 else None, None if f2 is None or not e2 else _ptr(f2), e2,
                                           seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, _ptr(counts)))
+        return counts
+
+    def mc_ec_decode(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z):
+        """gf2_mc_ec_decode: the eight counts of the error-correction cycle's tally over samples [first, first + count)."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        counts = np.zeros(EC_FIELDS_COUNT, dtype=np.uint64)
+        check(lib().gf2_mc_ec_decode(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF, first,
+                                     count, p_x, p_y, p_z, _ptr(counts)))
         return counts
 
     def mc_circuit_decode_strata(self, circ, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x, k_y, k_z):

@@ -63,6 +63,23 @@ def _parity_bytes(words, operator):
     return (np.unpackbits(masked.view(np.uint8), axis=1).sum(axis=1) & 1).astype(np.uint8)
 
 
+def code_tables(code):
+    """(keys1, flips1, keys2, flips2) of a code's syndrome tables: keys as gf2_mc_decode_hashed takes them and one flip byte per
+    entry (x_operator . correction for C1's table, z_operator . correction for C2's), cached on the code object like decode_local's."""
+    cached = getattr(code, "_hashed_table_arrays", None)
+    if cached is None or cached[0] is not code._c1_syndromes or cached[1] is not code._c2_syndromes:
+        cached = (code._c1_syndromes, code._c2_syndromes, montecarlo.table_entries(code._c1_syndromes, code.r_1, code.n),
+                  montecarlo.table_entries(code._c2_syndromes, code.r_2, code.n))
+        code._hashed_table_arrays = cached
+    flips = getattr(code, "_circuit_flip_arrays", None)
+    if flips is None or flips[0] is not cached:
+        two = lambda vec: np.pad(_native.pack_rows(np.asarray(vec).reshape(1, -1))[0], (0, 2))[:2]
+        flips = (cached, _parity_bytes(cached[2][1], two(code.x_operator_matrix()[0])),
+                 _parity_bytes(cached[3][1], two(code.z_operator_matrix()[0])))
+        code._circuit_flip_arrays = flips
+    return cached[2][0], flips[1], cached[3][0], flips[2]
+
+
 class FaultCircuit(object):
     """
     A gate list on n qubits with outcome rows, prepared for the Monte-Carlo: the effect table (host) and, on first use, its
@@ -142,20 +159,7 @@ class FaultCircuit(object):
         return {'hist_z': hist_z, 'hist_x': hist_x, 'mode': mode}
 
     def _tables(self):
-        """Keys (as gf2_mc_decode_hashed takes them) and one flip byte per entry, cached on the code object like decode_local's."""
-        code = self.code
-        cached = getattr(code, "_hashed_table_arrays", None)
-        if cached is None or cached[0] is not code._c1_syndromes or cached[1] is not code._c2_syndromes:
-            cached = (code._c1_syndromes, code._c2_syndromes, montecarlo.table_entries(code._c1_syndromes, code.r_1, code.n),
-                      montecarlo.table_entries(code._c2_syndromes, code.r_2, code.n))
-            code._hashed_table_arrays = cached
-        flips = getattr(code, "_circuit_flip_arrays", None)
-        if flips is None or flips[0] is not cached:
-            two = lambda vec: np.pad(_native.pack_rows(np.asarray(vec).reshape(1, -1))[0], (0, 2))[:2]
-            flips = (cached, _parity_bytes(cached[2][1], two(code.x_operator_matrix()[0])),
-                     _parity_bytes(cached[3][1], two(code.z_operator_matrix()[0])))
-            code._circuit_flip_arrays = flips
-        return cached[2][0], flips[1], cached[3][0], flips[2]
+        return code_tables(self.code)
 
     def logical_error_rates(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
         """Table decode + logical tally of the final frame by CSSCode.logical_error_rates' rule; the same dict of counts."""

@@ -22,9 +22,7 @@
 
 #include "gf2_internal.h"
 #include "gf2_circuit_dev.h"
-#include "gf2_sampler.h"
 
-#define CIRC_TAKEN_STRIDE 17                   // dwords per lane: 16 hold the 512 bits
 #define CIRC_BINS_LDS 4096                     // both histograms together, privatised in LDS up to this many bins
 #define CIRC_STRATUM_MAX GF2_CIRCUIT_STRATUM_MAX_WEIGHT
 
@@ -104,32 +102,7 @@ __global__ __launch_bounds__(CIRC_THREADS) void circuit_kernel(CircuitArgs a) {
 #pragma unroll
         for (int w = 0; w < LDR; ++w) out[w] = 0;
         if constexpr (STRATUM) stratum_faults<LDR>(a, eff, ks, out);
-        for (int s = 0; s < (STRATUM ? 0 : a.th.nseg); ++s) {
-            const bool last = s == a.th.nseg - 1;
-            const int nb = last ? a.th.nb_last : GF2_SEG_BITS;
-            const u64 d = segment_draw(ks, (u64)s);
-            const int K = error_count(d, nb, cdf_lds + (last ? GF2_SEG_CDF : 0));
-            if (K > 1)
-                for (int w = 0; w < (nb + 31) >> 5; ++w) mine[w] = 0;
-            for (int k = 0; k < K; ++k) {
-                unsigned int t, kind;
-                error_draw(d, k, K, nb, a.th.t_1, a.th.t_2, &t, &kind);
-                unsigned int pos = t;
-                if (K > 1) {                                                       // Floyd's rule: a candidate already taken -> j
-                    if ((mine[t >> 5] >> (t & 31u)) & 1u) pos = (unsigned int)(nb - K + k);
-                    mine[pos >> 5] |= 1u << (pos & 31u);
-                }
-                const u64* e = eff + (size_t)(2 * (s * GF2_SEG_BITS + (int)pos)) * LDR;   // pos < nb: a location below L
-                if (kind & 1u) {
-#pragma unroll
-                    for (int w = 0; w < LDR; ++w) out[w] ^= e[w];
-                }
-                if (kind & 2u) {
-#pragma unroll
-                    for (int w = 0; w < LDR; ++w) out[w] ^= e[LDR + w];
-                }
-            }
-        }
+        if constexpr (!STRATUM) circuit_gather<LDR>(a.th, cdf_lds, eff, mine, ks, out);
         if constexpr (EPI == CIRC_STORE) {
 #pragma unroll
             for (int w = 0; w < LDR; ++w) a.out[i * a.ldo + w] = out[w];

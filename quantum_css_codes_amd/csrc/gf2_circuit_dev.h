@@ -1,12 +1,15 @@
-// What gf2_circuit.hip (the fault Monte-Carlo) and gf2_enumerate.hip (the exact strata) share: the circuit object, the Monte-Carlo
-// layout of its outcome words and the device side of the tally's syndrome tables.
+// What gf2_circuit.hip (the fault Monte-Carlo), gf2_enumerate.hip (the exact strata) and gf2_ec.hip (the error-correction cycle)
+// share: the circuit object, the Monte-Carlo layout of its outcome words, the device side of the tally's syndrome tables and the
+// gather loop of a Monte-Carlo sample.
 #pragma once
 
 #include "gf2_internal.h"
 #include "gf2_hash_dev.h"
+#include "gf2_sampler.h"
 
 #define CIRC_THREADS 256
 #define CIRC_EFF_LDS_BYTES 20480               // effect tables up to this size are staged in LDS
+#define CIRC_TAKEN_STRIDE 17                   // dwords per lane: 16 hold the 512 bits
 
 struct gf2_circuit {
     int64_t locations, ldr;
@@ -98,3 +101,37 @@ struct CircuitTables {
         return rc;
     }
 };
+
+// The faults of Monte-Carlo sample `ks` XOR-ed into out[]: the sampler run over the circuit's locations segment by segment
+// (cdf_lds: the two staged inverse-CDF tables), every fault's effect gathered from eff (LDS or global).  mine: this lane's 512-bit
+// "taken" map for Floyd's rule, only touched by a segment with at least two faults.
+template <int LDR>
+__device__ __forceinline__ void circuit_gather(const SegTables& th, const u64* cdf_lds, const u64* eff, unsigned int* mine, u64 ks,
+                                               u64 (&out)[LDR]) {
+    for (int s = 0; s < th.nseg; ++s) {
+        const bool last = s == th.nseg - 1;
+        const int nb = last ? th.nb_last : GF2_SEG_BITS;
+        const u64 d = segment_draw(ks, (u64)s);
+        const int K = error_count(d, nb, cdf_lds + (last ? GF2_SEG_CDF : 0));
+        if (K > 1)
+            for (int w = 0; w < (nb + 31) >> 5; ++w) mine[w] = 0;
+        for (int k = 0; k < K; ++k) {
+            unsigned int t, kind;
+            error_draw(d, k, K, nb, th.t_1, th.t_2, &t, &kind);
+            unsigned int pos = t;
+            if (K > 1) {                                                       // Floyd's rule: a candidate already taken -> j
+                if ((mine[t >> 5] >> (t & 31u)) & 1u) pos = (unsigned int)(nb - K + k);
+                mine[pos >> 5] |= 1u << (pos & 31u);
+            }
+            const u64* e = eff + (size_t)(2 * (s * GF2_SEG_BITS + (int)pos)) * LDR;   // pos < nb: a location below L
+            if (kind & 1u) {
+#pragma unroll
+                for (int w = 0; w < LDR; ++w) out[w] ^= e[w];
+            }
+            if (kind & 2u) {
+#pragma unroll
+                for (int w = 0; w < LDR; ++w) out[w] ^= e[LDR + w];
+            }
+        }
+    }
+}

@@ -174,45 +174,60 @@ int gf2_unpack_rows_i64(const uint64_t* src, int64_t m, int64_t n, int64_t ld, i
     return unpack_rows_host<int64_t>(src, m, n, ld, dst, dst_stride);
 }
 
+}  // extern "C"
+
 // Effect table of a circuit's fault locations (DESIGN.md "Circuit faults"): a serial chain of ngates column operations on two
 // nrows x n bit matrices kept by COLUMN (cx[q], cz[q]: rw words each), walked backwards from the outcome rows.  Pauli-frame
 // propagation is linear over GF(2), so the column of qubit q at the moment just after gate g says which outcomes an X (cx) or
 // a Z (cz) fault on q at that moment flips.
-int gf2_circuit_effects(const int32_t* gates, int64_t ngates, int64_t n, const uint64_t* rows_x, const uint64_t* rows_z,
-                        int64_t nrows, int64_t ld, uint64_t* eff_out, int64_t ldr, int64_t capacity, int64_t* locations_out,
-                        int64_t* nloc_out) {
-    if (!nloc_out || (ngates > 0 && !gates)) GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: null argument");
+// row_time (null: every row on the final frame) and RESET are gf2_circuit_effects_timed's (DESIGN.md "Error-correction cycle"): a row
+// of time T joins the columns when the walk passes from gate T to gate T - 1, and a RESET on a emits its location (the preparation
+// fault) and then clears a's columns -- nothing before the reset reaches a later outcome through a.
+static int circuit_effects_walk(const char* who, bool timed, const int32_t* gates, int64_t ngates, int64_t n, const uint64_t* rows_x,
+                                const uint64_t* rows_z, int64_t nrows, int64_t ld, uint64_t* eff_out, int64_t ldr, int64_t capacity,
+                                int64_t* locations_out, int64_t* nloc_out, const int64_t* row_time) {
+    if (!nloc_out || (ngates > 0 && !gates)) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
     if (ngates < 0 || n < 1 || n > GF2_CIRCUIT_MAX_N || nrows < 0 || nrows > GF2_CIRCUIT_MAX_ROWS || capacity < 0)
-        GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: needs 1 <= n <= %d, nrows <= %d and non-negative counts", GF2_CIRCUIT_MAX_N,
-                 GF2_CIRCUIT_MAX_ROWS);
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= n <= %d, nrows <= %d and non-negative counts", who, GF2_CIRCUIT_MAX_N, GF2_CIRCUIT_MAX_ROWS);
     int64_t total = 0;
     for (int64_t g = 0; g < ngates; ++g) {
         const int32_t kind = gates[3 * g], a = gates[3 * g + 1], b = gates[3 * g + 2];
-        if (kind != GF2_GATE_H && kind != GF2_GATE_CNOT && kind != GF2_GATE_IDLE)
-            GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: gate %lld has unknown kind %d", (long long)g, (int)kind);
+        if (kind != GF2_GATE_H && kind != GF2_GATE_CNOT && kind != GF2_GATE_IDLE && !(timed && kind == GF2_GATE_RESET))
+            GF2_FAIL(GF2_E_ARG, "%s: gate %lld has unknown kind %d", who, (long long)g, (int)kind);
         if (a < 0 || a >= n || (kind == GF2_GATE_CNOT && (b < 0 || b >= n)))
-            GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: gate %lld acts on a qubit outside [0, %lld)", (long long)g, (long long)n);
-        if (kind == GF2_GATE_CNOT && a == b)
-            GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: gate %lld is a CNOT of qubit %d with itself", (long long)g, (int)a);
+            GF2_FAIL(GF2_E_ARG, "%s: gate %lld acts on a qubit outside [0, %lld)", who, (long long)g, (long long)n);
+        if (kind == GF2_GATE_CNOT && a == b) GF2_FAIL(GF2_E_ARG, "%s: gate %lld is a CNOT of qubit %d with itself", who, (long long)g, (int)a);
         total += kind == GF2_GATE_CNOT ? 2 : 1;
     }
+    if (timed && nrows > 0 && !row_time) GF2_FAIL(GF2_E_ARG, "%s: null row_time", who);
+    for (int64_t r = 0; timed && r < nrows; ++r)
+        if (row_time[r] < 0 || row_time[r] > ngates)
+            GF2_FAIL(GF2_E_ARG, "%s: row %lld has time %lld outside [0, ngates = %lld]", who, (long long)r, (long long)row_time[r], (long long)ngates);
     *nloc_out = total;
     if (capacity < total) return GF2_OK;                                // (capacity 0 just counts)
     const int64_t rw = gf2_words(nrows);
-    if (total > 0 && (!eff_out || ldr < rw || ldr < 1)) GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: eff_out needs ldr >= ceil(nrows / 64) words");
-    if (nrows > 0 && (!rows_x || !rows_z || ld < gf2_words(n))) GF2_FAIL(GF2_E_ARG, "gf2_circuit_effects: rows need ld >= ceil(n / 64) words");
+    if (total > 0 && (!eff_out || ldr < rw || ldr < 1)) GF2_FAIL(GF2_E_ARG, "%s: eff_out needs ldr >= ceil(nrows / 64) words", who);
+    if (nrows > 0 && (!rows_x || !rows_z || ld < gf2_words(n))) GF2_FAIL(GF2_E_ARG, "%s: rows need ld >= ceil(n / 64) words", who);
     std::vector<uint64_t> cx, cz;
+    std::vector<int64_t> order;                                         // timed: the rows by falling time
     try {
         cx.assign((size_t)(n * rw), 0);
         cz.assign((size_t)(n * rw), 0);
+        if (timed) {
+            order.resize((size_t)nrows);
+            for (int64_t r = 0; r < nrows; ++r) order[(size_t)r] = r;
+            std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return row_time[x] > row_time[y]; });
+        }
     } catch (const std::bad_alloc&) {
-        GF2_FAIL(GF2_E_NOMEM, "gf2_circuit_effects: out of host memory");
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
     }
-    for (int64_t r = 0; r < nrows; ++r)
+    auto join = [&](int64_t r) {
         for (int64_t q = 0; q < n; ++q) {
             cx[q * rw + (r >> 6)] |= ((rows_x[r * ld + (q >> 6)] >> (q & 63)) & 1ull) << (r & 63);
             cz[q * rw + (r >> 6)] |= ((rows_z[r * ld + (q >> 6)] >> (q & 63)) & 1ull) << (r & 63);
         }
+    };
+    for (int64_t r = 0; !timed && r < nrows; ++r) join(r);
     int64_t l = total;
     auto emit = [&](int64_t g, int64_t q) {
         l -= 1;
@@ -222,7 +237,9 @@ int gf2_circuit_effects(const int32_t* gates, int64_t ngates, int64_t n, const u
         }
         if (locations_out) locations_out[2 * l] = g, locations_out[2 * l + 1] = q;
     };
+    size_t next = 0;
     for (int64_t g = ngates - 1; g >= 0; --g) {
+        for (; timed && next < order.size() && row_time[order[next]] > g; ++next) join(order[next]);
         const int32_t kind = gates[3 * g], a = gates[3 * g + 1], b = gates[3 * g + 2];
         if (kind == GF2_GATE_CNOT) emit(g, b);
         emit(g, a);
@@ -230,8 +247,26 @@ int gf2_circuit_effects(const int32_t* gates, int64_t ngates, int64_t n, const u
             for (int64_t w = 0; w < rw; ++w) std::swap(cx[a * rw + w], cz[a * rw + w]);
         else if (kind == GF2_GATE_CNOT)
             for (int64_t w = 0; w < rw; ++w) cx[a * rw + w] ^= cx[b * rw + w], cz[b * rw + w] ^= cz[a * rw + w];
+        else if (kind == GF2_GATE_RESET)
+            for (int64_t w = 0; w < rw; ++w) cx[a * rw + w] = 0, cz[a * rw + w] = 0;
     }
     return GF2_OK;
+}
+
+extern "C" {
+
+int gf2_circuit_effects(const int32_t* gates, int64_t ngates, int64_t n, const uint64_t* rows_x, const uint64_t* rows_z,
+                        int64_t nrows, int64_t ld, uint64_t* eff_out, int64_t ldr, int64_t capacity, int64_t* locations_out,
+                        int64_t* nloc_out) {
+    return circuit_effects_walk("gf2_circuit_effects", false, gates, ngates, n, rows_x, rows_z, nrows, ld, eff_out, ldr, capacity,
+                                locations_out, nloc_out, nullptr);
+}
+
+int gf2_circuit_effects_timed(const int32_t* gates, int64_t ngates, int64_t n, const uint64_t* rows_x, const uint64_t* rows_z,
+                              int64_t nrows, int64_t ld, uint64_t* eff_out, int64_t ldr, int64_t capacity, int64_t* locations_out,
+                              int64_t* nloc_out, const int64_t* row_time) {
+    return circuit_effects_walk("gf2_circuit_effects_timed", true, gates, ngates, n, rows_x, rows_z, nrows, ld, eff_out, ldr, capacity,
+                                locations_out, nloc_out, row_time);
 }
 
 // A stratum's errors (DESIGN.md "Strata"), the host statement of what decode_strata_kernel and circuit_kernel's stratum mode draw:
@@ -431,6 +466,70 @@ int gf2_circuit_enumerate_host(const uint64_t* eff, int64_t locations, int64_t l
             if (k == w) break;
             kind[k] += 1;
         }
+    }
+    return GF2_OK;
+}
+
+// The tally rule of the error-correction cycle (DESIGN.md "Error-correction cycle"), serial: quil_classical_correct's record of known
+// errors (css_code.py:649-685) round by round as (syndrome K, operator parity P) per side, then gf2_mc_circuit_decode's judgement of
+// the final data frame relative to that record.
+int gf2_ec_tally_host(const uint64_t* words, int64_t count, int64_t ldw, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                      const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                      uint64_t* counts_out, uint8_t* class_out) {
+    const char* who = "gf2_ec_tally_host";
+    if (!counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
+    if (rounds < 1 || rounds > GF2_EC_MAX_ROUNDS) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= rounds <= %d, got %lld", who, GF2_EC_MAX_ROUNDS, (long long)rounds);
+    if (ldr > GF2_CIRCUIT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per sample, got %lld", who, GF2_CIRCUIT_MAX_LDR, (long long)ldr);
+    if (ldr < rounds + 2)
+        GF2_FAIL(GF2_E_ARG, "%s: %lld rounds need ldr = 1 + rounds + F words with F >= 1 flag words, got %lld", who, (long long)rounds, (long long)ldr);
+    if (count < 0 || ldw < ldr || (count > 0 && !words)) GF2_FAIL(GF2_E_ARG, "%s: needs count >= 0 samples of ldw >= ldr words", who);
+    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !flips1)) || (entries2 && (!keys2 || !flips2)))
+        GF2_FAIL(GF2_E_ARG, "%s: bad table (a null array with entries > 0, or a negative count)", who);
+    for (int k = 0; k < GF2_EC_FIELDS; ++k) counts_out[k] = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];                                                        // [0]: x side, parity_check_c2's table; [1]: z side, c1's
+    try {
+        if (!tab[0].make(keys2, flips2, entries2, 1) || !tab[1].make(keys1, flips1, entries1, 1))
+            GF2_FAIL(GF2_E_ARG, "%s: a syndrome key occurs twice in a table", who);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    for (int64_t i = 0; i < count; ++i) {
+        const uint64_t* w = words + i * ldw;
+        uint64_t flags = 0;
+        for (int64_t q = rounds + 1; q < ldr; ++q) flags |= w[q];
+        if (flags) {
+            if (class_out) class_out[i] = 0;
+            continue;
+        }
+        bool flip[2], miss[2];
+        uint64_t unmatched[2] = {0, 0};
+        for (int c = 0; c < 2; ++c) {
+            uint64_t K = 0, P = 0;
+            for (int64_t t = 1; t <= rounds; ++t) {
+                const uint64_t s = ((w[t] >> (32 * c)) & mask[c]) ^ K;
+                const int found = tab[c].find(0, s);
+                if (found < 0)
+                    unmatched[c] += 1;                                       // css_code.py:655-657: no match, nothing recorded
+                else
+                    K ^= s, P ^= (uint64_t)found;
+            }
+            const uint64_t s = ((w[0] >> (32 * c)) & mask[c]) ^ K;
+            const int found = tab[c].find(0, s);
+            miss[c] = found < 0;
+            flip[c] = (((w[0] >> (32 * c + 31)) & 1ull) ^ P ^ (uint64_t)(found > 0)) != 0;
+        }
+        counts_out[0] += 1;
+        counts_out[1] += flip[0];
+        counts_out[2] += flip[1];
+        counts_out[3] += flip[0] | flip[1];
+        counts_out[4] += miss[0];
+        counts_out[5] += miss[1];
+        counts_out[6] += unmatched[0];
+        counts_out[7] += unmatched[1];
+        if (class_out) class_out[i] = (uint8_t)(1 | flip[0] << 1 | flip[1] << 2 | miss[0] << 3 | miss[1] << 4);
     }
     return GF2_OK;
 }

@@ -371,6 +371,27 @@ class CSSCode(QECC):
         from . import circuit_noise
         return self.circuit_logical_error_strata_exact(circuit_noise.encoder_gates(self, state), weights, **options)
 
+    # -- build-defined: the error-correction cycle under faults (ec_noise.py; DESIGN.md "Error-correction cycle") ---------
+    def error_correct_gates(self, rounds=1, idle_data=False):
+        """[build-defined]  The gate list (H, CNOT, IDLE, RESET on 3n qubits: data, ancilla_1, ancilla_2) and the timed outcome rows
+        of `rounds` rounds of `error_correct` (css_code.py:436-470) with one attempt per ancilla preparation: an ec_noise.ECGates."""
+        from . import ec_noise
+        return ec_noise.error_correct_gates(self, rounds, idle_data)
+
+    def error_correct_logical_error_rates(self, num_samples, p_x, p_y, p_z, rounds=1, seed=0, first_sample=0, idle_data=False):
+        """[build-defined]  The logical error rate per cycle of `rounds` rounds of `error_correct` when every fault location of the
+        gadget fails independently: a dict of ec_noise.EC_FIELDS (counts; all but 'accepted' among accepted samples) plus
+        'samples'.  Repeat-until-success is post-selection on the verifications (ec_noise's docstring); counts of sample ranges
+        add, so sharding by first_sample needs no collective of its own."""
+        from . import ec_noise
+        return ec_noise.circuit_for(self, rounds, idle_data).logical_error_rates(num_samples, p_x, p_y, p_z, seed=seed,
+                                                                                 first_sample=first_sample)
+
+    def error_correct_single_faults(self, rounds=1):
+        """[build-defined]  The census of every single fault of the cycle, no GPU needed: ECCircuit.single_faults."""
+        from . import ec_noise
+        return ec_noise.circuit_for(self, rounds).single_faults()
+
 
 # -- free functions -----------------------------------------------------------------------------------------
 

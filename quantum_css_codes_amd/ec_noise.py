@@ -1,0 +1,224 @@
+"""
+Fault Monte-Carlo of the error-correction cycle [build-defined; DESIGN.md "Error-correction cycle"].
+
+The encoders circuit_noise.py studies are a sub-circuit of what the reference builds them for: CSSCode.error_correct
+(css_code.py:436-470), Steane's error-correction gadget.  This module says how often that gadget fails: the logical error rate
+per cycle of `rounds` rounds at physical fault rates (p_x, p_y, p_z) per location.
+
+Registers: three blocks of n qubits, data D = 0 .. n-1, A1 = n .. 2n-1, A2 = 2n .. 3n-1.  A round is, as css_code.py:458-470,
+    prep(A1, plus); CNOT D[i] -> A1[i]; measure A1 against parity_check_c2 (this round's key_x);
+    prep(A1, zero); CNOT A1[i] -> D[i]; H on A1; measure A1 against parity_check_c1 (key_z)
+and prep(B, s) is ONE attempt of encode_plus / encode_zero (css_code.py:314-366): RESET B, the noisy encoder, _error_detect_x and
+_error_detect_z against a freshly reset and encoded A2 (css_code.py:472-533).  Every row of those detections is a flag row.
+A measurement is no gate: it is a set of outcome rows read at its moment (a time per row), and its error is one IDLE gate on
+every measured qubit immediately before.  RESET clears the frame of its qubit and has one fault location (a preparation fault).
+
+Repeat-until-success is post-selection.  One sample is one draw of the Monte-Carlo sampler over all L locations -- one attempt
+per preparation -- and a sample with any flag bit set is rejected.  Attempts are independent, and the model puts no fault on the
+data block while it waits, so the accepted samples have exactly the distribution of the reference's while_do loop;
+samples / accepted is the expected number of whole-cycle attempts per accepted one under this model.
+
+Corrections are recorded (CodeBlock.x_errors, quil_classical_correct, css_code.py:649-685), never applied to the qubits, so
+everything but the table lookups is linear over GF(2) and one effect table carries the whole gadget.  The tally rule -- round
+t's syndrome decoded relative to what earlier rounds recorded, the final data frame judged against the record -- is stated in
+DESIGN.md and include/gf2hip.h; gf2_ec_tally_host is its serial form and gf2_mc_ec_decode the device kernel.
+"""
+import numpy as np
+
+from . import _native
+from . import circuit_noise
+
+GATE_H, GATE_CNOT, GATE_IDLE, GATE_RESET = _native.GATE_H, _native.GATE_CNOT, _native.GATE_IDLE, _native.GATE_RESET
+MAX_ROUNDS = _native.EC_MAX_ROUNDS
+EC_FIELDS = ('accepted', 'logical_x', 'logical_z', 'logical_any', 'uncorrectable_x', 'uncorrectable_z', 'round_unmatched_x',
+             'round_unmatched_z')
+ROW_UNUSED, ROW_FINAL, ROW_ROUND, ROW_FLAG = 0, 1, 2, 3
+KINDS = ('X', 'Y', 'Z')                             # the columns of single_faults' class bytes
+CLASS_ACCEPTED, CLASS_FLIP_X, CLASS_FLIP_Z, CLASS_UNCORRECTABLE_X, CLASS_UNCORRECTABLE_Z = 1, 2, 4, 8, 16
+
+
+class ECGates(object):
+    """What error_correct_gates returns: `gates` (g, 3) int32 rows (kind, a, b) on `qubits` = 3n qubits; the outcome rows `rows_x`,
+    `rows_z` (64 * ldr, 3n) uint8, row r being bit r & 63 of outcome word r >> 6, with their times `row_time`; `row_kind` (ROW_UNUSED,
+    ROW_FINAL, ROW_ROUND, ROW_FLAG) and `row_round` (1 .. rounds for round and flag rows, else 0); `flag_rows`, the rows of the
+    verifications in measurement order."""
+
+    def __init__(self, gates, qubits, rounds, ldr, rows_x, rows_z, row_time, row_kind, row_round, flag_rows):
+        self.gates, self.qubits, self.rounds, self.ldr = gates, qubits, rounds, ldr
+        self.rows_x, self.rows_z, self.row_time, self.row_kind, self.row_round = rows_x, rows_z, row_time, row_kind, row_round
+        self.flag_rows = flag_rows
+
+    @property
+    def num_rows(self):
+        return int(np.count_nonzero(self.row_kind))
+
+
+def _encoder(code, state, qubits):
+    from .css_code import CSSCode                   # (any object with n, r_1, r_2 and the two checks will do)
+    make = CSSCode.encode_zero_gates if state == 'zero' else CSSCode.encode_plus_gates
+    return make(code, qubits).tolist()
+
+
+def error_correct_gates(code, rounds=1, idle_data=False):
+    """The gate list and timed outcome rows of `rounds` rounds of CSSCode.error_correct (the module docstring has the order), one
+    attempt per preparation; idle_data adds one IDLE per data qubit at the start of each round.  Returns an ECGates."""
+    n, r_1, r_2 = int(code.n), int(code.r_1), int(code.r_2)
+    rounds = int(rounds)
+    if min(r_1, r_2) < 1 or max(r_1, r_2) > 31:
+        raise ValueError("the error-correction cycle needs 1 <= r_1, r_2 <= 31 (both keys of a frame share an outcome word)")
+    if not 1 <= rounds <= MAX_ROUNDS:
+        raise ValueError("the error-correction cycle needs 1 <= rounds <= %d" % MAX_ROUNDS)
+    h_1, h_2 = np.asarray(code.parity_check_c1), np.asarray(code.parity_check_c2)
+    z_op, x_op = np.asarray(code.z_operator_matrix()), np.asarray(code.x_operator_matrix())
+    data, anc_1, anc_2 = (list(range(b * n, (b + 1) * n)) for b in range(3))
+    gates = []
+    rows = []                                       # (bit or None for a flag, kind, round, time, block, side, vector)
+
+    def measure(block, matrix, kind, rnd, bits):
+        gates.extend((GATE_IDLE, q, 0) for q in block)              # measurement error
+        for row, bit in zip(matrix, bits):
+            rows.append((bit, kind, rnd, len(gates), block, 0, row))
+
+    def detect_x(block, rnd, include_operators):                    # css_code.py:472-501
+        gates.extend((GATE_RESET, q, 0) for q in anc_2)
+        gates.extend(_encoder(code, 'zero' if include_operators else 'plus', anc_2))
+        gates.extend((GATE_CNOT, b, a) for b, a in zip(block, anc_2))
+        matrix = np.concatenate([h_2, z_op]) if include_operators else h_2
+        measure(anc_2, matrix, ROW_FLAG, rnd, [None] * len(matrix))
+
+    def detect_z(block, rnd, include_operators):                    # css_code.py:503-533
+        gates.extend((GATE_RESET, q, 0) for q in anc_2)
+        gates.extend(_encoder(code, 'plus' if include_operators else 'zero', anc_2))
+        gates.extend((GATE_CNOT, a, b) for b, a in zip(block, anc_2))
+        gates.extend((GATE_H, a, 0) for a in anc_2)
+        matrix = np.concatenate([h_1, x_op]) if include_operators else h_1
+        measure(anc_2, matrix, ROW_FLAG, rnd, [None] * len(matrix))
+
+    def prep(block, state, rnd):                                    # css_code.py:314-366, one attempt
+        gates.extend((GATE_RESET, q, 0) for q in block)
+        gates.extend(_encoder(code, state, block))
+        detect_x(block, rnd, include_operators=state == 'zero')
+        detect_z(block, rnd, include_operators=state == 'plus')
+
+    for t in range(1, rounds + 1):                                  # css_code.py:458-470
+        if idle_data:
+            gates.extend((GATE_IDLE, q, 0) for q in data)
+        prep(anc_1, 'plus', t)
+        gates.extend((GATE_CNOT, d, a) for d, a in zip(data, anc_1))
+        measure(anc_1, h_2, ROW_ROUND, t, [64 * t + r_2 - 1 - i for i in range(r_2)])
+        prep(anc_1, 'zero', t)
+        gates.extend((GATE_CNOT, a, d) for d, a in zip(data, anc_1))
+        gates.extend((GATE_H, a, 0) for a in anc_1)
+        measure(anc_1, h_1, ROW_ROUND, t, [64 * t + 32 + r_1 - 1 - i for i in range(r_1)])
+    end = len(gates)
+    for i in range(r_2):                                            # vec_to_int: row 0 is the most significant bit
+        rows.append((r_2 - 1 - i, ROW_FINAL, 0, end, data, 0, h_2[i]))
+    rows.append((31, ROW_FINAL, 0, end, data, 0, z_op[0]))
+    for i in range(r_1):
+        rows.append((32 + r_1 - 1 - i, ROW_FINAL, 0, end, data, 1, h_1[i]))
+    rows.append((63, ROW_FINAL, 0, end, data, 1, x_op[0]))
+
+    flags = sum(1 for row in rows if row[0] is None)
+    ldr = 1 + rounds + (flags + 63) // 64
+    if ldr > _native.CIRCUIT_MAX_LDR:
+        raise ValueError("%d rounds with %d flag rows need %d outcome words per sample, more than %d"
+                         % (rounds, flags, ldr, _native.CIRCUIT_MAX_LDR))
+    rows_x = np.zeros((64 * ldr, 3 * n), dtype=np.uint8)
+    rows_z = np.zeros_like(rows_x)
+    row_time = np.full(64 * ldr, end, dtype=np.int64)
+    row_kind = np.zeros(64 * ldr, dtype=np.int8)
+    row_round = np.zeros(64 * ldr, dtype=np.int8)
+    flag_rows = []
+    for bit, kind, rnd, time, block, side, vector in rows:
+        if bit is None:
+            bit = 64 * (1 + rounds) + len(flag_rows)
+            flag_rows.append(bit)
+        (rows_z if side else rows_x)[bit, block] = np.asarray(vector) & 1
+        row_time[bit], row_kind[bit], row_round[bit] = time, kind, rnd
+    return ECGates(np.array(gates, dtype=np.int32).reshape(-1, 3), 3 * n, rounds, ldr, rows_x, rows_z, row_time, row_kind, row_round,
+                   np.array(flag_rows, dtype=np.int64))
+
+
+class ECCircuit(object):
+    """The error-correction cycle of a code prepared for the Monte-Carlo: the gadget (error_correct_gates), its effect table
+    (gf2_circuit_effects_timed, host code) and, on first use, the device copy."""
+
+    def __init__(self, code, rounds=1, idle_data=False):
+        self.code = code
+        self.rounds = int(rounds)
+        self.gadget = error_correct_gates(code, rounds, idle_data)
+        self.ldr = self.gadget.ldr
+        self.effects, self.locations = _native.circuit_effects_timed(
+            self.gadget.gates, self.gadget.qubits, _native.pack_rows(self.gadget.rows_x), _native.pack_rows(self.gadget.rows_z),
+            self.gadget.row_time, ldr=self.ldr)
+        self._device = None
+
+    @property
+    def num_locations(self):
+        return len(self.locations)
+
+    def device(self):
+        if self._device is None:
+            if not 1 <= self.num_locations <= circuit_noise.MAX_LOCATIONS:
+                raise ValueError("the Monte-Carlo needs 1 <= L <= %d (2^20) fault locations, the cycle has %d"
+                                 % (circuit_noise.MAX_LOCATIONS, self.num_locations))
+            self._device = _native.default_context().circuit_create(self.effects)
+        return self._device
+
+    def _tables(self):
+        keys1, flips1, keys2, flips2 = circuit_noise.code_tables(self.code)
+        return self.code.r_1, keys1, flips1, self.code.r_2, keys2, flips2
+
+    def outcomes(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """The outcome words of samples [first_sample, first_sample + num_samples), rejected ones included: a (num_samples, ldr)
+        uint64 array (gf2_circuit_outcomes_dev)."""
+        ctx = _native.default_context()
+        circ = self.device()
+        count = int(num_samples)
+        buf = ctx.alloc(max(1, count) * self.ldr * 8)
+        ctx.circuit_outcomes_dev(circ, int(seed), int(first_sample), count, float(p_x), float(p_y), float(p_z), buf, self.ldr)
+        out = buf.download((count, self.ldr), np.uint64)
+        buf.free()
+        return out
+
+    def logical_error_rates(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """The tally of samples [first_sample, first_sample + num_samples) on the device: a dict of EC_FIELDS plus 'samples'.
+        Every field after 'accepted' counts among accepted samples; the counts of sample ranges add."""
+        counts = _native.default_context().mc_ec_decode(self.device(), self.rounds, *self._tables(), int(seed), int(first_sample),
+                                                        int(num_samples), float(p_x), float(p_y), float(p_z))
+        out = {name: int(v) for name, v in zip(EC_FIELDS, counts)}
+        out['samples'] = int(num_samples)
+        return out
+
+    def tally_host(self, words, classes=False):
+        """The tally rule over outcome words (samples, ldr) on the host (gf2_ec_tally_host, no GPU): the dict of EC_FIELDS plus
+        'samples'; classes=True returns (dict, class byte per sample) instead."""
+        words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, self.ldr)
+        got = _native.ec_tally_host(words, self.rounds, *self._tables(), classes=classes)
+        counts = got[0] if classes else got
+        out = {name: int(v) for name, v in zip(EC_FIELDS, counts)}
+        out['samples'] = len(words)
+        return (out, got[1]) if classes else out
+
+    def single_faults(self):
+        """The census of all 3 L single faults, no GPU: (classes, flipping) -- classes (L, 3) uint8, the class byte (CLASS_* bits)
+        of an X, Y, Z fault (the columns, KINDS) at every location; flipping, the accepted faults with a logical flip as
+        (gate index, gate (kind, a, b), qubit, 'X' / 'Y' / 'Z')."""
+        eff = self.effects
+        words = np.stack((eff[:, 0], eff[:, 0] ^ eff[:, 1], eff[:, 1]), axis=1)              # X, Y, Z
+        _, classes = self.tally_host(words.reshape(-1, self.ldr), classes=True)
+        classes = classes.reshape(-1, 3)
+        flipping = []
+        for l, k in zip(*np.nonzero((classes & CLASS_ACCEPTED != 0) & (classes & (CLASS_FLIP_X | CLASS_FLIP_Z) != 0))):
+            g, q = (int(v) for v in self.locations[l])
+            flipping.append((g, tuple(int(v) for v in self.gadget.gates[g]), q, KINDS[k]))
+        return classes, flipping
+
+
+def circuit_for(code, rounds=1, idle_data=False):
+    """ECCircuit(code, rounds, idle_data), cached on the code object."""
+    cache = code.__dict__.setdefault("_ec_circuits", {})
+    key = (int(rounds), bool(idle_data))
+    if key not in cache:
+        cache[key] = ECCircuit(code, rounds, idle_data)
+    return cache[key]
