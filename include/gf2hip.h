@@ -463,6 +463,49 @@ int gf2_mc_ec_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, i
                      int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed,
                      int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, uint64_t* counts_out);
 
+/* ---- the fault-tolerant logical measurement: a rewritten one-qubit program under circuit-level faults ----
+ * [build-defined, DESIGN.md "Logical measurement"; ftqc.rewrite_program, ftqc.py:76-95; CSSCode.measure / noisy_measure,
+ * css_code.py:542-646]  The program is a sequence of steps in program order, nsteps of them, and bit s of measure_mask says that
+ * step s is a MEASURE step (one trial of the logical measurement) and not an EC step (one round of error_correct on the data).
+ * Outcome words, ldr = nsteps + F (F >= 1 words of flag rows), 1 <= r_1, r_2 <= 31, ldr <= GF2_FT_MAX_LDR:
+ *   word s of an EC step: the measured key_x in bits 0 .. r_2 - 1 and key_z in bits 32 .. 32 + r_1 - 1 (row 0 the most significant);
+ *   word s of a MEASURE step: key_x in bits 0 .. r_2 - 1 and z_operator . e_x of the measured ancilla in bit 31; the high half zero;
+ *   words nsteps .. ldr - 1: the flag rows (the verifications of every preparation), in measurement order.
+ * There is no final-frame word: the result is classical.  Tally rule per sample (quil_classical_correct, css_code.py:649-685, which
+ * corrections and measurements share because both update data.x_errors): accepted iff every flag word is zero.  Accepted, with
+ * K_x = P_x = K_z = P_z = 0, for s = 0 .. nsteps - 1: an EC step does, on each side, v = key ^ K; found: K ^= v, P ^= the entry's
+ * flip byte; not found: unmatched counts.  A MEASURE step does the same on the x side only, and then its trial is wrong iff
+ * bit 31 ^ P_x is 1.  The sample is wrong iff more than half of its trials are.  counts[GF2_FT_FIELDS]: accepted, wrong,
+ * trial_wrong (wrong trials summed), first_trial_wrong, split_vote (trials not unanimous), unmatched_x, unmatched_z -- all but the
+ * first among accepted samples. */
+#define GF2_FT_FIELDS  7
+#define GF2_FT_MAX_LDR 16
+
+/* The rule on the host, serial, no GPU needed (replaces running the rewritten program's classical side, css_code.py:542-589 and
+ * :649-685, per sample): words is count x ldw (ldw >= ldr), tables as gf2_ec_tally_host takes them.  class_out (may be null): one
+ * byte per sample, bit 0 accepted, bit 1 wrong, bit 2 first trial wrong, bit 3 split vote, bit 4 an unmatched x key, bit 5 an
+ * unmatched z key (0 for a rejected sample).  GF2_E_ARG, naming the limit: r > 31, ldr > GF2_FT_MAX_LDR, nsteps outside
+ * [1, ldr - 1], a measure_mask with bits at or above nsteps or with an even number of bits, a key twice in a table. */
+int gf2_ft_tally_host(const uint64_t* words, int64_t count, int64_t ldw, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                      const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                      const uint8_t* flips2, int64_t entries2, uint64_t* counts_out, uint8_t* class_out);
+
+/* gf2_circuit_create for the effect table of a rewritten program (ftqc.py:76-95): 1 <= ldr <= GF2_FT_MAX_LDR words per effect.
+ * The circuit is destroyed by gf2_circuit_destroy.  One with ldr > GF2_CIRCUIT_MAX_LDR is taken by gf2_ft_outcomes_dev and
+ * gf2_mc_ft_decode only: every other entry point refuses it with GF2_E_ARG. */
+int gf2_ft_circuit_create(gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int64_t ldr, gf2_circuit** circuit_out);
+
+/* gf2_circuit_outcomes_dev for 1 <= ldr <= GF2_FT_MAX_LDR (the rewritten program run once per sample, test_fidelity.py's loop). */
+int gf2_ft_outcomes_dev(gf2_ctx* ctx, const gf2_circuit* circuit, uint64_t seed, int64_t first_sample, int64_t count, double p_x,
+                        double p_y, double p_z, uint64_t* out_dev, int64_t ldo);
+
+/* The tally of samples first_sample .. first_sample + count - 1 on the device (test_fidelity.py's trial loop over the rewritten
+ * program), drawn as gf2_ft_outcomes_dev draws them; no outcome word is stored.  The circuit's ldr must be nsteps + F with
+ * 8 <= ldr <= GF2_FT_MAX_LDR, and its effects may set no bit outside the layout above.  counts_out[GF2_FT_FIELDS] on the host. */
+int gf2_mc_ft_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, uint64_t measure_mask, int64_t r1, const uint64_t* keys1,
+                     const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                     uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

@@ -22,6 +22,7 @@ HIST_FULL, HIST_WEIGHT = 0, 1
 GATE_H, GATE_CNOT, GATE_IDLE = 0, 1, 2
 GATE_RESET = 3                                      # circuit_effects_timed only
 EC_FIELDS_COUNT, EC_MAX_ROUNDS = 8, 6
+FT_FIELDS_COUNT, FT_MAX_LDR = 7, 16
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 ENUMERATE_MAX_WEIGHT = 8
@@ -118,6 +119,11 @@ SIGNATURES = {
     "gf2_circuit_effects_timed": [_p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _c_i64, _c_i64, _p, ctypes.POINTER(_c_i64), _p],
     "gf2_ec_tally_host": [_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _p],
     "gf2_mc_ec_decode": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double,
+                         ctypes.c_double, ctypes.c_double, _p],
+    "gf2_ft_tally_host": [_p, _c_i64, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _p],
+    "gf2_ft_circuit_create": [_p, _p, _c_i64, _c_i64, _pp],
+    "gf2_ft_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p, _c_i64],
+    "gf2_mc_ft_decode": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double,
                          ctypes.c_double, ctypes.c_double, _p],
     "gf2_circuit_create": [_p, _p, _c_i64, _c_i64, _pp],
     "gf2_circuit_destroy": [_p, _p],
@@ -355,6 +361,21 @@ def ec_tally_host(words, rounds, r1, keys1, flips1, r2, keys2, flips2, ldr=None,
     return (counts, cls[:len(words)]) if classes else counts
 
 
+def ft_tally_host(words, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, ldr=None, classes=False):
+    """gf2_ft_tally_host (host code, no GPU): the seven counts of the logical measurement's tally rule over outcome words
+    (count, ldw); ldr (default ldw) is the program's nsteps + F.  classes=True also returns the class byte of every sample."""
+    words = np.ascontiguousarray(words, dtype="<u8")
+    if words.ndim != 2:
+        raise ValueError("words must be (samples, ldw)")
+    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+    counts = np.zeros(FT_FIELDS_COUNT, dtype=np.uint64)
+    cls = np.zeros(max(1, len(words)), dtype=np.uint8)
+    check(lib().gf2_ft_tally_host(_ptr(words) if len(words) else None, len(words), words.shape[1], words.shape[1] if ldr is None else int(ldr),
+                                  int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2), *t2, _ptr(counts),
+                                  _ptr(cls) if classes else None))
+    return (counts, cls[:len(words)]) if classes else counts
+
+
 def stratum_errors(nb, w, count, kinds=(1, 1, 1), seed=0, first=0):
     """gf2_stratum_errors (host code, no GPU): the packed (e_x, e_z) rows, count x words(nb) each, of samples [first, first + count)
     of the stratum of weight w over nb positions (DESIGN.md "Strata")."""
@@ -501,14 +522,15 @@ class Check(object):
 class Circuit(object):
     """The effect table of a circuit's fault locations on the device (gf2_circuit_create).  eff: (L, 2, ldr) packed words."""
 
-    def __init__(self, ctx, eff):
+    def __init__(self, ctx, eff, ft=False):
         self.ctx = ctx
         eff = np.ascontiguousarray(eff, dtype="<u8")
         if eff.ndim != 3 or eff.shape[1] != 2:
             raise ValueError("effects must be an (L, 2, ldr) array")
         self.locations, self.ldr = int(eff.shape[0]), int(eff.shape[2])
         out = ctypes.c_void_p()
-        check(lib().gf2_circuit_create(ctx.handle, _ptr(eff), self.locations, self.ldr, ctypes.byref(out)))
+        create = lib().gf2_ft_circuit_create if ft else lib().gf2_circuit_create             # (ft: up to FT_MAX_LDR words)
+        check(create(ctx.handle, _ptr(eff), self.locations, self.ldr, ctypes.byref(out)))
         self.handle = out.value
 
     def free(self):
@@ -808,6 +830,21 @@ class Context(object):
         counts = np.zeros(EC_FIELDS_COUNT, dtype=np.uint64)
         check(lib().gf2_mc_ec_decode(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF, first,
                                      count, p_x, p_y, p_z, _ptr(counts)))
+        return counts
+
+    def ft_circuit_create(self, eff):
+        """gf2_ft_circuit_create: an effect table of up to FT_MAX_LDR words, for ft_outcomes_dev and mc_ft_decode only."""
+        return Circuit(self, eff, ft=True)
+
+    def ft_outcomes_dev(self, circ, seed, first, count, p_x, p_y, p_z, out_buf, ldo):
+        check(lib().gf2_ft_outcomes_dev(self.handle, circ.handle, seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, out_buf.ptr, ldo))
+
+    def mc_ft_decode(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z):
+        """gf2_mc_ft_decode: the seven counts of the logical measurement's tally over samples [first, first + count)."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        counts = np.zeros(FT_FIELDS_COUNT, dtype=np.uint64)
+        check(lib().gf2_mc_ft_decode(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2), *t2,
+                                     seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, _ptr(counts)))
         return counts
 
     def mc_circuit_decode_strata(self, circ, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x, k_y, k_z):

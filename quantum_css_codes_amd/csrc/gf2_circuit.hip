@@ -209,22 +209,21 @@ static int circuit_launch(gf2_ctx* ctx, const gf2_circuit* circ, CircuitArgs& a,
     return GF2_OK;
 }
 
-extern "C" {
-
-int gf2_circuit_create(gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int64_t ldr, gf2_circuit** circuit_out) {
-    if (!ctx || !eff || !circuit_out) GF2_FAIL(GF2_E_ARG, "gf2_circuit_create: null argument");
+int gf2_circuit_create_upto(const char* who, gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t max_ldr,
+                            gf2_circuit** circuit_out) {
+    if (!ctx || !eff || !circuit_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
     *circuit_out = nullptr;
     if (locations < 1 || locations > GF2_CIRCUIT_MAX_LOCATIONS)
-        GF2_FAIL(GF2_E_ARG, "gf2_circuit_create: needs 1 <= locations <= %d (2^20), got %lld", GF2_CIRCUIT_MAX_LOCATIONS, (long long)locations);
-    if (ldr < 1 || ldr > GF2_CIRCUIT_MAX_LDR)
-        GF2_FAIL(GF2_E_ARG, "gf2_circuit_create: needs 1 <= ldr <= %d words per effect, got %lld", GF2_CIRCUIT_MAX_LDR, (long long)ldr);
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= locations <= %d (2^20), got %lld", who, GF2_CIRCUIT_MAX_LOCATIONS, (long long)locations);
+    if (ldr < 1 || ldr > max_ldr)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= ldr <= %d words per effect, got %lld", who, (int)max_ldr, (long long)ldr);
     GF2_TRY(gf2_ctx_activate(ctx));
     gf2_circuit* circ = new (std::nothrow) gf2_circuit();
-    if (!circ) GF2_FAIL(GF2_E_NOMEM, "gf2_circuit_create: out of host memory");
+    if (!circ) GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
     circ->locations = locations;
     circ->ldr = ldr;
     circ->eff_dev = nullptr;
-    for (int w = 0; w < GF2_CIRCUIT_MAX_LDR; ++w) circ->any[w] = 0;
+    for (int w = 0; w < GF2_FT_MAX_LDR; ++w) circ->any[w] = 0;
     for (int64_t i = 0; i < 2 * locations; ++i)
         for (int64_t w = 0; w < ldr; ++w) circ->any[w] |= eff[i * ldr + w];
     const size_t bytes = (size_t)2 * locations * ldr * 8;
@@ -239,6 +238,12 @@ int gf2_circuit_create(gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int
     return GF2_OK;
 }
 
+extern "C" {
+
+int gf2_circuit_create(gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int64_t ldr, gf2_circuit** circuit_out) {
+    return gf2_circuit_create_upto("gf2_circuit_create", ctx, eff, locations, ldr, GF2_CIRCUIT_MAX_LDR, circuit_out);
+}
+
 int gf2_circuit_destroy(gf2_ctx* ctx, gf2_circuit* circuit) {
     if (!ctx) GF2_FAIL(GF2_E_ARG, "gf2_circuit_destroy: null context");
     if (!circuit) return GF2_OK;
@@ -250,6 +255,8 @@ int gf2_circuit_destroy(gf2_ctx* ctx, gf2_circuit* circuit) {
 int gf2_circuit_outcomes_dev(gf2_ctx* ctx, const gf2_circuit* circuit, uint64_t seed, int64_t first_sample, int64_t count,
                              double p_x, double p_y, double p_z, uint64_t* out_dev, int64_t ldo) {
     if (!ctx || !circuit) GF2_FAIL(GF2_E_ARG, "gf2_circuit_outcomes_dev: null argument");
+    if (circuit->ldr > GF2_CIRCUIT_MAX_LDR)                               // (a gf2_ft_circuit_create one: gf2_ft_outcomes_dev stores it)
+        GF2_FAIL(GF2_E_ARG, "gf2_circuit_outcomes_dev: needs ldr <= %d words per sample, got %lld", GF2_CIRCUIT_MAX_LDR, (long long)circuit->ldr);
     if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "gf2_circuit_outcomes_dev: negative range");
     if (ldo < circuit->ldr) GF2_FAIL(GF2_E_ARG, "gf2_circuit_outcomes_dev: ldo must be at least the circuit's %lld words", (long long)circuit->ldr);
     GF2_TRY(check_probabilities(p_x, p_y, p_z));

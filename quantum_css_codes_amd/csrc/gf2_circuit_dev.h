@@ -1,5 +1,5 @@
-// What gf2_circuit.hip (the fault Monte-Carlo), gf2_enumerate.hip (the exact strata) and gf2_ec.hip (the error-correction cycle)
-// share: the circuit object, the Monte-Carlo layout of its outcome words, the device side of the tally's syndrome tables and the
+// What gf2_circuit.hip (the fault Monte-Carlo), gf2_enumerate.hip (the exact strata), gf2_ec.hip (the error-correction cycle) and
+// gf2_ft.hip (the fault-tolerant logical measurement) share: the circuit object, the Monte-Carlo layout of its outcome words, the device side of the tally's syndrome tables and the
 // gather loop of a Monte-Carlo sample.
 #pragma once
 
@@ -14,8 +14,12 @@
 struct gf2_circuit {
     int64_t locations, ldr;
     u64* eff_dev;                              // 2 * locations * ldr words
-    u64 any[GF2_CIRCUIT_MAX_LDR];              // OR of all effects, word by word: which outcome bits can be set at all
+    u64 any[GF2_FT_MAX_LDR];                   // OR of all effects, word by word: which outcome bits can be set at all
 };
+
+// gf2_circuit.hip: gf2_circuit_create for 1 <= ldr <= max_ldr (gf2_ft_circuit_create's GF2_FT_MAX_LDR: gf2_ft.hip)
+int gf2_circuit_create_upto(const char* who, gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t max_ldr,
+                            gf2_circuit** circuit_out);
 
 // gf2_host.cpp: the argument rules of an enumerated rank range (include/gf2hip.h "exact strata")
 int gf2_enum_check_range(const char* who, int64_t nb, int64_t w, int64_t first_rank, int64_t count);

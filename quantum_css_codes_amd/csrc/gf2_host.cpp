@@ -534,4 +534,76 @@ int gf2_ec_tally_host(const uint64_t* words, int64_t count, int64_t ldw, int64_t
     return GF2_OK;
 }
 
+// The tally rule of the fault-tolerant logical measurement (DESIGN.md "Logical measurement"), serial: the record of known errors
+// (syndrome K, operator parity P per side) runs through the steps in program order; an EC step updates both sides, a MEASURE step
+// the x side only (noisy_measure corrects data.x_errors, css_code.py:636-639) and reads its trial's bit against the updated record;
+// the majority of the trials is the result (css_code.py:580-583).
+int gf2_ft_tally_host(const uint64_t* words, int64_t count, int64_t ldw, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                      const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                      const uint8_t* flips2, int64_t entries2, uint64_t* counts_out, uint8_t* class_out) {
+    const char* who = "gf2_ft_tally_host";
+    if (!counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
+    if (ldr > GF2_FT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per sample, got %lld", who, GF2_FT_MAX_LDR, (long long)ldr);
+    if (nsteps < 1 || ldr < nsteps + 1)
+        GF2_FAIL(GF2_E_ARG, "%s: needs nsteps >= 1 and ldr = nsteps + F words with F >= 1 flag words, got nsteps = %lld and ldr = %lld", who,
+                 (long long)nsteps, (long long)ldr);
+    if (measure_mask >> nsteps) GF2_FAIL(GF2_E_ARG, "%s: measure_mask has bits at or above nsteps = %lld", who, (long long)nsteps);
+    const int trials = __builtin_popcountll(measure_mask);
+    if (trials % 2 == 0) GF2_FAIL(GF2_E_ARG, "%s: a majority vote needs an odd number of trials, measure_mask has %d", who, trials);
+    if (count < 0 || ldw < ldr || (count > 0 && !words)) GF2_FAIL(GF2_E_ARG, "%s: needs count >= 0 samples of ldw >= ldr words", who);
+    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !flips1)) || (entries2 && (!keys2 || !flips2)))
+        GF2_FAIL(GF2_E_ARG, "%s: bad table (a null array with entries > 0, or a negative count)", who);
+    for (int k = 0; k < GF2_FT_FIELDS; ++k) counts_out[k] = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];                                                        // [0]: x side, parity_check_c2's table; [1]: z side, c1's
+    try {
+        if (!tab[0].make(keys2, flips2, entries2, 1) || !tab[1].make(keys1, flips1, entries1, 1))
+            GF2_FAIL(GF2_E_ARG, "%s: a syndrome key occurs twice in a table", who);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    for (int64_t i = 0; i < count; ++i) {
+        const uint64_t* w = words + i * ldw;
+        uint64_t flags = 0;
+        for (int64_t q = nsteps; q < ldr; ++q) flags |= w[q];
+        if (flags) {
+            if (class_out) class_out[i] = 0;
+            continue;
+        }
+        uint64_t K[2] = {0, 0}, P[2] = {0, 0}, unmatched[2] = {0, 0};
+        int wrong_trials = 0, seen_trials = 0;
+        bool first_wrong = false;
+        for (int64_t s = 0; s < nsteps; ++s) {
+            const bool measure = (measure_mask >> s) & 1ull;
+            for (int c = 0; c < (measure ? 1 : 2); ++c) {
+                const uint64_t v = ((w[s] >> (32 * c)) & mask[c]) ^ K[c];
+                const int found = tab[c].find(0, v);
+                if (found < 0)
+                    unmatched[c] += 1;                                       // css_code.py:655-657: no match, nothing recorded
+                else
+                    K[c] ^= v, P[c] ^= (uint64_t)found;
+            }
+            if (measure) {
+                const bool bad = (((w[s] >> 31) & 1ull) ^ P[0]) != 0;
+                if (seen_trials == 0) first_wrong = bad;
+                wrong_trials += bad;
+                seen_trials += 1;
+            }
+        }
+        const bool wrong = 2 * wrong_trials > trials, split = wrong_trials != 0 && wrong_trials != trials;
+        counts_out[0] += 1;
+        counts_out[1] += wrong;
+        counts_out[2] += (uint64_t)wrong_trials;
+        counts_out[3] += first_wrong;
+        counts_out[4] += split;
+        counts_out[5] += unmatched[0];
+        counts_out[6] += unmatched[1];
+        if (class_out)
+            class_out[i] = (uint8_t)(1 | wrong << 1 | first_wrong << 2 | split << 3 | (unmatched[0] != 0) << 4 | (unmatched[1] != 0) << 5);
+    }
+    return GF2_OK;
+}
+
 }  // extern "C"

@@ -392,6 +392,20 @@ class CSSCode(QECC):
         from . import ec_noise
         return ec_noise.circuit_for(self, rounds).single_faults()
 
+    # -- build-defined: the rewritten program's measured bit under faults (ft_noise.py; DESIGN.md "Logical measurement") ---------
+    def logical_program_error_rates(self, ops, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """[build-defined]  How often the bit measured by ftqc.rewrite_program of `ops; MEASURE` (ops: logical 'I', 'X', 'Y', 'Z' on
+        one qubit) is wrong when every fault location of the rewritten program fails independently: a dict of ft_noise.FT_FIELDS
+        (counts; all but 'accepted' among accepted samples) plus 'samples'.  ft_noise.raw_program_error_rate is the bare program's
+        side of the comparison."""
+        from . import ft_noise
+        return ft_noise.program_for(self, ops).measurement_error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample)
+
+    def logical_program_single_faults(self, ops):
+        """[build-defined]  The census of every single fault of the rewritten program, no GPU needed: FTProgram.single_faults."""
+        from . import ft_noise
+        return ft_noise.program_for(self, ops).single_faults()
+
 
 # -- free functions -----------------------------------------------------------------------------------------
 

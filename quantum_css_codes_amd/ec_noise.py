@@ -59,84 +59,109 @@ def _encoder(code, state, qubits):
     return make(code, qubits).tolist()
 
 
+class GadgetBuilder(object):
+    """The gate list and the timed outcome rows of a sequence of gadgets on the three blocks, as they are emitted: `gates`, rows
+    (kind, a, b), and `rows`, tuples (bit or None for a flag row, kind, round, time, block, side, vector).  error_correct_gates
+    and ft_noise.program_gates are written with it."""
+
+    def __init__(self, code):
+        self.code, self.n, self.r_1, self.r_2 = code, int(code.n), int(code.r_1), int(code.r_2)
+        if min(self.r_1, self.r_2) < 1 or max(self.r_1, self.r_2) > 31:
+            raise ValueError("the error-correction cycle needs 1 <= r_1, r_2 <= 31 (both keys of a frame share an outcome word)")
+        self.h_1, self.h_2 = np.asarray(code.parity_check_c1), np.asarray(code.parity_check_c2)
+        self.z_op, self.x_op = np.asarray(code.z_operator_matrix()), np.asarray(code.x_operator_matrix())
+        self.data, self.anc_1, self.anc_2 = (list(range(b * self.n, (b + 1) * self.n)) for b in range(3))
+        self.gates = []
+        self.rows = []
+
+    def measure(self, block, matrix, kind, rnd, bits):
+        self.gates.extend((GATE_IDLE, q, 0) for q in block)         # measurement error
+        for row, bit in zip(matrix, bits):
+            self.rows.append((bit, kind, rnd, len(self.gates), block, 0, row))
+
+    def detect_x(self, block, verifier, rnd, include_operators):    # css_code.py:472-501
+        self.gates.extend((GATE_RESET, q, 0) for q in verifier)
+        self.gates.extend(_encoder(self.code, 'zero' if include_operators else 'plus', verifier))
+        self.gates.extend((GATE_CNOT, b, a) for b, a in zip(block, verifier))
+        matrix = np.concatenate([self.h_2, self.z_op]) if include_operators else self.h_2
+        self.measure(verifier, matrix, ROW_FLAG, rnd, [None] * len(matrix))
+
+    def detect_z(self, block, verifier, rnd, include_operators):    # css_code.py:503-533
+        self.gates.extend((GATE_RESET, q, 0) for q in verifier)
+        self.gates.extend(_encoder(self.code, 'plus' if include_operators else 'zero', verifier))
+        self.gates.extend((GATE_CNOT, a, b) for b, a in zip(block, verifier))
+        self.gates.extend((GATE_H, a, 0) for a in verifier)
+        matrix = np.concatenate([self.h_1, self.x_op]) if include_operators else self.h_1
+        self.measure(verifier, matrix, ROW_FLAG, rnd, [None] * len(matrix))
+
+    def prep(self, block, state, rnd, verifier=None):               # css_code.py:314-366, one attempt
+        verifier = self.anc_2 if verifier is None else verifier
+        self.gates.extend((GATE_RESET, q, 0) for q in block)
+        self.gates.extend(_encoder(self.code, state, block))
+        self.detect_x(block, verifier, rnd, include_operators=state == 'zero')
+        self.detect_z(block, verifier, rnd, include_operators=state == 'plus')
+
+    def error_correct(self, rnd, word):                             # css_code.py:458-470; the keys go to outcome word `word`
+        r_1, r_2 = self.r_1, self.r_2
+        self.prep(self.anc_1, 'plus', rnd)
+        self.gates.extend((GATE_CNOT, d, a) for d, a in zip(self.data, self.anc_1))
+        self.measure(self.anc_1, self.h_2, ROW_ROUND, rnd, [64 * word + r_2 - 1 - i for i in range(r_2)])
+        self.prep(self.anc_1, 'zero', rnd)
+        self.gates.extend((GATE_CNOT, a, d) for d, a in zip(self.data, self.anc_1))
+        self.gates.extend((GATE_H, a, 0) for a in self.anc_1)
+        self.measure(self.anc_1, self.h_1, ROW_ROUND, rnd, [64 * word + 32 + r_1 - 1 - i for i in range(r_1)])
+
+    @property
+    def num_flags(self):
+        return sum(1 for row in self.rows if row[0] is None)
+
+    def arrays(self, ldr, first_flag_word):
+        """(gates, rows_x, rows_z, row_time, row_kind, row_round, flag_rows) for ldr outcome words, the flag rows from word
+        first_flag_word on in measurement order."""
+        end = len(self.gates)
+        rows_x = np.zeros((64 * ldr, 3 * self.n), dtype=np.uint8)
+        rows_z = np.zeros_like(rows_x)
+        row_time = np.full(64 * ldr, end, dtype=np.int64)
+        row_kind = np.zeros(64 * ldr, dtype=np.int8)
+        row_round = np.zeros(64 * ldr, dtype=np.int8)
+        flag_rows = []
+        for bit, kind, rnd, time, block, side, vector in self.rows:
+            if bit is None:
+                bit = 64 * first_flag_word + len(flag_rows)
+                flag_rows.append(bit)
+            (rows_z if side else rows_x)[bit, block] = np.asarray(vector) & 1
+            row_time[bit], row_kind[bit], row_round[bit] = time, kind, rnd
+        return (np.array(self.gates, dtype=np.int32).reshape(-1, 3), rows_x, rows_z, row_time, row_kind, row_round,
+                np.array(flag_rows, dtype=np.int64))
+
+
 def error_correct_gates(code, rounds=1, idle_data=False):
     """The gate list and timed outcome rows of `rounds` rounds of CSSCode.error_correct (the module docstring has the order), one
     attempt per preparation; idle_data adds one IDLE per data qubit at the start of each round.  Returns an ECGates."""
-    n, r_1, r_2 = int(code.n), int(code.r_1), int(code.r_2)
     rounds = int(rounds)
-    if min(r_1, r_2) < 1 or max(r_1, r_2) > 31:
-        raise ValueError("the error-correction cycle needs 1 <= r_1, r_2 <= 31 (both keys of a frame share an outcome word)")
+    build = GadgetBuilder(code)
     if not 1 <= rounds <= MAX_ROUNDS:
         raise ValueError("the error-correction cycle needs 1 <= rounds <= %d" % MAX_ROUNDS)
-    h_1, h_2 = np.asarray(code.parity_check_c1), np.asarray(code.parity_check_c2)
-    z_op, x_op = np.asarray(code.z_operator_matrix()), np.asarray(code.x_operator_matrix())
-    data, anc_1, anc_2 = (list(range(b * n, (b + 1) * n)) for b in range(3))
-    gates = []
-    rows = []                                       # (bit or None for a flag, kind, round, time, block, side, vector)
-
-    def measure(block, matrix, kind, rnd, bits):
-        gates.extend((GATE_IDLE, q, 0) for q in block)              # measurement error
-        for row, bit in zip(matrix, bits):
-            rows.append((bit, kind, rnd, len(gates), block, 0, row))
-
-    def detect_x(block, rnd, include_operators):                    # css_code.py:472-501
-        gates.extend((GATE_RESET, q, 0) for q in anc_2)
-        gates.extend(_encoder(code, 'zero' if include_operators else 'plus', anc_2))
-        gates.extend((GATE_CNOT, b, a) for b, a in zip(block, anc_2))
-        matrix = np.concatenate([h_2, z_op]) if include_operators else h_2
-        measure(anc_2, matrix, ROW_FLAG, rnd, [None] * len(matrix))
-
-    def detect_z(block, rnd, include_operators):                    # css_code.py:503-533
-        gates.extend((GATE_RESET, q, 0) for q in anc_2)
-        gates.extend(_encoder(code, 'plus' if include_operators else 'zero', anc_2))
-        gates.extend((GATE_CNOT, a, b) for b, a in zip(block, anc_2))
-        gates.extend((GATE_H, a, 0) for a in anc_2)
-        matrix = np.concatenate([h_1, x_op]) if include_operators else h_1
-        measure(anc_2, matrix, ROW_FLAG, rnd, [None] * len(matrix))
-
-    def prep(block, state, rnd):                                    # css_code.py:314-366, one attempt
-        gates.extend((GATE_RESET, q, 0) for q in block)
-        gates.extend(_encoder(code, state, block))
-        detect_x(block, rnd, include_operators=state == 'zero')
-        detect_z(block, rnd, include_operators=state == 'plus')
-
+    r_1, r_2, data = build.r_1, build.r_2, build.data
     for t in range(1, rounds + 1):                                  # css_code.py:458-470
         if idle_data:
-            gates.extend((GATE_IDLE, q, 0) for q in data)
-        prep(anc_1, 'plus', t)
-        gates.extend((GATE_CNOT, d, a) for d, a in zip(data, anc_1))
-        measure(anc_1, h_2, ROW_ROUND, t, [64 * t + r_2 - 1 - i for i in range(r_2)])
-        prep(anc_1, 'zero', t)
-        gates.extend((GATE_CNOT, a, d) for d, a in zip(data, anc_1))
-        gates.extend((GATE_H, a, 0) for a in anc_1)
-        measure(anc_1, h_1, ROW_ROUND, t, [64 * t + 32 + r_1 - 1 - i for i in range(r_1)])
-    end = len(gates)
+            build.gates.extend((GATE_IDLE, q, 0) for q in data)
+        build.error_correct(t, t)
+    end = len(build.gates)
     for i in range(r_2):                                            # vec_to_int: row 0 is the most significant bit
-        rows.append((r_2 - 1 - i, ROW_FINAL, 0, end, data, 0, h_2[i]))
-    rows.append((31, ROW_FINAL, 0, end, data, 0, z_op[0]))
+        build.rows.append((r_2 - 1 - i, ROW_FINAL, 0, end, data, 0, build.h_2[i]))
+    build.rows.append((31, ROW_FINAL, 0, end, data, 0, build.z_op[0]))
     for i in range(r_1):
-        rows.append((32 + r_1 - 1 - i, ROW_FINAL, 0, end, data, 1, h_1[i]))
-    rows.append((63, ROW_FINAL, 0, end, data, 1, x_op[0]))
+        build.rows.append((32 + r_1 - 1 - i, ROW_FINAL, 0, end, data, 1, build.h_1[i]))
+    build.rows.append((63, ROW_FINAL, 0, end, data, 1, build.x_op[0]))
 
-    flags = sum(1 for row in rows if row[0] is None)
+    flags = build.num_flags
     ldr = 1 + rounds + (flags + 63) // 64
     if ldr > _native.CIRCUIT_MAX_LDR:
         raise ValueError("%d rounds with %d flag rows need %d outcome words per sample, more than %d"
                          % (rounds, flags, ldr, _native.CIRCUIT_MAX_LDR))
-    rows_x = np.zeros((64 * ldr, 3 * n), dtype=np.uint8)
-    rows_z = np.zeros_like(rows_x)
-    row_time = np.full(64 * ldr, end, dtype=np.int64)
-    row_kind = np.zeros(64 * ldr, dtype=np.int8)
-    row_round = np.zeros(64 * ldr, dtype=np.int8)
-    flag_rows = []
-    for bit, kind, rnd, time, block, side, vector in rows:
-        if bit is None:
-            bit = 64 * (1 + rounds) + len(flag_rows)
-            flag_rows.append(bit)
-        (rows_z if side else rows_x)[bit, block] = np.asarray(vector) & 1
-        row_time[bit], row_kind[bit], row_round[bit] = time, kind, rnd
-    return ECGates(np.array(gates, dtype=np.int32).reshape(-1, 3), 3 * n, rounds, ldr, rows_x, rows_z, row_time, row_kind, row_round,
-                   np.array(flag_rows, dtype=np.int64))
+    gates, rows_x, rows_z, row_time, row_kind, row_round, flag_rows = build.arrays(ldr, 1 + rounds)
+    return ECGates(gates, 3 * build.n, rounds, ldr, rows_x, rows_z, row_time, row_kind, row_round, flag_rows)
 
 
 class ECCircuit(object):
