@@ -506,6 +506,41 @@ int gf2_mc_ft_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, u
                      const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
                      uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, uint64_t* counts_out);
 
+/* ---- exact strata of the two post-selected gadgets ----------------------------------------------------
+ * [build-defined, DESIGN.md "Exact strata of the cycle" and "Exact strata of the measurement"]  The notions of "exact strata" above,
+ * unchanged: a configuration (S, kappa) of weight w, its outcome words the XOR of its picks' effects, rank(S) in the combinatorial
+ * number system, a call covering ranks [first_rank, first_rank + count) with all 3^w kind assignments each, 0 <= w <=
+ * min(L, GF2_ENUMERATE_MAX_WEIGHT), the same range errors.  What differs is the judgement: the tally rule per sample of the
+ * error-correction cycle (gf2_ec_tally_host) or of the logical measurement (gf2_ft_tally_host), post-selection included.
+ * counts_out[(w + 1)][(w + 1)][F], F = GF2_EC_FIELDS or GF2_FT_FIELDS: entry [n_x][n_y][field] over the configurations of the range
+ * with that kind composition; field 0 is `accepted`, the others count among accepted configurations.  Counts of disjoint ranges add.
+ * With kind weights (k_x, k_y, k_z) of sum s, A_w(field) = sum counts[n_x][n_y][field] k_x^n_x k_y^n_y k_z^n_z / s^w, and
+ * P(accepted and field) = sum_w A_w p^w (1 - p)^(L - w) at total fault probability p per location.
+ *
+ * The definitions on the host, serial, no GPU needed (they stand for running the gadget once per fault configuration:
+ * CSSCode.error_correct, css_code.py:436-470, with its classical side :649-685; ftqc.rewrite_program, ftqc.py:76-95, with
+ * CSSCode.measure, css_code.py:542-589 -- test_fidelity.py's trial loop, one trial per configuration).  eff: 2 * locations * ldr
+ * words as gf2_circuit_effects_timed writes them.  Argument errors as gf2_ec_tally_host's / gf2_ft_tally_host's (r > 31, rounds,
+ * nsteps, the mask, ldr, the tables) and gf2_circuit_enumerate_host's (weight, range), plus GF2_E_ARG for effects that set bits
+ * outside the layout. */
+int gf2_ec_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                          const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                          int64_t entries2, int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out);
+int gf2_ft_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                          const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                          const uint8_t* flips2, int64_t entries2, int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out);
+
+/* The same counts on the device (css_code.py:436-470 and ftqc.py:76-95 as above).  The circuit is one of gf2_circuit_create
+ * (the cycle: ldr = 1 + rounds + F, 3 <= ldr <= GF2_CIRCUIT_MAX_LDR) or of either constructor (the measurement: ldr = nsteps + F,
+ * 8 <= ldr <= GF2_FT_MAX_LDR); its effects may set no bit outside the layout, as gf2_mc_ec_decode / gf2_mc_ft_decode require.
+ * The hash tables are made once, the range is cut into launches of bounded size, the counts come back once. */
+int gf2_ec_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                     int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, int64_t w,
+                     int64_t first_rank, int64_t count, uint64_t* counts_out);
+int gf2_ft_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, uint64_t measure_mask, int64_t r1, const uint64_t* keys1,
+                     const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                     int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

@@ -137,6 +137,10 @@ SIGNATURES = {
     "gf2_subset_unrank": [_c_i64, _c_i64, _c_i64, _p],
     "gf2_circuit_enumerate_host": [_p, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
     "gf2_circuit_enumerate": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
+    "gf2_ec_enumerate_host": [_p, _c_i64, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
+    "gf2_ft_enumerate_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
+    "gf2_ec_enumerate": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
+    "gf2_ft_enumerate": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
     "gf2_comm_unique_id": [_p, ctypes.c_size_t],
     "gf2_comm_create": [_p, _p, ctypes.c_int, ctypes.c_int, _pp],
     "gf2_comm_create_all": [_pp, ctypes.c_int, _pp],
@@ -425,6 +429,31 @@ def circuit_enumerate_host(eff, r1, keys1, flips1, r2, keys2, flips2, w, first_r
     check(lib().gf2_circuit_enumerate_host(_ptr(eff), eff.shape[0], eff.shape[2], r1, *t1, r2, *t2, int(w), int(first_rank), int(count),
                                            _ptr(out)))
     return out
+
+
+def _gadget_enumerate_host(fn, fields, eff, head, tables, w, first_rank, count):
+    eff = np.ascontiguousarray(eff, dtype="<u8")
+    if eff.ndim != 3 or eff.shape[1] != 2:
+        raise ValueError("eff must be (locations, 2, ldr)")
+    r1, keys1, flips1, r2, keys2, flips2 = tables
+    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+    side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
+    out = np.zeros((side, side, fields), dtype=np.uint64)
+    check(fn(_ptr(eff), eff.shape[0], eff.shape[2], *head, int(r1), *t1, int(r2), *t2, int(w), int(first_rank), int(count), _ptr(out)))
+    return out
+
+
+def ec_enumerate_host(eff, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
+    """gf2_ec_enumerate_host (host code, no GPU): the (w + 1, w + 1, 8) uint64 counts [n_x][n_y][field] of the error-correction
+    cycle's tally rule over the subsets of ranks [first_rank, first_rank + count), each with all 3^w kind assignments."""
+    return _gadget_enumerate_host(lib().gf2_ec_enumerate_host, EC_FIELDS_COUNT, eff, (int(rounds),),
+                                  (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count)
+
+
+def ft_enumerate_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
+    """gf2_ft_enumerate_host (host code, no GPU): the (w + 1, w + 1, 7) counts of the logical measurement's tally rule, likewise."""
+    return _gadget_enumerate_host(lib().gf2_ft_enumerate_host, FT_FIELDS_COUNT, eff, (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF),
+                                  (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count)
 
 
 # ---- context ----------------------------------------------------------------------------------------------
@@ -867,6 +896,24 @@ class Context(object):
         return out
 
     # -- syndromes ----------------------------------------------------------------------------------------
+    def ec_enumerate(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
+        """gf2_ec_enumerate: ec_enumerate_host's counts from the device."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
+        out = np.zeros((side, side, EC_FIELDS_COUNT), dtype=np.uint64)
+        check(lib().gf2_ec_enumerate(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, int(w), int(first_rank), int(count),
+                                     _ptr(out)))
+        return out
+
+    def ft_enumerate(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
+        """gf2_ft_enumerate: ft_enumerate_host's counts from the device."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
+        out = np.zeros((side, side, FT_FIELDS_COUNT), dtype=np.uint64)
+        check(lib().gf2_ft_enumerate(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2), *t2,
+                                     int(w), int(first_rank), int(count), _ptr(out)))
+        return out
+
     def check_create(self, packed, r, n):
         return Check(self, packed, r, n)
 

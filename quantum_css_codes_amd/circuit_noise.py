@@ -80,6 +80,29 @@ def code_tables(code):
     return cached[2][0], flips[1], cached[3][0], flips[2]
 
 
+def gadget_enumerate_request(total, weights, first_rank, count, max_configurations, what):
+    """The argument rules of FaultCircuit.enumerate_strata for the gadgets' exact strata (ECCircuit / FTProgram.enumerate_strata):
+    (weights, firsts, counts) as lists of ints, ValueError for a weight, a range or a size that is refused."""
+    weights = [int(w) for w in np.asarray(weights).reshape(-1)]
+    limit = min(total, _native.ENUMERATE_MAX_WEIGHT)
+    if any(w < 0 or w > limit for w in weights):
+        raise ValueError("an enumerated stratum's weight lies in [0, min(L = %d, %d)]" % (total, _native.ENUMERATE_MAX_WEIGHT))
+    if not 1 <= total <= MAX_LOCATIONS:
+        raise ValueError("the enumeration needs 1 <= L <= %d (2^20) fault locations, the %s has %d" % (MAX_LOCATIONS, what, total))
+    subsets = [math.comb(total, w) for w in weights]
+    firsts = [0] * len(weights) if first_rank is None else [int(v) for v in np.broadcast_to(np.asarray(first_rank, dtype=object), (len(weights),))]
+    counts = ([c - f for c, f in zip(subsets, firsts)] if count is None
+              else [int(v) for v in np.broadcast_to(np.asarray(count, dtype=object), (len(weights),))])
+    for w, c, f, n in zip(weights, subsets, firsts, counts):
+        if f < 0 or n < 0 or f + n > c:
+            raise ValueError("ranks [%d, %d + %d) leave the range [0, C(%d, %d) = %d)" % (f, f, n, total, w, c))
+    size = sum(n * 3**w for w, n in zip(weights, counts))
+    budget = ENUMERATE_BUDGET if max_configurations is None else int(max_configurations)
+    if size > budget:
+        raise ValueError("%d fault configurations to enumerate, more than max_configurations = %d" % (size, budget))
+    return weights, firsts, counts
+
+
 class FaultCircuit(object):
     """
     A gate list on n qubits with outcome rows, prepared for the Monte-Carlo: the effect table (host) and, on first use, its

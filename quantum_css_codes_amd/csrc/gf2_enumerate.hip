@@ -14,12 +14,7 @@
 // Tallies: the composition is wave-uniform, so a field's count over the wavefront is the population count of a ballot, added by
 // one lane to the workgroup's LDS bins [n_x][n_y][5] (at most 405 dwords; a launch covers at most ENUM_LAUNCH_CONFIGS < 2^32
 // configurations) only when it is non-zero; the bins go to global memory once per workgroup.
-#include "gf2_circuit_dev.h"
-
-#define ENUM_MAX_W GF2_ENUMERATE_MAX_WEIGHT
-#define ENUM_LAUNCH_CONFIGS (1ll << 30)        // configurations per launch (DESIGN.md "Exact strata")
-#define ENUM_MAX_RUN 32                        // ranks per lane and unranking
-#define ENUM_MAX_BLOCKS 2048                   // 8 workgroups of 256 lanes on each of the 256 CUs
+#include "gf2_enumerate_dev.h"
 
 struct EnumArgs {
     const u64* eff;
@@ -33,33 +28,6 @@ struct EnumArgs {
     const unsigned char* flips[2];
     u64* counts;                               // [(weight + 1)][(weight + 1)][5]
 };
-
-// C(s, K) for s < L, exact: c_i = C(s - K + i, i) -> c_{i+1} = c_i (s - K + 1 + i) / (i + 1), the division split so that no
-// intermediate exceeds the result (below C(L, w) < 2^63).  The divisors are constants after unrolling.
-template <int K>
-__device__ __forceinline__ u64 enum_binom(u64 s) {
-    if (s < (u64)K) return 0;
-    u64 c = 1;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        const u64 m = s - K + 1 + i, d = i + 1;
-        c = (c / d) * m + ((c % d) * m) / d;
-    }
-    return c;
-}
-
-// Pick K - 1 of the subset of rank r: the largest s in [K - 1, hi) with C(s, K) <= r.  hi and r are updated for the pick below.
-template <int K>
-__device__ __forceinline__ unsigned int enum_unrank_pick(u64& r, unsigned int& hi) {
-    unsigned int lo = K - 1;
-    while (hi - lo > 1) {
-        const unsigned int mid = lo + ((hi - lo) >> 1);
-        if (enum_binom<K>(mid) <= r) lo = mid; else hi = mid;
-    }
-    r -= enum_binom<K>(lo);
-    hi = lo;
-    return lo;
-}
 
 template <int LDR, bool STAGED>
 __global__ __launch_bounds__(CIRC_THREADS) void enumerate_kernel(EnumArgs a) {
@@ -79,61 +47,18 @@ __global__ __launch_bounds__(CIRC_THREADS) void enumerate_kernel(EnumArgs a) {
         const int64_t run = base + threadIdx.x;
         const int64_t first = run * a.run;                                             // of this lane, within the launch
         unsigned int pos[ENUM_MAX_W];
-        {
-            // a lane without a run unranks rank 0: picks 0 .. w - 1, all below L
-            u64 r = first < a.count ? a.first_rank + (u64)first : 0ull;
-            unsigned int hi = (unsigned int)a.locations;
-            pos[7] = w > 7 ? enum_unrank_pick<8>(r, hi) : 0u;
-            pos[6] = w > 6 ? enum_unrank_pick<7>(r, hi) : 0u;
-            pos[5] = w > 5 ? enum_unrank_pick<6>(r, hi) : 0u;
-            pos[4] = w > 4 ? enum_unrank_pick<5>(r, hi) : 0u;
-            pos[3] = w > 3 ? enum_unrank_pick<4>(r, hi) : 0u;
-            pos[2] = w > 2 ? enum_unrank_pick<3>(r, hi) : 0u;
-            pos[1] = w > 1 ? enum_unrank_pick<2>(r, hi) : 0u;
-            pos[0] = w > 0 ? enum_unrank_pick<1>(r, hi) : 0u;
-        }
+        // a lane without a run unranks rank 0: picks 0 .. w - 1, all below L
+        enum_unrank(w, first < a.count ? a.first_rank + (u64)first : 0ull, (unsigned int)a.locations, pos);
         for (int step = 0; step < a.run; ++step) {
             const bool live = first + step < a.count;
-            if (step > 0 && live) {
-                // successor: the lowest pick that can move up does, the picks below it fall back to 0, 1, ...  (a live subset is
-                // not the last of all, so the pick that moves stays below L)
-                bool done = false;
-#pragma unroll
-                for (int j = 0; j < ENUM_MAX_W; ++j) {
-                    if (j < w && !done) {
-                        const bool can = j == w - 1 || pos[j] + 1 < pos[j + 1 < ENUM_MAX_W ? j + 1 : j];
-                        pos[j] = can ? pos[j] + 1 : (unsigned int)j;
-                        done = can;
-                    }
-                }
-            }
-            // all X
+            if (step > 0 && live) enum_successor(w, pos);
             u64 out[LDR];
-#pragma unroll
-            for (int q = 0; q < LDR; ++q) out[q] = 0;
-#pragma unroll
-            for (int k = 0; k < ENUM_MAX_W; ++k) {
-                if (k < w) {
-                    const u64* e = eff + (size_t)(2 * pos[k]) * LDR;
-#pragma unroll
-                    for (int q = 0; q < LDR; ++q) out[q] ^= e[q];
-                }
-            }
+            enum_all_x<LDR>(w, eff, pos, out);                                         // all X
             int n_x = w, n_y = 0;
             for (unsigned int t = 0; t < a.pow3; ++t) {
                 if (t > 0) {
-                    // digit j of the Gray code moves: a = digit j of t (not 0), reflected when the digits above it make an odd number
-                    unsigned int q3 = t;
-                    int j = 0;
-                    while (q3 % 3u == 0u) q3 /= 3u, ++j;
-                    const unsigned int digit = q3 % 3u, above = q3 / 3u;
-                    const unsigned int now = (above & 1u) ? 2u - digit : digit, was = (above & 1u) ? 3u - digit : digit - 1u;
-                    const bool xy = (now < was ? now : was) == 0u;                    // X <-> Y: the Z effect; Y <-> Z: the X effect
-                    n_x += (was == 0u) ? -1 : (now == 0u) ? 1 : 0;
-                    n_y += (now == 1u) ? 1 : -1;
-                    unsigned int p = pos[0];                                          // (selects on the scalar j: no scratch)
-#pragma unroll
-                    for (int k = 1; k < ENUM_MAX_W; ++k) p = j == k ? pos[k] : p;
+                    bool xy;
+                    const unsigned int p = enum_gray_step(t, pos, xy, n_x, n_y);
                     const u64* e = eff + (size_t)(2 * p + (xy ? 1u : 0u)) * LDR;
 #pragma unroll
                     for (int q = 0; q < LDR; ++q) out[q] ^= e[q];

@@ -381,6 +381,155 @@ struct HostTable {                                                          // s
         return it != entries.end() && it->hi == hi && it->lo == lo ? (it->flip & 1) : -1;
     }
 };
+
+// One sample of the error-correction cycle's tally rule (DESIGN.md "Error-correction cycle"): the class byte (0: rejected), the
+// sample's eight fields added to counts.  gf2_ec_tally_host and gf2_ec_enumerate_host judge with it.
+uint8_t ec_tally_sample(const uint64_t* w, int64_t ldr, int64_t rounds, const uint64_t* mask, const HostTable* tab, uint64_t* counts) {
+    uint64_t flags = 0;
+    for (int64_t q = rounds + 1; q < ldr; ++q) flags |= w[q];
+    if (flags) return 0;
+    bool flip[2], miss[2];
+    uint64_t unmatched[2] = {0, 0};
+    for (int c = 0; c < 2; ++c) {
+        uint64_t K = 0, P = 0;
+        for (int64_t t = 1; t <= rounds; ++t) {
+            const uint64_t s = ((w[t] >> (32 * c)) & mask[c]) ^ K;
+            const int found = tab[c].find(0, s);
+            if (found < 0)
+                unmatched[c] += 1;                                       // css_code.py:655-657: no match, nothing recorded
+            else
+                K ^= s, P ^= (uint64_t)found;
+        }
+        const uint64_t s = ((w[0] >> (32 * c)) & mask[c]) ^ K;
+        const int found = tab[c].find(0, s);
+        miss[c] = found < 0;
+        flip[c] = (((w[0] >> (32 * c + 31)) & 1ull) ^ P ^ (uint64_t)(found > 0)) != 0;
+    }
+    counts[0] += 1;
+    counts[1] += flip[0];
+    counts[2] += flip[1];
+    counts[3] += flip[0] | flip[1];
+    counts[4] += miss[0];
+    counts[5] += miss[1];
+    counts[6] += unmatched[0];
+    counts[7] += unmatched[1];
+    return (uint8_t)(1 | flip[0] << 1 | flip[1] << 2 | miss[0] << 3 | miss[1] << 4);
+}
+
+// One sample of the logical measurement's tally rule (DESIGN.md "Logical measurement"), likewise: gf2_ft_tally_host and
+// gf2_ft_enumerate_host judge with it.
+uint8_t ft_tally_sample(const uint64_t* w, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int trials, const uint64_t* mask,
+                        const HostTable* tab, uint64_t* counts) {
+    uint64_t flags = 0;
+    for (int64_t q = nsteps; q < ldr; ++q) flags |= w[q];
+    if (flags) return 0;
+    uint64_t K[2] = {0, 0}, P[2] = {0, 0}, unmatched[2] = {0, 0};
+    int wrong_trials = 0, seen_trials = 0;
+    bool first_wrong = false;
+    for (int64_t s = 0; s < nsteps; ++s) {
+        const bool measure = (measure_mask >> s) & 1ull;
+        for (int c = 0; c < (measure ? 1 : 2); ++c) {
+            const uint64_t v = ((w[s] >> (32 * c)) & mask[c]) ^ K[c];
+            const int found = tab[c].find(0, v);
+            if (found < 0)
+                unmatched[c] += 1;                                       // css_code.py:655-657: no match, nothing recorded
+            else
+                K[c] ^= v, P[c] ^= (uint64_t)found;
+        }
+        if (measure) {
+            const bool bad = (((w[s] >> 31) & 1ull) ^ P[0]) != 0;
+            if (seen_trials == 0) first_wrong = bad;
+            wrong_trials += bad;
+            seen_trials += 1;
+        }
+    }
+    const bool wrong = 2 * wrong_trials > trials, split = wrong_trials != 0 && wrong_trials != trials;
+    counts[0] += 1;
+    counts[1] += wrong;
+    counts[2] += (uint64_t)wrong_trials;
+    counts[3] += first_wrong;
+    counts[4] += split;
+    counts[5] += unmatched[0];
+    counts[6] += unmatched[1];
+    return (uint8_t)(1 | wrong << 1 | first_wrong << 2 | split << 3 | (unmatched[0] != 0) << 4 | (unmatched[1] != 0) << 5);
+}
+
+// The walk of an enumerated rank range (DESIGN.md "Exact strata"), serial: every subset of ranks [first_rank, first_rank + count)
+// (the first unranked, the others by the colexicographic successor), every kind assignment by an odometer over {1, 2, 3}^w, the
+// outcome words XOR-ed from scratch and handed to judge(out, bin) with the bin [n_x][n_y] of `fields` counts.
+template <class Judge>
+void gadget_enumerate_walk(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t w, int64_t first_rank, int64_t count, int fields,
+                           uint64_t* counts_out, Judge judge) {
+    const int64_t side = w + 1;
+    int32_t pos[GF2_ENUMERATE_MAX_WEIGHT] = {0};
+    int kind[GF2_ENUMERATE_MAX_WEIGHT];
+    subset_unrank(locations, (int)w, (uint64_t)first_rank, pos);
+    for (int64_t i = 0; i < count; ++i) {
+        if (i > 0) {                                                        // successor: the lowest pick that can move up does
+            int64_t j = 0;
+            while (j < w - 1 && pos[j] + 1 == pos[j + 1]) pos[j] = (int32_t)j, ++j;
+            pos[j] += 1;
+        }
+        for (int64_t k = 0; k < w; ++k) kind[k] = 1;
+        for (;;) {
+            uint64_t out[GF2_FT_MAX_LDR] = {0};
+            int64_t n_x = 0, n_y = 0;
+            for (int64_t k = 0; k < w; ++k) {
+                const uint64_t* e = eff + (size_t)(2 * pos[k]) * ldr;
+                for (int64_t q = 0; q < ldr; ++q) out[q] ^= (kind[k] & 1 ? e[q] : 0ull) ^ (kind[k] & 2 ? e[ldr + q] : 0ull);
+                n_x += kind[k] == 1;
+                n_y += kind[k] == 3;
+            }
+            judge(out, counts_out + (n_x * side + n_y) * fields);
+            int64_t k = 0;                                                   // odometer over 1, 2, 3
+            while (k < w && kind[k] == 3) kind[k++] = 1;
+            if (k == w) break;
+            kind[k] += 1;
+        }
+    }
+}
+
+// The argument rules gf2_ec_tally_host and gf2_ec_enumerate_host share ...
+int ec_check_layout(const char* who, int64_t ldr, int64_t rounds, int64_t r1, int64_t r2) {
+    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
+    if (rounds < 1 || rounds > GF2_EC_MAX_ROUNDS) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= rounds <= %d, got %lld", who, GF2_EC_MAX_ROUNDS, (long long)rounds);
+    if (ldr > GF2_CIRCUIT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per sample, got %lld", who, GF2_CIRCUIT_MAX_LDR, (long long)ldr);
+    if (ldr < rounds + 2)
+        GF2_FAIL(GF2_E_ARG, "%s: %lld rounds need ldr = 1 + rounds + F words with F >= 1 flag words, got %lld", who, (long long)rounds, (long long)ldr);
+    return GF2_OK;
+}
+
+// ... and those of gf2_ft_tally_host and gf2_ft_enumerate_host.
+int ft_check_layout(const char* who, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1, int64_t r2) {
+    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
+    if (ldr > GF2_FT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per sample, got %lld", who, GF2_FT_MAX_LDR, (long long)ldr);
+    if (nsteps < 1 || ldr < nsteps + 1)
+        GF2_FAIL(GF2_E_ARG, "%s: needs nsteps >= 1 and ldr = nsteps + F words with F >= 1 flag words, got nsteps = %lld and ldr = %lld", who,
+                 (long long)nsteps, (long long)ldr);
+    if (measure_mask >> nsteps) GF2_FAIL(GF2_E_ARG, "%s: measure_mask has bits at or above nsteps = %lld", who, (long long)nsteps);
+    const int trials = __builtin_popcountll(measure_mask);
+    if (trials % 2 == 0) GF2_FAIL(GF2_E_ARG, "%s: a majority vote needs an odd number of trials, measure_mask has %d", who, trials);
+    return GF2_OK;
+}
+
+int check_table_args(const char* who, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, const uint64_t* keys2,
+                     const uint8_t* flips2, int64_t entries2) {
+    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !flips1)) || (entries2 && (!keys2 || !flips2)))
+        GF2_FAIL(GF2_E_ARG, "%s: bad table (a null array with entries > 0, or a negative count)", who);
+    return GF2_OK;
+}
+
+// [0]: x side, parity_check_c2's table; [1]: z side, c1's (keys of one word)
+int make_host_tables(const char* who, HostTable* tab, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, const uint64_t* keys2,
+                     const uint8_t* flips2, int64_t entries2) {
+    try {
+        if (!tab[0].make(keys2, flips2, entries2, 1) || !tab[1].make(keys1, flips1, entries1, 1))
+            GF2_FAIL(GF2_E_ARG, "%s: a syndrome key occurs twice in a table", who);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    return GF2_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -478,58 +627,17 @@ int gf2_ec_tally_host(const uint64_t* words, int64_t count, int64_t ldw, int64_t
                       uint64_t* counts_out, uint8_t* class_out) {
     const char* who = "gf2_ec_tally_host";
     if (!counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (rounds < 1 || rounds > GF2_EC_MAX_ROUNDS) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= rounds <= %d, got %lld", who, GF2_EC_MAX_ROUNDS, (long long)rounds);
-    if (ldr > GF2_CIRCUIT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per sample, got %lld", who, GF2_CIRCUIT_MAX_LDR, (long long)ldr);
-    if (ldr < rounds + 2)
-        GF2_FAIL(GF2_E_ARG, "%s: %lld rounds need ldr = 1 + rounds + F words with F >= 1 flag words, got %lld", who, (long long)rounds, (long long)ldr);
+    if (int rc = ec_check_layout(who, ldr, rounds, r1, r2)) return rc;
     if (count < 0 || ldw < ldr || (count > 0 && !words)) GF2_FAIL(GF2_E_ARG, "%s: needs count >= 0 samples of ldw >= ldr words", who);
-    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !flips1)) || (entries2 && (!keys2 || !flips2)))
-        GF2_FAIL(GF2_E_ARG, "%s: bad table (a null array with entries > 0, or a negative count)", who);
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
     for (int k = 0; k < GF2_EC_FIELDS; ++k) counts_out[k] = 0;
     if (count == 0) return GF2_OK;
-    HostTable tab[2];                                                        // [0]: x side, parity_check_c2's table; [1]: z side, c1's
-    try {
-        if (!tab[0].make(keys2, flips2, entries2, 1) || !tab[1].make(keys1, flips1, entries1, 1))
-            GF2_FAIL(GF2_E_ARG, "%s: a syndrome key occurs twice in a table", who);
-    } catch (const std::bad_alloc&) {
-        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
-    }
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
     const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
     for (int64_t i = 0; i < count; ++i) {
-        const uint64_t* w = words + i * ldw;
-        uint64_t flags = 0;
-        for (int64_t q = rounds + 1; q < ldr; ++q) flags |= w[q];
-        if (flags) {
-            if (class_out) class_out[i] = 0;
-            continue;
-        }
-        bool flip[2], miss[2];
-        uint64_t unmatched[2] = {0, 0};
-        for (int c = 0; c < 2; ++c) {
-            uint64_t K = 0, P = 0;
-            for (int64_t t = 1; t <= rounds; ++t) {
-                const uint64_t s = ((w[t] >> (32 * c)) & mask[c]) ^ K;
-                const int found = tab[c].find(0, s);
-                if (found < 0)
-                    unmatched[c] += 1;                                       // css_code.py:655-657: no match, nothing recorded
-                else
-                    K ^= s, P ^= (uint64_t)found;
-            }
-            const uint64_t s = ((w[0] >> (32 * c)) & mask[c]) ^ K;
-            const int found = tab[c].find(0, s);
-            miss[c] = found < 0;
-            flip[c] = (((w[0] >> (32 * c + 31)) & 1ull) ^ P ^ (uint64_t)(found > 0)) != 0;
-        }
-        counts_out[0] += 1;
-        counts_out[1] += flip[0];
-        counts_out[2] += flip[1];
-        counts_out[3] += flip[0] | flip[1];
-        counts_out[4] += miss[0];
-        counts_out[5] += miss[1];
-        counts_out[6] += unmatched[0];
-        counts_out[7] += unmatched[1];
-        if (class_out) class_out[i] = (uint8_t)(1 | flip[0] << 1 | flip[1] << 2 | miss[0] << 3 | miss[1] << 4);
+        const uint8_t cls = ec_tally_sample(words + i * ldw, ldr, rounds, mask, tab, counts_out);
+        if (class_out) class_out[i] = cls;
     }
     return GF2_OK;
 }
@@ -543,66 +651,77 @@ int gf2_ft_tally_host(const uint64_t* words, int64_t count, int64_t ldw, int64_t
                       const uint8_t* flips2, int64_t entries2, uint64_t* counts_out, uint8_t* class_out) {
     const char* who = "gf2_ft_tally_host";
     if (!counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (ldr > GF2_FT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per sample, got %lld", who, GF2_FT_MAX_LDR, (long long)ldr);
-    if (nsteps < 1 || ldr < nsteps + 1)
-        GF2_FAIL(GF2_E_ARG, "%s: needs nsteps >= 1 and ldr = nsteps + F words with F >= 1 flag words, got nsteps = %lld and ldr = %lld", who,
-                 (long long)nsteps, (long long)ldr);
-    if (measure_mask >> nsteps) GF2_FAIL(GF2_E_ARG, "%s: measure_mask has bits at or above nsteps = %lld", who, (long long)nsteps);
+    if (int rc = ft_check_layout(who, ldr, nsteps, measure_mask, r1, r2)) return rc;
     const int trials = __builtin_popcountll(measure_mask);
-    if (trials % 2 == 0) GF2_FAIL(GF2_E_ARG, "%s: a majority vote needs an odd number of trials, measure_mask has %d", who, trials);
     if (count < 0 || ldw < ldr || (count > 0 && !words)) GF2_FAIL(GF2_E_ARG, "%s: needs count >= 0 samples of ldw >= ldr words", who);
-    if (entries1 < 0 || entries2 < 0 || (entries1 && (!keys1 || !flips1)) || (entries2 && (!keys2 || !flips2)))
-        GF2_FAIL(GF2_E_ARG, "%s: bad table (a null array with entries > 0, or a negative count)", who);
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
     for (int k = 0; k < GF2_FT_FIELDS; ++k) counts_out[k] = 0;
     if (count == 0) return GF2_OK;
-    HostTable tab[2];                                                        // [0]: x side, parity_check_c2's table; [1]: z side, c1's
-    try {
-        if (!tab[0].make(keys2, flips2, entries2, 1) || !tab[1].make(keys1, flips1, entries1, 1))
-            GF2_FAIL(GF2_E_ARG, "%s: a syndrome key occurs twice in a table", who);
-    } catch (const std::bad_alloc&) {
-        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
-    }
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
     const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
     for (int64_t i = 0; i < count; ++i) {
-        const uint64_t* w = words + i * ldw;
-        uint64_t flags = 0;
-        for (int64_t q = nsteps; q < ldr; ++q) flags |= w[q];
-        if (flags) {
-            if (class_out) class_out[i] = 0;
-            continue;
-        }
-        uint64_t K[2] = {0, 0}, P[2] = {0, 0}, unmatched[2] = {0, 0};
-        int wrong_trials = 0, seen_trials = 0;
-        bool first_wrong = false;
-        for (int64_t s = 0; s < nsteps; ++s) {
-            const bool measure = (measure_mask >> s) & 1ull;
-            for (int c = 0; c < (measure ? 1 : 2); ++c) {
-                const uint64_t v = ((w[s] >> (32 * c)) & mask[c]) ^ K[c];
-                const int found = tab[c].find(0, v);
-                if (found < 0)
-                    unmatched[c] += 1;                                       // css_code.py:655-657: no match, nothing recorded
-                else
-                    K[c] ^= v, P[c] ^= (uint64_t)found;
-            }
-            if (measure) {
-                const bool bad = (((w[s] >> 31) & 1ull) ^ P[0]) != 0;
-                if (seen_trials == 0) first_wrong = bad;
-                wrong_trials += bad;
-                seen_trials += 1;
-            }
-        }
-        const bool wrong = 2 * wrong_trials > trials, split = wrong_trials != 0 && wrong_trials != trials;
-        counts_out[0] += 1;
-        counts_out[1] += wrong;
-        counts_out[2] += (uint64_t)wrong_trials;
-        counts_out[3] += first_wrong;
-        counts_out[4] += split;
-        counts_out[5] += unmatched[0];
-        counts_out[6] += unmatched[1];
-        if (class_out)
-            class_out[i] = (uint8_t)(1 | wrong << 1 | first_wrong << 2 | split << 3 | (unmatched[0] != 0) << 4 | (unmatched[1] != 0) << 5);
+        const uint8_t cls = ft_tally_sample(words + i * ldw, ldr, nsteps, measure_mask, trials, mask, tab, counts_out);
+        if (class_out) class_out[i] = cls;
     }
+    return GF2_OK;
+}
+
+// The definition of gf2_ec_enumerate (DESIGN.md "Exact strata of the cycle"), serial: gf2_circuit_enumerate_host's walk, every
+// configuration's outcome words judged by gf2_ec_tally_host's per-sample rule.
+int gf2_ec_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                          const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                          int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out) {
+    const char* who = "gf2_ec_enumerate_host";
+    if (!eff || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
+    if (int rc = ec_check_layout(who, ldr, rounds, r1, r2)) return rc;
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    const uint64_t keys = mask[0] | mask[1] << 32;
+    uint64_t any[GF2_CIRCUIT_MAX_LDR] = {0};
+    for (int64_t i = 0; i < 2 * locations; ++i)
+        for (int64_t q = 0; q < ldr; ++q) any[q] |= eff[i * ldr + q];
+    bool beyond = (any[0] & ~(keys | 1ull << 31 | 1ull << 63)) != 0;
+    for (int64_t t = 1; t <= rounds; ++t) beyond |= (any[t] & ~keys) != 0;
+    if (beyond) GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits, the two parity bits and the flag words", who);
+    for (int64_t k = 0; k < (w + 1) * (w + 1) * GF2_EC_FIELDS; ++k) counts_out[k] = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    gadget_enumerate_walk(eff, locations, ldr, w, first_rank, count, GF2_EC_FIELDS, counts_out,
+                          [&](const uint64_t* out, uint64_t* bin) { (void)ec_tally_sample(out, ldr, rounds, mask, tab, bin); });
+    return GF2_OK;
+}
+
+// The definition of gf2_ft_enumerate (DESIGN.md "Exact strata of the measurement"), likewise with gf2_ft_tally_host's rule.
+int gf2_ft_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                          const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                          const uint8_t* flips2, int64_t entries2, int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out) {
+    const char* who = "gf2_ft_enumerate_host";
+    if (!eff || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
+    if (int rc = ft_check_layout(who, ldr, nsteps, measure_mask, r1, r2)) return rc;
+    const int trials = __builtin_popcountll(measure_mask);
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    uint64_t any[GF2_FT_MAX_LDR] = {0};
+    for (int64_t i = 0; i < 2 * locations; ++i)
+        for (int64_t q = 0; q < ldr; ++q) any[q] |= eff[i * ldr + q];
+    bool beyond = false;
+    for (int64_t s = 0; s < nsteps; ++s)
+        beyond |= (any[s] & ~((measure_mask >> s) & 1ull ? mask[0] | 1ull << 31 : mask[0] | mask[1] << 32)) != 0;
+    if (beyond)
+        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key bits and bit 31)", who);
+    for (int64_t k = 0; k < (w + 1) * (w + 1) * GF2_FT_FIELDS; ++k) counts_out[k] = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    gadget_enumerate_walk(eff, locations, ldr, w, first_rank, count, GF2_FT_FIELDS, counts_out, [&](const uint64_t* out, uint64_t* bin) {
+        (void)ft_tally_sample(out, ldr, nsteps, measure_mask, trials, mask, tab, bin);
+    });
     return GF2_OK;
 }
 

@@ -387,6 +387,12 @@ class CSSCode(QECC):
         return ec_noise.circuit_for(self, rounds, idle_data).logical_error_rates(num_samples, p_x, p_y, p_z, seed=seed,
                                                                                  first_sample=first_sample)
 
+    def error_correct_strata_exact(self, weights, rounds=1, idle_data=False, **options):
+        """The exact strata `weights` of the cycle (ec_noise.ECCircuit.enumerate_strata; DESIGN.md "Exact strata of the cycle"): a
+        montecarlo.PostSelectedStrata, whose series() gives the Taylor coefficients of the logical error rate per cycle."""
+        from . import ec_noise
+        return ec_noise.circuit_for(self, rounds, idle_data).enumerate_strata(weights, **options)
+
     def error_correct_single_faults(self, rounds=1):
         """[build-defined]  The census of every single fault of the cycle, no GPU needed: ECCircuit.single_faults."""
         from . import ec_noise
@@ -400,6 +406,13 @@ class CSSCode(QECC):
         side of the comparison."""
         from . import ft_noise
         return ft_noise.program_for(self, ops).measurement_error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample)
+
+    def logical_program_strata_exact(self, ops, weights, **options):
+        """The exact strata `weights` of the rewritten program `ops; MEASURE` (ft_noise.FTProgram.enumerate_strata; DESIGN.md "Exact
+        strata of the measurement"): a montecarlo.PostSelectedStrata, whose series((k_x, k_y, k_z), 'wrong') gives the Taylor
+        coefficients of the probability that the measured bit is wrong."""
+        from . import ft_noise
+        return ft_noise.program_for(self, ops).enumerate_strata(weights, **options)
 
     def logical_program_single_faults(self, ops):
         """[build-defined]  The census of every single fault of the rewritten program, no GPU needed: FTProgram.single_faults."""

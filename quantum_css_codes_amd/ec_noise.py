@@ -225,6 +225,24 @@ class ECCircuit(object):
         out['samples'] = len(words)
         return (out, got[1]) if classes else out
 
+    def enumerate_strata(self, weights, first_rank=None, count=None, max_configurations=None, host=False):
+        """Exact strata of the cycle (DESIGN.md "Exact strata of the cycle"): every configuration of exactly weights[s] <= 8 faults
+        -- each subset of the L locations with every assignment of X, Y, Z to its picks -- judged by logical_error_rates' tally
+        rule, post-selection included, and counted per kind composition.  Arguments as FaultCircuit.enumerate_strata's: ranks
+        [first_rank, first_rank + count) per weight (default: everything), more than `max_configurations` (default
+        circuit_noise.ENUMERATE_BUDGET) configurations in all is a ValueError, host=True runs the serial host statement
+        (gf2_ec_enumerate_host) and needs no GPU.  Returns a montecarlo.PostSelectedStrata over nb = L."""
+        from . import montecarlo
+        weights, firsts, counts = circuit_noise.gadget_enumerate_request(self.num_locations, weights, first_rank, count, max_configurations,
+                                                                         "cycle")
+        if host:
+            run = lambda w, f, n: _native.ec_enumerate_host(self.effects, self.rounds, *self._tables(), w, f, n)
+        else:
+            ctx, circ = _native.default_context(), self.device()
+            run = lambda w, f, n: ctx.ec_enumerate(circ, self.rounds, *self._tables(), w, f, n)
+        return montecarlo.PostSelectedStrata(self.num_locations, weights, [run(w, f, n) for w, f, n in zip(weights, firsts, counts)],
+                                             EC_FIELDS)
+
     def single_faults(self):
         """The census of all 3 L single faults, no GPU: (classes, flipping) -- classes (L, 3) uint8, the class byte (CLASS_* bits)
         of an X, Y, Z fault (the columns, KINDS) at every location; flipping, the accepted faults with a logical flip as

@@ -190,6 +190,22 @@ class FTProgram(object):
         out = self._dict(got[0] if classes else got, len(words))
         return (out, got[1]) if classes else out
 
+    def enumerate_strata(self, weights, first_rank=None, count=None, max_configurations=None, host=False):
+        """Exact strata of the measurement (DESIGN.md "Exact strata of the measurement"): every configuration of exactly
+        weights[s] <= 8 faults of the rewritten program judged by measurement_error_rates' tally rule, post-selection included, and
+        counted per kind composition.  Arguments as FaultCircuit.enumerate_strata's (ECCircuit.enumerate_strata has them in
+        full); host=True runs gf2_ft_enumerate_host and needs no GPU.  Returns a montecarlo.PostSelectedStrata over nb = L."""
+        from . import montecarlo
+        weights, firsts, counts = circuit_noise.gadget_enumerate_request(self.num_locations, weights, first_rank, count, max_configurations,
+                                                                         "program")
+        if host:
+            run = lambda w, f, n: _native.ft_enumerate_host(self.effects, self.nsteps, self.measure_mask, *self._tables(), w, f, n)
+        else:
+            ctx, circ = _native.default_context(), self.device()
+            run = lambda w, f, n: ctx.ft_enumerate(circ, self.nsteps, self.measure_mask, *self._tables(), w, f, n)
+        return montecarlo.PostSelectedStrata(self.num_locations, weights, [run(w, f, n) for w, f, n in zip(weights, firsts, counts)],
+                                             FT_FIELDS)
+
     def single_faults(self):
         """The census of all 3 L single faults, no GPU: (classes, wrong) -- classes (L, 3) uint8, the class byte (CLASS_* bits) of
         an X, Y, Z fault (the columns, KINDS) at every location; wrong, the accepted faults that make the measured bit wrong, as

@@ -466,10 +466,129 @@ class MergedStrata(object):
         return rows[:, 0], rows[:, 1], rows[:, 2]
 
 
+class PostSelectedStrata(object):
+    """Exact strata of a post-selected gadget (ec_noise.ECCircuit / ft_noise.FTProgram.enumerate_strata): `weights` (distinct) over
+    `nb` positions and, per weight w, the (w + 1, w + 1, F) uint64 counts [n_x][n_y][field] over ALL C(nb, w) subsets, `fields`
+    naming the F columns.  Field 0 is 'accepted'; every other field counts among accepted configurations.  With kind weights
+    (k_x, k_y, k_z) of sum s,  A_w(field) = sum counts[n_x][n_y][field] k_x^n_x k_y^n_y k_z^n_z / s^w,  and at total fault
+    probability p per position  P(accepted and field) = sum_w A_w p^w (1 - p)^(nb - w).  The fields whose value per configuration
+    is 0 or 1 are indicators; the others (`SUM_FIELDS`) are sums, for which a rate has no bounds but a series is the series of the
+    conditional expectation."""
+
+    SUM_FIELDS = ('trial_wrong', 'unmatched_x', 'unmatched_z', 'round_unmatched_x', 'round_unmatched_z')
+
+    def __init__(self, nb, weights, counts, fields):
+        self.nb = int(nb)
+        self.fields = tuple(fields)
+        if not self.fields or self.fields[0] != 'accepted':
+            raise ValueError("the first field of a post-selected tally is 'accepted'")
+        self.weights = [int(w) for w in np.asarray(weights).reshape(-1)]
+        if len(set(self.weights)) != len(self.weights):
+            raise ValueError("the weights of the strata must be distinct")
+        if any(w < 0 or w > self.nb for w in self.weights):
+            raise ValueError("a stratum's weight lies in [0, nb]")
+        counts = list(counts)
+        if len(counts) != len(self.weights):
+            raise ValueError("one array of counts per weight")
+        self.counts = [np.asarray(c, dtype=np.uint64).reshape(w + 1, w + 1, len(self.fields)).copy() for w, c in zip(self.weights, counts)]
+
+    def configurations(self):
+        """3^w C(nb, w) per weight."""
+        return [3**w * math.comb(self.nb, w) for w in self.weights]
+
+    def _column(self, field):
+        if field not in self.fields:
+            raise ValueError("no field %r (the fields are %s)" % (field, ', '.join(self.fields)))
+        return self.fields.index(field)
+
+    def coefficients(self, kinds=(1, 1, 1), field='accepted'):
+        """A_w(field) per enumerated weight: exact fractions.Fraction when the kinds are integers or Fractions, floats otherwise."""
+        kinds = _kind_ratio(kinds)
+        exact = all(isinstance(k, numbers.Rational) for k in kinds)
+        k_x, k_y, k_z = (_fractions.Fraction(k) for k in kinds) if exact else (float(k) for k in kinds)
+        col, s, out = self._column(field), k_x + k_y + k_z, []
+        for w, counts in zip(self.weights, self.counts):
+            total = _fractions.Fraction(0) if exact else 0.0
+            for n_x in range(w + 1):
+                for n_y in range(w + 1 - n_x):
+                    c = int(counts[n_x, n_y, col])
+                    if c:
+                        total += c * k_x**n_x * k_y**n_y * k_z**(w - n_x - n_y)
+            out.append(total / s**w)
+        return out
+
+    def joint(self, p_t, kinds=(1, 1, 1), field='accepted'):
+        """P(accepted and field) at total fault probability p_t per position, over the enumerated weights: sum_w A_w p^w
+        (1 - p)^(nb - w) = sum_w (A_w / C(nb, w)) B_w with binomial_weights' B_w (log space: accurate at p_t = 1e-12 and below).
+        For a sum field, the expectation of the field over accepted configurations times P(accepted)."""
+        b_all = binomial_weights(self.nb, p_t)
+        return math.fsum(float(a_w / math.comb(self.nb, w)) * b_all[w] for w, a_w in zip(self.weights, self.coefficients(kinds, field)))
+
+    def _missing_mass(self, p_t):
+        b_all = binomial_weights(self.nb, p_t)
+        have = np.zeros(self.nb + 1, dtype=bool)
+        have[self.weights] = True
+        return math.fsum(b_all[~have])
+
+    def rate(self, p_t, kinds=(1, 1, 1), field='wrong'):
+        """The conditional rate P(field | accepted) of an indicator field as (estimate, lower, upper): with N = joint(field),
+        D = joint('accepted') and T the binomial mass of the weights not enumerated, estimate = N / D, lower = N / (D + T), upper =
+        (N + T) / (D + T).  The bounds are rigorous: the missing weights add n to N and d to D with 0 <= n <= d <= T."""
+        if field in self.SUM_FIELDS:
+            raise ValueError("rate() is defined for indicator fields; %r is a sum (series() gives its conditional expectation)" % (field,))
+        n, d, t = self.joint(p_t, kinds, field), self.joint(p_t, kinds, 'accepted'), self._missing_mass(p_t)
+        if not d > 0:
+            raise ValueError("no accepted configuration among the enumerated weights at p_t = %r" % (p_t,))
+        return n / d, n / (d + t), (n + t) / (d + t)
+
+    def acceptance(self, p_t, kinds=(1, 1, 1)):
+        """(D, D + T): bounds on the probability that an attempt is accepted; their reciprocals bound the expected number of
+        attempts of repeat-until-success."""
+        d = self.joint(p_t, kinds, 'accepted')
+        return d, d + self._missing_mass(p_t)
+
+    def series(self, kinds=(1, 1, 1), field='wrong', order=None):
+        """The Taylor coefficients [c_0, ..., c_m] in p_t of the conditional rate of `field` (for a sum field: of its conditional
+        expectation), exact for rational kinds.  m (or `order`, if smaller) is the largest order with every weight 0 .. m
+        enumerated.  (1 - p)^nb cancels in N / D, which leaves the quotient of sum A_w(field) x^w by sum A_w(accepted) x^w in
+        x = p / (1 - p) = p + p^2 + ..., re-expanded in p.  Needs A_0(accepted) = 1 (no fault: accepted), ValueError otherwise."""
+        have = set(self.weights)
+        m = -1
+        while m + 1 in have:
+            m += 1
+        if m < 0:
+            raise ValueError("a series needs the stratum of weight 0")
+        if order is not None:
+            if int(order) < 0 or int(order) > m:
+                raise ValueError("order %d outside [0, %d], the weights enumerated without a gap" % (int(order), m))
+            m = int(order)
+        at = {w: i for i, w in enumerate(self.weights)}
+        num_all, den_all = self.coefficients(kinds, field), self.coefficients(kinds, 'accepted')
+        num = [num_all[at[w]] for w in range(m + 1)]
+        den = [den_all[at[w]] for w in range(m + 1)]
+        if den[0] != 1:
+            raise ValueError("a series needs A_0(accepted) = 1, got %r" % (den[0],))
+        q = []                                                       # num / den as a power series in x
+        for k in range(m + 1):
+            q.append(num[k] - sum(q[i] * den[k - i] for i in range(k)))
+        # x^j = p^j (1 - p)^-j = sum_k C(k - 1, j - 1) p^k for j >= 1
+        out = [q[0]] + [sum(q[j] * math.comb(k - 1, j - 1) for j in range(1, k + 1)) for k in range(1, m + 1)]
+        return out
+
+    def leading_order(self, kinds=(1, 1, 1), field='wrong'):
+        """(m, c_m): the first non-zero coefficient of series(); None when every coefficient is zero."""
+        for k, c in enumerate(self.series(kinds, field)):
+            if c != 0:
+                return k, c
+        return None
+
+
 def enumerate_sharded(circuit, weights, group=None, local_fn=None):
     """The whole strata `weights` of a FaultCircuit over the ranks of a process group: every weight's rank range [0, C(L, w)) is cut
     by shard_range, this rank enumerates its part, and one all-reduce sums the counts.  `local_fn(circuit, weights, first_rank,
-    count)` replaces circuit.enumerate_strata (the CPU tests pass the host statement).  Returns an ExactStrata."""
+    count)` replaces circuit.enumerate_strata (the CPU tests pass the host statement).  Returns an ExactStrata -- or, for an
+    ec_noise.ECCircuit or an ft_noise.FTProgram, whose parts are PostSelectedStrata, a PostSelectedStrata: the field count and the
+    class of the result are those of the part."""
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -481,9 +600,13 @@ def enumerate_sharded(circuit, weights, group=None, local_fn=None):
     part = fn(circuit, weights, [start for start, _ in shards], [mine for _, mine in shards])
     total, = all_reduce_histograms([np.concatenate([c.reshape(-1) for c in part.counts]) if weights else np.zeros(0, dtype=np.uint64)],
                                    group=group)
+    post_selected = isinstance(part, PostSelectedStrata)
+    nfields = len(part.fields) if post_selected else len(DECODE_FIELDS)
     counts, at = [], 0
     for w in weights:
-        size = (w + 1) * (w + 1) * len(DECODE_FIELDS)
+        size = (w + 1) * (w + 1) * nfields
         counts.append(total[at:at + size])
         at += size
+    if post_selected:
+        return PostSelectedStrata(circuit.num_locations, weights, counts, part.fields)
     return ExactStrata(circuit.num_locations, weights, counts)
