@@ -541,6 +541,41 @@ int gf2_ft_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, u
                      const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
                      int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out);
 
+/* ---- sampled strata of the two post-selected gadgets ----------------------------------------------------
+ * [build-defined, DESIGN.md "Sampled strata of the cycle" and "Sampled strata of the measurement"]  The two notions above combined,
+ * neither changed: stratified sample i of weight w over the gadget's L locations is the pure function of (seed, i, w) of
+ * "weight-stratified Monte-Carlo" (one segment, Floyd's rule, kinds X : Y : Z = k_x : k_y : k_z), its outcome words are the XOR of
+ * its picks' effects, and the words are judged by the tally rule per sample of the error-correction cycle (gf2_ec_tally_host) or of
+ * the logical measurement (gf2_ft_tally_host), post-selection included.  With a_w = accepted / N_w and n_w = field / N_w of
+ * stratum w, P(accepted and field) = sum_w C(L, w) p^w (1 - p)^(L - w) n_w and the conditional rate is the ratio of two such sums.
+ *
+ * The definition on the host, serial, no GPU needed (it stands for running the gadget once per stratified sample:
+ * CSSCode.error_correct, css_code.py:436-470; ftqc.rewrite_program, ftqc.py:76-95, with CSSCode.measure, css_code.py:542-589): the
+ * outcome words of samples first_sample .. first_sample + count - 1 of stratum w.  eff: 2 * locations * ldr words as
+ * gf2_circuit_effects_timed writes them, 1 <= locations <= GF2_CIRCUIT_MAX_LOCATIONS, 1 <= ldr <= GF2_FT_MAX_LDR,
+ * 0 <= w <= min(L, GF2_CIRCUIT_STRATUM_MAX_WEIGHT); words_out is count x ldw (ldw >= ldr), words past ldr are left as they were.
+ * gf2_ec_tally_host / gf2_ft_tally_host applied to words_out complete the statement. */
+int gf2_stratum_outcomes_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t w, uint64_t seed, int64_t first_sample,
+                              int64_t count, double k_x, double k_y, double k_z, uint64_t* words_out, int64_t ldw);
+
+/* gf2_mc_ec_decode over strata (css_code.py:436-470 with its classical side :649-685, once per stratified sample): stratum s has
+ * exactly weights[s] faults among the circuit's L locations, 0 <= weights[s] <= min(L, GF2_CIRCUIT_STRATUM_MAX_WEIGHT), and samples
+ * first_sample .. first_sample + counts[s] - 1; counts_out is nstrata x GF2_EC_FIELDS words.  Circuit, layout and tables as
+ * gf2_mc_ec_decode requires them (ldr = 1 + rounds + F, 3 <= ldr <= GF2_CIRCUIT_MAX_LDR, no effect bit outside the layout); strata
+ * arguments as gf2_mc_circuit_decode_strata requires them (nstrata <= GF2_STRATA_MAX, non-negative counts and first_sample, the kind
+ * weights).  The hash tables are made once per call, the counts come back once. */
+int gf2_mc_ec_decode_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                            const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                            int64_t entries2, uint64_t seed, int64_t first_sample, int64_t nstrata, const int32_t* weights,
+                            const int64_t* counts, double k_x, double k_y, double k_z, uint64_t* counts_out);
+
+/* gf2_mc_ft_decode over strata (ftqc.py:76-95 and css_code.py:542-589, test_fidelity.py's trial loop with one trial per stratified
+ * sample), likewise: the circuit's ldr = nsteps + F with 8 <= ldr <= GF2_FT_MAX_LDR; counts_out is nstrata x GF2_FT_FIELDS words. */
+int gf2_mc_ft_decode_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                            const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                            const uint8_t* flips2, int64_t entries2, uint64_t seed, int64_t first_sample, int64_t nstrata,
+                            const int32_t* weights, const int64_t* counts, double k_x, double k_y, double k_z, uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

@@ -141,6 +141,12 @@ SIGNATURES = {
     "gf2_ft_enumerate_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
     "gf2_ec_enumerate": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
     "gf2_ft_enumerate": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
+    "gf2_stratum_outcomes_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p,
+                                  _c_i64],
+    "gf2_mc_ec_decode_strata": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, _p, _p,
+                                ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
+    "gf2_mc_ft_decode_strata": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, _p, _p,
+                                ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
     "gf2_comm_unique_id": [_p, ctypes.c_size_t],
     "gf2_comm_create": [_p, _p, ctypes.c_int, ctypes.c_int, _pp],
     "gf2_comm_create_all": [_pp, ctypes.c_int, _pp],
@@ -390,6 +396,22 @@ def stratum_errors(nb, w, count, kinds=(1, 1, 1), seed=0, first=0):
     k_x, k_y, k_z = (float(k) for k in kinds)
     check(lib().gf2_stratum_errors(int(nb), int(w), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, k_x, k_y, k_z, _ptr(ex), _ptr(ez), ld))
     return ex[:count], ez[:count]
+
+
+def stratum_outcomes_host(eff, w, count, kinds=(1, 1, 1), seed=0, first=0, ldw=None):
+    """gf2_stratum_outcomes_host (host code, no GPU): the (count, ldw) outcome words of samples [first, first + count) of the stratum
+    of weight w over the L locations of an effect table eff, (L, 2, ldr) as circuit_effects_timed returns it; ldw (default ldr) words
+    per sample, those past ldr zero here."""
+    eff = np.ascontiguousarray(eff, dtype="<u8")
+    if eff.ndim != 3 or eff.shape[1] != 2:
+        raise ValueError("eff must be (locations, 2, ldr)")
+    count = int(count)
+    ldw = eff.shape[2] if ldw is None else int(ldw)
+    out = np.zeros((max(1, count), max(1, ldw)), dtype="<u8")
+    k_x, k_y, k_z = (float(k) for k in kinds)
+    check(lib().gf2_stratum_outcomes_host(_ptr(eff), eff.shape[0], eff.shape[2], int(w), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count,
+                                          k_x, k_y, k_z, _ptr(out), ldw))
+    return out[:max(0, count)]
 
 
 def _strata_arrays(weights, counts):
@@ -885,6 +907,26 @@ class Context(object):
                                                  len(k1), r2, _ptr(k2) if len(k2) else None, _ptr(f2) if len(k2) else None, len(k2),
                                                  seed & 0xFFFFFFFFFFFFFFFF, first, len(weights), _ptr(weights), _ptr(counts),
                                                  k_x, k_y, k_z, _ptr(out)))
+        return out
+
+    def mc_ec_decode_strata(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x, k_y, k_z):
+        """gf2_mc_ec_decode_strata: mc_ec_decode's tables; weights and counts per stratum.  Returns the (nstrata, 8) counts."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        weights, counts, _ = _strata_arrays(weights, counts)
+        out = np.zeros((len(weights), EC_FIELDS_COUNT), dtype=np.uint64)
+        check(lib().gf2_mc_ec_decode_strata(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF,
+                                            first, len(weights), _ptr(weights), _ptr(counts), k_x, k_y, k_z, _ptr(out)))
+        return out
+
+    def mc_ft_decode_strata(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x,
+                            k_y, k_z):
+        """gf2_mc_ft_decode_strata: mc_ft_decode's tables; weights and counts per stratum.  Returns the (nstrata, 7) counts."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        weights, counts, _ = _strata_arrays(weights, counts)
+        out = np.zeros((len(weights), FT_FIELDS_COUNT), dtype=np.uint64)
+        check(lib().gf2_mc_ft_decode_strata(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1,
+                                            int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF, first, len(weights), _ptr(weights), _ptr(counts),
+                                            k_x, k_y, k_z, _ptr(out)))
         return out
 
     def circuit_enumerate(self, circ, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):

@@ -1,5 +1,6 @@
 // What gf2_circuit.hip (the fault Monte-Carlo), gf2_enumerate.hip (the exact strata), gf2_ec.hip (the error-correction cycle),
-// gf2_ft.hip (the fault-tolerant logical measurement) and gf2_gadget_enumerate.hip (the exact strata of those two) share: the circuit
+// gf2_ft.hip (the fault-tolerant logical measurement), gf2_gadget_enumerate.hip (the exact strata of those two) and
+// gf2_gadget_strata.hip (their sampled strata) share: the circuit
 // object, the Monte-Carlo layout of its outcome words, the device side of the tally's syndrome tables and the gather loop of a
 // Monte-Carlo sample.
 #pragma once

@@ -1,6 +1,6 @@
 // The tally rules of the two post-selected gadgets on one lane's outcome words, as __forceinline__ device functions: the chain of
-// ec_kernel (gf2_ec.hip) and the step walk of ft_kernel (gf2_ft.hip), which gadget_enumerate_kernel (gf2_gadget_enumerate.hip)
-// calls.  The two samplers keep their own text of the same rule: calling these functions from them moved their register counts
+// ec_kernel (gf2_ec.hip) and the step walk of ft_kernel (gf2_ft.hip), which gadget_enumerate_kernel (gf2_gadget_enumerate.hip) and
+// gadget_strata_kernel (gf2_gadget_strata.hip) call.  The two samplers keep their own text of the same rule: calling these functions from them moved their register counts
 // (DESIGN.md "Exact strata of the cycle", "Kernel"), and tests/test_gpu_gadget_enumerate.py holds the two texts together through
 // the host statement.  Both rules are fully unrolled over constant word indices under uniform guards, so out[] never takes a
 // run-time index (it would go to scratch).  Args: a kernel's argument block with mask[2], tab[2], flips[2] and rounds (the cycle)

@@ -317,6 +317,50 @@ int gf2_stratum_errors(int64_t nb, int64_t w, uint64_t seed, int64_t first_sampl
     return GF2_OK;
 }
 
+// The outcome words of a gadget's stratified samples (DESIGN.md "Sampled strata of the cycle"), the host statement of what
+// gadget_strata_kernel draws: the same draw as above over the L locations of an effect table, every pick's X / Z effect XOR-ed into
+// the sample's ldr words.  gf2_ec_tally_host / gf2_ft_tally_host judge the words; no tally rule is repeated here.
+int gf2_stratum_outcomes_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t w, uint64_t seed, int64_t first_sample,
+                              int64_t count, double k_x, double k_y, double k_z, uint64_t* words_out, int64_t ldw) {
+    const char* who = "gf2_stratum_outcomes_host";
+    if (!eff) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (locations < 1 || locations > GF2_CIRCUIT_MAX_LOCATIONS)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= locations <= %d (2^20), got %lld", who, GF2_CIRCUIT_MAX_LOCATIONS, (long long)locations);
+    if (ldr < 1 || ldr > GF2_FT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= ldr <= %d words per effect, got %lld", who, GF2_FT_MAX_LDR, (long long)ldr);
+    if (w < 0 || w > GF2_CIRCUIT_STRATUM_MAX_WEIGHT || w > locations)
+        GF2_FAIL(GF2_E_ARG, "%s: weight %lld outside [0, min(L = %lld, %d)]", who, (long long)w, (long long)locations, GF2_CIRCUIT_STRATUM_MAX_WEIGHT);
+    if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "%s: negative range", who);
+    if (ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the table's %lld words", who, (long long)ldr);
+    const double s = k_x + k_y + k_z;
+    if (!(k_x >= 0.0) || !(k_y >= 0.0) || !(k_z >= 0.0) || !(s > 0.0) || !(s < __builtin_inf()))
+        GF2_FAIL(GF2_E_ARG, "%s: the kind weights must be non-negative and finite with a positive sum", who);
+    if (count > 0 && !words_out) GF2_FAIL(GF2_E_ARG, "%s: null buffer", who);
+    const uint64_t t_1 = host_quantise(k_x / s), t_2 = host_quantise((k_x + k_y) / s);
+    const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
+    for (int64_t i = 0; i < count; ++i) {
+        uint64_t* const out = words_out + i * ldw;
+        for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
+        const uint64_t ks = host_mix64(seed + golden * ((uint64_t)(first_sample + i) + 1));
+        const uint64_t d = host_mix64(ks + stream * ((uint64_t)w + 1));          // the segment slot carries the weight
+        uint64_t picks[GF2_CIRCUIT_STRATUM_MAX_WEIGHT];
+        for (int64_t k = 0; k < w; ++k) {
+            const uint64_t v = host_mix64(d + golden * (uint64_t)(k + 1));
+            const uint64_t j = (uint64_t)(locations - w + k);
+            const uint64_t t = ((v >> 32) * (j + 1)) >> 32;                       // Floyd: a candidate in [0, j]
+            bool taken = false;
+            for (int64_t q = 0; q < k; ++q) taken |= picks[q] == t;
+            picks[k] = taken ? j : t;
+            const uint64_t c = v & 0xFFFFFFFFull;
+            const uint64_t* e = eff + (size_t)(2 * picks[k]) * ldr;
+            if (c < t_2)
+                for (int64_t q = 0; q < ldr; ++q) out[q] ^= e[q];
+            if (c >= t_1)
+                for (int64_t q = 0; q < ldr; ++q) out[q] ^= e[ldr + q];
+        }
+    }
+    return GF2_OK;
+}
+
 }  // extern "C"
 
 // ---- exact strata (DESIGN.md "Exact strata") ---------------------------------------------------------------------------------

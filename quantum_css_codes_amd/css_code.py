@@ -393,6 +393,13 @@ class CSSCode(QECC):
         from . import ec_noise
         return ec_noise.circuit_for(self, rounds, idle_data).enumerate_strata(weights, **options)
 
+    def error_correct_strata(self, weights, samples, rounds=1, idle_data=False, **options):
+        """Sampled strata `weights` of the cycle, samples[s] stratified samples each (ec_noise.ECCircuit.strata; DESIGN.md "Sampled
+        strata of the cycle"): a montecarlo.SampledPostSelectedStrata.  error_correct_strata_exact(...).merged(it) combines them
+        with the exact strata into a rate with a standard error and rigorous bounds."""
+        from . import ec_noise
+        return ec_noise.circuit_for(self, rounds, idle_data).strata(weights, samples, **options)
+
     def error_correct_single_faults(self, rounds=1):
         """[build-defined]  The census of every single fault of the cycle, no GPU needed: ECCircuit.single_faults."""
         from . import ec_noise
@@ -413,6 +420,13 @@ class CSSCode(QECC):
         coefficients of the probability that the measured bit is wrong."""
         from . import ft_noise
         return ft_noise.program_for(self, ops).enumerate_strata(weights, **options)
+
+    def logical_program_strata(self, ops, weights, samples, **options):
+        """Sampled strata `weights` of the rewritten program `ops; MEASURE`, samples[s] stratified samples each
+        (ft_noise.FTProgram.strata; DESIGN.md "Sampled strata of the measurement"): a montecarlo.SampledPostSelectedStrata, to be
+        merged with logical_program_strata_exact's."""
+        from . import ft_noise
+        return ft_noise.program_for(self, ops).strata(weights, samples, **options)
 
     def logical_program_single_faults(self, ops):
         """[build-defined]  The census of every single fault of the rewritten program, no GPU needed: FTProgram.single_faults."""

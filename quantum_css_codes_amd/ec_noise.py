@@ -243,6 +243,21 @@ class ECCircuit(object):
         return montecarlo.PostSelectedStrata(self.num_locations, weights, [run(w, f, n) for w, f, n in zip(weights, firsts, counts)],
                                              EC_FIELDS)
 
+    def strata(self, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0, host=False):
+        """Sampled strata of the cycle (DESIGN.md "Sampled strata of the cycle"): stratum s draws samples [first_sample, first_sample +
+        samples[s]) of exactly weights[s] <= 16 faults among the L locations, kinds X : Y : Z = kinds, and judges them by
+        logical_error_rates' tally rule, post-selection included (gf2_mc_ec_decode_strata).  `samples` and `first_sample` are one
+        number for all strata or one per stratum.  host=True draws the outcome words with gf2_stratum_outcomes_host and tallies them
+        with gf2_ec_tally_host: no GPU.  Returns a montecarlo.SampledPostSelectedStrata over nb = L."""
+        from . import montecarlo
+        tables = self._tables()
+        if host:
+            run = montecarlo.host_strata_run(self.effects, lambda words: _native.ec_tally_host(words, self.rounds, *tables), len(EC_FIELDS), seed)
+        else:
+            ctx, circ = _native.default_context(), self.device()
+            run = lambda first, ws, ns, ks: ctx.mc_ec_decode_strata(circ, self.rounds, *tables, int(seed), int(first), ws, ns, *ks)
+        return montecarlo.gadget_strata_local(self.num_locations, EC_FIELDS, weights, samples, kinds, first_sample, run)
+
     def single_faults(self):
         """The census of all 3 L single faults, no GPU: (classes, flipping) -- classes (L, 3) uint8, the class byte (CLASS_* bits)
         of an X, Y, Z fault (the columns, KINDS) at every location; flipping, the accepted faults with a logical flip as

@@ -206,6 +206,22 @@ class FTProgram(object):
         return montecarlo.PostSelectedStrata(self.num_locations, weights, [run(w, f, n) for w, f, n in zip(weights, firsts, counts)],
                                              FT_FIELDS)
 
+    def strata(self, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0, host=False):
+        """Sampled strata of the measurement (DESIGN.md "Sampled strata of the measurement"): stratum s draws samples [first_sample,
+        first_sample + samples[s]) of exactly weights[s] <= 16 faults among the L locations of the rewritten program, kinds X : Y : Z
+        = kinds, judged by measurement_error_rates' tally rule, post-selection included (gf2_mc_ft_decode_strata).  Arguments as
+        ECCircuit.strata's; host=True goes through gf2_stratum_outcomes_host and gf2_ft_tally_host and needs no GPU.  Returns a
+        montecarlo.SampledPostSelectedStrata over nb = L."""
+        from . import montecarlo
+        tables = self._tables()
+        if host:
+            run = montecarlo.host_strata_run(self.effects, lambda words: _native.ft_tally_host(words, self.nsteps, self.measure_mask, *tables),
+                                             len(FT_FIELDS), seed)
+        else:
+            ctx, circ = _native.default_context(), self.device()
+            run = lambda first, ws, ns, ks: ctx.mc_ft_decode_strata(circ, self.nsteps, self.measure_mask, *tables, int(seed), int(first), ws, ns, *ks)
+        return montecarlo.gadget_strata_local(self.num_locations, FT_FIELDS, weights, samples, kinds, first_sample, run)
+
     def single_faults(self):
         """The census of all 3 L single faults, no GPU: (classes, wrong) -- classes (L, 3) uint8, the class byte (CLASS_* bits) of
         an X, Y, Z fault (the columns, KINDS) at every location; wrong, the accepted faults that make the measured bit wrong, as

@@ -582,6 +582,206 @@ class PostSelectedStrata(object):
                 return k, c
         return None
 
+    def merged(self, sampled, kinds=None):
+        """These strata with the sampled ones of `sampled` (a SampledPostSelectedStrata or several): see MergedPostSelectedStrata."""
+        return MergedPostSelectedStrata(self, [sampled] if isinstance(sampled, SampledPostSelectedStrata) else list(sampled), kinds)
+
+
+# ---- sampled strata of a post-selected gadget (DESIGN.md "Sampled strata of the cycle", "Sampled strata of the measurement") --------
+
+# MergedPostSelectedStrata.rate's result: the conditional rate lies in [lower, upper] up to the statistical error `stderr` of `estimate`.
+PostSelectedRate = collections.namedtuple('PostSelectedRate', ('estimate', 'stderr', 'lower', 'upper'))
+
+
+class SampledPostSelectedStrata(object):
+    """Tallies of a stratified run of a post-selected gadget (ec_noise.ECCircuit.strata / ft_noise.FTProgram.strata) over `nb`
+    positions: `weights` (nstrata, distinct), `samples` (N_w per stratum), `counts` (nstrata x F in the order of `fields`, field 0
+    'accepted', every other field among accepted samples) and the `kinds` the strata were drawn with.  joint, acceptance and rate are
+    MergedPostSelectedStrata's over these strata alone; PostSelectedStrata.merged adds exact strata."""
+
+    SUM_FIELDS = PostSelectedStrata.SUM_FIELDS
+
+    def __init__(self, nb, weights, samples, counts, fields, kinds=(1, 1, 1)):
+        self.nb = int(nb)
+        self.fields = tuple(fields)
+        if not self.fields or self.fields[0] != 'accepted':
+            raise ValueError("the first field of a post-selected tally is 'accepted'")
+        self.weights = np.asarray(weights, dtype=np.int64).reshape(-1).copy()
+        self.samples = np.asarray(samples, dtype=np.int64).reshape(-1).copy()
+        self.counts = np.asarray(counts, dtype=np.uint64).reshape(len(self.weights), len(self.fields)).copy()
+        self.kinds = _kind_ratio(tuple(float(k) for k in kinds))
+        if self.samples.shape != self.weights.shape:
+            raise ValueError("one sample count per stratum")
+        if len(set(self.weights.tolist())) != len(self.weights):
+            raise ValueError("the weights of the strata must be distinct")
+        if len(self.weights) and (self.weights.min() < 0 or self.weights.max() > self.nb):
+            raise ValueError("a stratum's weight lies in [0, nb]")
+        if self.samples.size and self.samples.min() < 0:
+            raise ValueError("negative sample count")
+
+    def _column(self, field):
+        if field not in self.fields:
+            raise ValueError("no field %r (the fields are %s)" % (field, ', '.join(self.fields)))
+        return self.fields.index(field)
+
+    def fractions(self, field='accepted'):
+        """counts / samples per stratum (0 where a stratum has no samples): the fraction of ALL samples that are accepted and
+        carry `field`."""
+        col = self.counts[:, self._column(field)].astype(np.float64)
+        return np.divide(col, self.samples, out=np.zeros(len(col)), where=self.samples > 0)
+
+    def _alone(self):
+        return MergedPostSelectedStrata(None, [self], self.kinds)
+
+    def joint(self, p_t, field='accepted'):
+        return self._alone().joint(p_t, field)
+
+    def acceptance(self, p_t):
+        return self._alone().acceptance(p_t)
+
+    def rate(self, p_t, field='wrong'):
+        return self._alone().rate(p_t, field)
+
+    def as_dicts(self):
+        return [dict(zip(self.fields, (int(v) for v in row)), weight=int(w), samples=int(n))
+                for w, n, row in zip(self.weights, self.samples, self.counts)]
+
+
+class MergedPostSelectedStrata(object):
+    """Exact and sampled strata of one post-selected gadget together: the exact stratum where there is one (no variance, and the
+    weight counts as covered), the sampled estimate elsewhere.  `exact` is a PostSelectedStrata or None, `sampled` a list of
+    SampledPostSelectedStrata over the same nb positions and fields, all drawn with one kind ratio (that of `kinds`, when given),
+    which is then the ratio of the exact coefficients too; no weight may be sampled twice.
+
+    With B_w = binomial_weights(nb, p_t)[w], a_w the fraction of stratum w that is accepted and n_w the fraction accepted with the
+    field (for an exact stratum A_w / C(nb, w)):  N = sum_w B_w n_w,  D = sum_w B_w a_w,  T = the mass of the weights neither sampled
+    nor enumerated."""
+
+    def __init__(self, exact, sampled, kinds=None):
+        self.exact, self.sampled = exact, list(sampled)
+        if exact is None and not self.sampled:
+            raise ValueError("no strata at all")
+        first = exact if exact is not None else self.sampled[0]
+        self.nb, self.fields = first.nb, first.fields
+        if kinds is None:
+            if not self.sampled:
+                raise ValueError("kinds are needed when there are no sampled strata")
+            kinds = self.sampled[0].kinds
+        self.kinds = _kind_ratio(kinds)
+        seen = set()
+        for part in self.sampled:
+            if part.nb != self.nb:
+                raise ValueError("sampled strata over %d positions, the others over %d" % (part.nb, self.nb))
+            if part.fields != self.fields:
+                raise ValueError("sampled strata with fields %r, the others with %r" % (part.fields, self.fields))
+            if not _same_ratio(part.kinds, self.kinds):
+                raise ValueError("sampled strata drawn with kinds %r do not match %r" % (part.kinds, self.kinds))
+            live = set(part.weights[part.samples > 0].tolist())
+            if live & seen:
+                raise ValueError("two sampled strata of one weight")
+            seen |= live
+        self.weights = np.array(sorted(set(exact.weights if exact is not None else ()) | seen), dtype=np.int64)
+
+    def _column(self, field):
+        if field not in self.fields:
+            raise ValueError("no field %r (the fields are %s)" % (field, ', '.join(self.fields)))
+        return self.fields.index(field)
+
+    def _parts(self, field):
+        """weight -> (n_w, a_w, N_w), N_w = 0 for an exact stratum."""
+        self._column(field)
+        out = {}
+        for part in self.sampled:
+            for w, n, f, a in zip(part.weights.tolist(), part.samples.tolist(), part.fractions(field), part.fractions('accepted')):
+                if n > 0:
+                    out[w] = (float(f), float(a), n)
+        if self.exact is not None:
+            for w, f, a in zip(self.exact.weights, self.exact.coefficients(self.kinds, field), self.exact.coefficients(self.kinds, 'accepted')):
+                c = math.comb(self.nb, w)
+                out[w] = (float(f / c), float(a / c), 0)
+        return out
+
+    def _missing_mass(self, b_all):
+        have = np.zeros(self.nb + 1, dtype=bool)
+        have[self.weights] = True
+        return math.fsum(b_all[~have])
+
+    def joint(self, p_t, field='accepted'):
+        """P(accepted and field) at total fault probability p_t per position over the covered weights: sum_w B_w n_w."""
+        b_all = binomial_weights(self.nb, p_t)
+        return math.fsum(b_all[w] * f for w, (f, a, n) in self._parts(field).items())
+
+    def acceptance(self, p_t):
+        """(D, D + T): the probability that an attempt is accepted lies between them (up to the sampling error of D)."""
+        b_all = binomial_weights(self.nb, p_t)
+        d = math.fsum(b_all[w] * a for w, (f, a, n) in self._parts('accepted').items())
+        return d, d + self._missing_mass(b_all)
+
+    def rate(self, p_t, field='wrong'):
+        """The conditional rate P(field | accepted) of an indicator field as PostSelectedRate(estimate, stderr, lower, upper):
+        estimate R = N / D; lower = N / (D + T) and upper = (N + T) / (D + T) as PostSelectedStrata.rate defines them; stderr the
+        delta-method error of the ratio,  (1 / D) sqrt(sum over sampled w of B_w^2 [n_w (1 - R)^2 + (a_w - n_w) R^2 - (n_w - R a_w)^2]
+        / N_w):  a sample of stratum w contributes x - R y with (x, y) = (1, 1), (0, 1) or (0, 0) -- an indicator field is a subset of
+        `accepted` -- whose variance is the bracket."""
+        if field in PostSelectedStrata.SUM_FIELDS:
+            raise ValueError("rate() is defined for indicator fields; %r is a sum" % (field,))
+        b_all = binomial_weights(self.nb, p_t)
+        parts = self._parts(field)
+        n_tot = math.fsum(b_all[w] * f for w, (f, a, n) in parts.items())
+        d = math.fsum(b_all[w] * a for w, (f, a, n) in parts.items())
+        t = self._missing_mass(b_all)
+        if not d > 0:
+            raise ValueError("no accepted sample or configuration among the covered weights at p_t = %r" % (p_t,))
+        r = n_tot / d
+        var = math.fsum(b_all[w]**2 * (f * (1.0 - r)**2 + (a - f) * r**2 - (f - r * a)**2) / n for w, (f, a, n) in parts.items() if n > 0)
+        return PostSelectedRate(r, math.sqrt(max(var, 0.0)) / d, n_tot / (d + t), (n_tot + t) / (d + t))
+
+
+def host_strata_run(effects, tally, nfields, seed, chunk=1 << 18):
+    """The `run` of gadget_strata_local on the host: gf2_stratum_outcomes_host's words, `chunk` samples at a time, handed to `tally`
+    (words -> the gadget's counts; _native.ec_tally_host / ft_tally_host with the gadget's arguments)."""
+    def run(first, weights, samples, kinds):
+        out = np.zeros((len(weights), nfields), dtype=np.uint64)
+        for s, (w, count) in enumerate(zip(weights, np.asarray(samples).tolist())):
+            for done in range(0, int(count), chunk):
+                now = min(chunk, int(count) - done)
+                out[s] += tally(_native.stratum_outcomes_host(effects, w, now, kinds, seed, int(first) + done))
+        return out
+    return run
+
+
+def gadget_strata_local(nb, fields, weights, samples, kinds, first_sample, run):
+    """What ECCircuit.strata and FTProgram.strata share: the request checked and grouped as strata_local groups it (one native call
+    per distinct first sample), `run(first, weights, samples, kinds)` returning the (nstrata, F) counts of a call."""
+    weights, samples, firsts, kinds = _strata_request(weights, samples, kinds, first_sample)
+    top = min(int(nb), _native.CIRCUIT_STRATUM_MAX_WEIGHT)
+    if any(w < 0 or w > top for w in weights):
+        raise ValueError("a stratum's weight lies in [0, min(L = %d, %d)]" % (int(nb), _native.CIRCUIT_STRATUM_MAX_WEIGHT))
+    if firsts.size and firsts.min() < 0:
+        raise ValueError("negative first sample")
+    counts = np.zeros((len(weights), len(fields)), dtype=np.uint64)
+    for first, rows in _strata_calls(firsts):
+        counts[rows] = run(int(first), [weights[s] for s in rows], samples[rows], kinds)
+    return SampledPostSelectedStrata(nb, weights, samples, counts, fields, kinds)
+
+
+def gadget_strata_sharded(gadget, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0, group=None, local_fn=None):
+    """Sampled strata of an ec_noise.ECCircuit or an ft_noise.FTProgram over the ranks of a process group: every stratum's sample
+    range is cut by shard_range, this rank runs its part, and one all-reduce sums the nstrata x F counts.  `local_fn(gadget, weights,
+    samples, kinds=, seed=, first_sample=)` replaces gadget.strata (the CPU tests pass the host statement).  Returns a
+    SampledPostSelectedStrata with the whole sample counts."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+    else:
+        rank, world = 0, 1
+    weights, samples, firsts, kinds = _strata_request(weights, samples, kinds, first_sample)
+    shards = [shard_range(first, count, rank, world) for first, count in zip(firsts.tolist(), samples.tolist())]
+    fn = local_fn or (lambda g, ws, ns, kinds, seed, first_sample: g.strata(ws, ns, kinds=kinds, seed=seed, first_sample=first_sample))
+    part = fn(gadget, weights, [mine for _, mine in shards], kinds=kinds, seed=seed, first_sample=[start for start, _ in shards])
+    total, = all_reduce_histograms([part.counts.reshape(-1)], group=group)
+    return SampledPostSelectedStrata(part.nb, weights, samples, total, part.fields, kinds)
+
 
 def enumerate_sharded(circuit, weights, group=None, local_fn=None):
     """The whole strata `weights` of a FaultCircuit over the ranks of a process group: every weight's rank range [0, C(L, w)) is cut
