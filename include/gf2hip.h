@@ -541,6 +541,51 @@ int gf2_ft_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, u
                      const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
                      int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out);
 
+/* ---- malignant fault sets of the two post-selected gadgets ---------------------------------------------
+ * [build-defined, DESIGN.md "Malignant fault sets of the cycle" and "Malignant fault sets of the measurement"]  The walk of "exact
+ * strata of the two post-selected gadgets" above, unchanged -- ranks [first_rank, first_rank + count) of weight w, all 3^w kind
+ * assignments each, the same judgement -- but the configurations of a chosen class are listed instead of counted.  A
+ * configuration's class byte is the byte gf2_ec_tally_host / gf2_ft_tally_host write to class_out for its outcome words (bit 0
+ * accepted; the cycle: bit 1 flip_x, 2 flip_z, 3 uncorrectable x, 4 uncorrectable z; the measurement: bit 1 wrong, 2 first trial
+ * wrong, 3 split vote, 4 an unmatched x key, 5 an unmatched z key; 0 for a rejected configuration).  `select` is a non-empty subset of
+ * the rule's class bits, and a configuration is listed iff it is accepted and (class & select) != 0: select = 1 lists every
+ * accepted configuration.  A record is GF2_FAULT_RECORD_WORDS words:
+ *   word 0: rank(S) in the combinatorial number system, absolute (the rank first_rank counts in);
+ *   word 1: bits 0 .. 15 the kinds code sum_j kind_j 3^j, kind_j = 0 X, 1 Y, 2 Z the kind of the j-th pick in ascending location
+ *           order; bits 32 .. 39 the class byte; every other bit zero.
+ * *found_out is the number of listed configurations of the range, whatever the capacity; records_out (capacity records) holds them
+ * sorted by (word 0, kinds code) ascending and is written only if capacity >= *found_out (call again with a larger buffer
+ * otherwise; capacity 0 just counts, and records_out may then be null).  The lists of disjoint ranges concatenate.
+ *
+ * The definitions on the host, serial, no GPU needed: gf2_ec_enumerate_host's / gf2_ft_enumerate_host's walk, rule and argument
+ * errors, plus GF2_E_ARG for select == 0, for a select bit outside the rule's class bits and for capacity < 0. */
+#define GF2_FAULT_RECORD_WORDS 2
+#define GF2_EC_CLASS_BITS 0x1full
+#define GF2_FT_CLASS_BITS 0x3full
+#define GF2_FAULT_LIST_MAX_CAPACITY (1ll << 28)  /* records a device list may hold (4 GiB) */
+int gf2_ec_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                               const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                               int64_t entries2, int64_t w, int64_t first_rank, int64_t count, uint64_t select, int64_t capacity,
+                               uint64_t* records_out, int64_t* found_out);
+int gf2_ft_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                               const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                               const uint8_t* flips2, int64_t entries2, int64_t w, int64_t first_rank, int64_t count, uint64_t select,
+                               int64_t capacity, uint64_t* records_out, int64_t* found_out);
+
+/* The same lists from the device.  Circuit, layout, tables and range as gf2_ec_enumerate / gf2_ft_enumerate check them, the list's
+ * arguments as above, and capacity <= GF2_FAULT_LIST_MAX_CAPACITY.  The range is cut into the same launches; a wavefront that has
+ * anything to list takes its slots with one atomic add on a 64-bit counter that is zeroed once per call and runs on across the
+ * launches, and a record is stored only if its slot is below capacity.  The call allocates `capacity` records on the device,
+ * downloads them only when *found_out <= capacity and sorts them on the host by (word 0, kinds code): the result does not depend
+ * on the order the wavefronts arrived in and is byte-identical to the host statement's. */
+int gf2_ec_enumerate_list(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                          int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, int64_t w,
+                          int64_t first_rank, int64_t count, uint64_t select, int64_t capacity, uint64_t* records_out, int64_t* found_out);
+int gf2_ft_enumerate_list(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, uint64_t measure_mask, int64_t r1, const uint64_t* keys1,
+                          const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                          int64_t w, int64_t first_rank, int64_t count, uint64_t select, int64_t capacity, uint64_t* records_out,
+                          int64_t* found_out);
+
 /* ---- sampled strata of the two post-selected gadgets ----------------------------------------------------
  * [build-defined, DESIGN.md "Sampled strata of the cycle" and "Sampled strata of the measurement"]  The two notions above combined,
  * neither changed: stratified sample i of weight w over the gadget's L locations is the pure function of (seed, i, w) of

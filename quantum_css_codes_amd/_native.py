@@ -26,6 +26,7 @@ FT_FIELDS_COUNT, FT_MAX_LDR = 7, 16
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 ENUMERATE_MAX_WEIGHT = 8
+FAULT_RECORD_WORDS, FAULT_LIST_MAX_CAPACITY = 2, 1 << 28       # GF2_FAULT_RECORD_WORDS, GF2_FAULT_LIST_MAX_CAPACITY
 K_SYNDROME, K_HIST, K_SAMPLER, K_ELIM = 0, 1, 2, 3
 # routing flags of a context and its tunables: the few a caller needs are in include/gf2hip.h (F_MC_DENSE, F_RREF_SEQUENTIAL,
 # F_NORMALIZE_SEQUENTIAL, OPT_SLAB_PASS_LOG2, OPT_MC_CHUNK_LOG2), the rest -- routes for the parity tests and the A/B scripts -- in
@@ -141,6 +142,14 @@ SIGNATURES = {
     "gf2_ft_enumerate_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
     "gf2_ec_enumerate": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
     "gf2_ft_enumerate": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
+    "gf2_ec_enumerate_list_host": [_p, _c_i64, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64,
+                                   _p, ctypes.POINTER(_c_i64)],
+    "gf2_ft_enumerate_list_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_u64,
+                                   _c_i64, _p, ctypes.POINTER(_c_i64)],
+    "gf2_ec_enumerate_list": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p,
+                              ctypes.POINTER(_c_i64)],
+    "gf2_ft_enumerate_list": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p,
+                              ctypes.POINTER(_c_i64)],
     "gf2_stratum_outcomes_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p,
                                   _c_i64],
     "gf2_mc_ec_decode_strata": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, _p, _p,
@@ -476,6 +485,41 @@ def ft_enumerate_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, f
     """gf2_ft_enumerate_host (host code, no GPU): the (w + 1, w + 1, 7) counts of the logical measurement's tally rule, likewise."""
     return _gadget_enumerate_host(lib().gf2_ft_enumerate_host, FT_FIELDS_COUNT, eff, (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF),
                                   (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count)
+
+
+def _fault_list_call(fn, head, select, capacity, limit=None):
+    """One call of a gf2_*_enumerate_list* entry point: (found, records) -- records the (found, 2) uint64 words, or None when
+    `capacity` records (0: just count) do not hold them.  limit: the capacity above which the entry point refuses the call."""
+    capacity = int(capacity)
+    records = np.zeros((max(1, capacity if limit is None else min(capacity, limit)), FAULT_RECORD_WORDS), dtype="<u8")
+    found = _c_i64(0)
+    check(fn(*head, int(select) & 0xFFFFFFFFFFFFFFFF, capacity, _ptr(records) if capacity > 0 else None, ctypes.byref(found)))
+    found = int(found.value)
+    return found, (records[:found].copy() if found <= capacity else None)
+
+
+def _gadget_list_host(fn, eff, head, tables, w, first_rank, count, select, capacity):
+    eff = np.ascontiguousarray(eff, dtype="<u8")
+    if eff.ndim != 3 or eff.shape[1] != 2:
+        raise ValueError("eff must be (locations, 2, ldr)")
+    r1, keys1, flips1, r2, keys2, flips2 = tables
+    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+    return _fault_list_call(fn, (_ptr(eff), eff.shape[0], eff.shape[2]) + tuple(head) + (int(r1),) + t1 + (int(r2),) + t2 +
+                            (int(w), int(first_rank), int(count)), select, capacity)
+
+
+def ec_enumerate_list_host(eff, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):
+    """gf2_ec_enumerate_list_host (host code, no GPU): (found, records) of the error-correction cycle over the subsets of ranks
+    [first_rank, first_rank + count) -- found, the number of accepted configurations whose class byte has a bit of `select`;
+    records, their (found, 2) uint64 words sorted by (rank, kinds code), or None when `capacity` records do not hold them."""
+    return _gadget_list_host(lib().gf2_ec_enumerate_list_host, eff, (int(rounds),), (r1, keys1, flips1, r2, keys2, flips2), w, first_rank,
+                             count, select, capacity)
+
+
+def ft_enumerate_list_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):
+    """gf2_ft_enumerate_list_host (host code, no GPU): (found, records) of the logical measurement, likewise."""
+    return _gadget_list_host(lib().gf2_ft_enumerate_list_host, eff, (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF),
+                             (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count, select, capacity)
 
 
 # ---- context ----------------------------------------------------------------------------------------------
@@ -955,6 +999,19 @@ class Context(object):
         check(lib().gf2_ft_enumerate(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2), *t2,
                                      int(w), int(first_rank), int(count), _ptr(out)))
         return out
+
+    def ec_enumerate_list(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):
+        """gf2_ec_enumerate_list: ec_enumerate_list_host's (found, records) from the device, byte for byte."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        return _fault_list_call(lib().gf2_ec_enumerate_list, (self.handle, circ.handle, int(rounds), int(r1)) + t1 + (int(r2),) + t2 +
+                                (int(w), int(first_rank), int(count)), select, capacity, FAULT_LIST_MAX_CAPACITY)
+
+    def ft_enumerate_list(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):
+        """gf2_ft_enumerate_list: ft_enumerate_list_host's (found, records) from the device, byte for byte."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        return _fault_list_call(lib().gf2_ft_enumerate_list, (self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF,
+                                                              int(r1)) + t1 + (int(r2),) + t2 + (int(w), int(first_rank), int(count)),
+                                select, capacity, FAULT_LIST_MAX_CAPACITY)
 
     def check_create(self, packed, r, n):
         return Check(self, packed, r, n)

@@ -499,12 +499,11 @@ uint8_t ft_tally_sample(const uint64_t* w, int64_t ldr, int64_t nsteps, uint64_t
 }
 
 // The walk of an enumerated rank range (DESIGN.md "Exact strata"), serial: every subset of ranks [first_rank, first_rank + count)
-// (the first unranked, the others by the colexicographic successor), every kind assignment by an odometer over {1, 2, 3}^w, the
-// outcome words XOR-ed from scratch and handed to judge(out, bin) with the bin [n_x][n_y] of `fields` counts.
-template <class Judge>
-void gadget_enumerate_walk(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t w, int64_t first_rank, int64_t count, int fields,
-                           uint64_t* counts_out, Judge judge) {
-    const int64_t side = w + 1;
+// (the first unranked, the others by the colexicographic successor), every kind assignment by an odometer over {1, 2, 3}^w (1 X,
+// 2 Z, 3 Y: the sampler's kind bits), the outcome words XOR-ed from scratch and handed to visit(i, kind, n_x, n_y, out), i the
+// subset's place in the range and kind[k] the kind of pick k in ascending location order.
+template <class Visit>
+void gadget_walk(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t w, int64_t first_rank, int64_t count, Visit visit) {
     int32_t pos[GF2_ENUMERATE_MAX_WEIGHT] = {0};
     int kind[GF2_ENUMERATE_MAX_WEIGHT];
     subset_unrank(locations, (int)w, (uint64_t)first_rank, pos);
@@ -524,13 +523,66 @@ void gadget_enumerate_walk(const uint64_t* eff, int64_t locations, int64_t ldr, 
                 n_x += kind[k] == 1;
                 n_y += kind[k] == 3;
             }
-            judge(out, counts_out + (n_x * side + n_y) * fields);
+            visit(i, kind, n_x, n_y, out);
             int64_t k = 0;                                                   // odometer over 1, 2, 3
             while (k < w && kind[k] == 3) kind[k++] = 1;
             if (k == w) break;
             kind[k] += 1;
         }
     }
+}
+
+// ... every configuration handed to judge(out, bin) with the bin [n_x][n_y] of `fields` counts.
+template <class Judge>
+void gadget_enumerate_walk(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t w, int64_t first_rank, int64_t count, int fields,
+                           uint64_t* counts_out, Judge judge) {
+    const int64_t side = w + 1;
+    gadget_walk(eff, locations, ldr, w, first_rank, count, [&](int64_t, const int*, int64_t n_x, int64_t n_y, const uint64_t* out) {
+        judge(out, counts_out + (n_x * side + n_y) * fields);
+    });
+}
+
+// ... or listed (include/gf2hip.h "malignant fault sets"): classify(out) is the configuration's class byte; the records of the
+// listed ones, sorted by (rank, kinds code), go to records_out if they fit `capacity`, their number to *found_out either way.
+template <class Classify>
+int gadget_list_walk(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t w, int64_t first_rank, int64_t count,
+                     uint64_t select, int64_t capacity, uint64_t* records_out, int64_t* found_out, Classify classify) {
+    struct Record { uint64_t rank, tail; };
+    std::vector<Record> records;
+    int64_t found = 0;
+    try {
+        gadget_walk(eff, locations, ldr, w, first_rank, count, [&](int64_t i, const int* kind, int64_t, int64_t, const uint64_t* out) {
+            const uint8_t cls = classify(out);
+            if (!(cls & 1) || !(cls & select)) return;
+            if (found++ >= capacity) return;                                 // (counted; the list is dropped once it cannot fit)
+            uint64_t code = 0, place = 1;
+            for (int64_t k = 0; k < w; ++k, place *= 3) code += (kind[k] == 1 ? 0u : kind[k] == 3 ? 1u : 2u) * place;   // 0 X, 1 Y, 2 Z
+            records.push_back(Record{(uint64_t)first_rank + (uint64_t)i, code | (uint64_t)cls << 32});
+        });
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    *found_out = found;
+    if (found > capacity) return GF2_OK;
+    std::sort(records.begin(), records.end(), [](const Record& a, const Record& b) {
+        return a.rank != b.rank ? a.rank < b.rank : (a.tail & 0xFFFFull) < (b.tail & 0xFFFFull);
+    });
+    for (size_t k = 0; k < records.size(); ++k) {
+        records_out[GF2_FAULT_RECORD_WORDS * k] = records[k].rank;
+        records_out[GF2_FAULT_RECORD_WORDS * k + 1] = records[k].tail;
+    }
+    return GF2_OK;
+}
+
+// The argument rules of a list on top of the enumeration's (include/gf2hip.h "malignant fault sets"); class_bits: the rule's.
+int list_check_args(const char* who, uint64_t select, uint64_t class_bits, int64_t capacity, const uint64_t* records_out, const int64_t* found_out) {
+    if (!found_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (select == 0) GF2_FAIL(GF2_E_ARG, "%s: select names no class bit", who);
+    if (select & ~class_bits)
+        GF2_FAIL(GF2_E_ARG, "%s: select 0x%llx has bits outside the rule's class bits 0x%llx", who, (unsigned long long)select, (unsigned long long)class_bits);
+    if (capacity < 0) GF2_FAIL(GF2_E_ARG, "%s: negative capacity", who);
+    if (capacity > 0 && !records_out) GF2_FAIL(GF2_E_ARG, "%s: null buffer for %lld records", who, (long long)capacity);
+    return GF2_OK;
 }
 
 // The argument rules gf2_ec_tally_host and gf2_ec_enumerate_host share ...
@@ -572,6 +624,44 @@ int make_host_tables(const char* who, HostTable* tab, const uint64_t* keys1, con
     } catch (const std::bad_alloc&) {
         GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
     }
+    return GF2_OK;
+}
+
+// The argument rules gf2_ec_enumerate_host and gf2_ec_enumerate_list_host share (eff not null) ...
+int ec_enumerate_check(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                       const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                       int64_t w, int64_t first_rank, int64_t count) {
+    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
+    if (int rc = ec_check_layout(who, ldr, rounds, r1, r2)) return rc;
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
+    const uint64_t keys = ((1ull << r2) - 1) | ((1ull << r1) - 1) << 32;
+    uint64_t any[GF2_CIRCUIT_MAX_LDR] = {0};
+    for (int64_t i = 0; i < 2 * locations; ++i)
+        for (int64_t q = 0; q < ldr; ++q) any[q] |= eff[i * ldr + q];
+    bool beyond = (any[0] & ~(keys | 1ull << 31 | 1ull << 63)) != 0;
+    for (int64_t t = 1; t <= rounds; ++t) beyond |= (any[t] & ~keys) != 0;
+    if (beyond) GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits, the two parity bits and the flag words", who);
+    return GF2_OK;
+}
+
+// ... and those of gf2_ft_enumerate_host and gf2_ft_enumerate_list_host.
+int ft_enumerate_check(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                       const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                       int64_t entries2, int64_t w, int64_t first_rank, int64_t count) {
+    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
+    if (int rc = ft_check_layout(who, ldr, nsteps, measure_mask, r1, r2)) return rc;
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    uint64_t any[GF2_FT_MAX_LDR] = {0};
+    for (int64_t i = 0; i < 2 * locations; ++i)
+        for (int64_t q = 0; q < ldr; ++q) any[q] |= eff[i * ldr + q];
+    bool beyond = false;
+    for (int64_t s = 0; s < nsteps; ++s)
+        beyond |= (any[s] & ~((measure_mask >> s) & 1ull ? mask[0] | 1ull << 31 : mask[0] | mask[1] << 32)) != 0;
+    if (beyond)
+        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key bits and bit 31)", who);
     return GF2_OK;
 }
 }  // namespace
@@ -718,18 +808,8 @@ int gf2_ec_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, i
                           int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out) {
     const char* who = "gf2_ec_enumerate_host";
     if (!eff || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
-    if (int rc = ec_check_layout(who, ldr, rounds, r1, r2)) return rc;
-    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
-    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
+    if (int rc = ec_enumerate_check(who, eff, locations, ldr, rounds, r1, keys1, flips1, entries1, r2, keys2, flips2, entries2, w, first_rank, count)) return rc;
     const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
-    const uint64_t keys = mask[0] | mask[1] << 32;
-    uint64_t any[GF2_CIRCUIT_MAX_LDR] = {0};
-    for (int64_t i = 0; i < 2 * locations; ++i)
-        for (int64_t q = 0; q < ldr; ++q) any[q] |= eff[i * ldr + q];
-    bool beyond = (any[0] & ~(keys | 1ull << 31 | 1ull << 63)) != 0;
-    for (int64_t t = 1; t <= rounds; ++t) beyond |= (any[t] & ~keys) != 0;
-    if (beyond) GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits, the two parity bits and the flag words", who);
     for (int64_t k = 0; k < (w + 1) * (w + 1) * GF2_EC_FIELDS; ++k) counts_out[k] = 0;
     if (count == 0) return GF2_OK;
     HostTable tab[2];
@@ -745,20 +825,10 @@ int gf2_ft_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, i
                           const uint8_t* flips2, int64_t entries2, int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out) {
     const char* who = "gf2_ft_enumerate_host";
     if (!eff || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
-    if (int rc = ft_check_layout(who, ldr, nsteps, measure_mask, r1, r2)) return rc;
+    if (int rc = ft_enumerate_check(who, eff, locations, ldr, nsteps, measure_mask, r1, keys1, flips1, entries1, r2, keys2, flips2, entries2, w, first_rank, count))
+        return rc;
     const int trials = __builtin_popcountll(measure_mask);
-    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
-    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
     const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
-    uint64_t any[GF2_FT_MAX_LDR] = {0};
-    for (int64_t i = 0; i < 2 * locations; ++i)
-        for (int64_t q = 0; q < ldr; ++q) any[q] |= eff[i * ldr + q];
-    bool beyond = false;
-    for (int64_t s = 0; s < nsteps; ++s)
-        beyond |= (any[s] & ~((measure_mask >> s) & 1ull ? mask[0] | 1ull << 31 : mask[0] | mask[1] << 32)) != 0;
-    if (beyond)
-        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key bits and bit 31)", who);
     for (int64_t k = 0; k < (w + 1) * (w + 1) * GF2_FT_FIELDS; ++k) counts_out[k] = 0;
     if (count == 0) return GF2_OK;
     HostTable tab[2];
@@ -767,6 +837,49 @@ int gf2_ft_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, i
         (void)ft_tally_sample(out, ldr, nsteps, measure_mask, trials, mask, tab, bin);
     });
     return GF2_OK;
+}
+
+// The definition of gf2_ec_enumerate_list (DESIGN.md "Malignant fault sets of the cycle"), serial: gf2_ec_enumerate_host's walk and
+// rule, the class byte of every configuration kept instead of its counts.
+int gf2_ec_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                               const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                               int64_t entries2, int64_t w, int64_t first_rank, int64_t count, uint64_t select, int64_t capacity,
+                               uint64_t* records_out, int64_t* found_out) {
+    const char* who = "gf2_ec_enumerate_list_host";
+    if (!eff) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (int rc = list_check_args(who, select, GF2_EC_CLASS_BITS, capacity, records_out, found_out)) return rc;
+    if (int rc = ec_enumerate_check(who, eff, locations, ldr, rounds, r1, keys1, flips1, entries1, r2, keys2, flips2, entries2, w, first_rank, count)) return rc;
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    *found_out = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    return gadget_list_walk(who, eff, locations, ldr, w, first_rank, count, select, capacity, records_out, found_out, [&](const uint64_t* out) {
+        uint64_t unused[GF2_EC_FIELDS] = {0};
+        return ec_tally_sample(out, ldr, rounds, mask, tab, unused);
+    });
+}
+
+// The definition of gf2_ft_enumerate_list (DESIGN.md "Malignant fault sets of the measurement"), likewise.
+int gf2_ft_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                               const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                               const uint8_t* flips2, int64_t entries2, int64_t w, int64_t first_rank, int64_t count, uint64_t select,
+                               int64_t capacity, uint64_t* records_out, int64_t* found_out) {
+    const char* who = "gf2_ft_enumerate_list_host";
+    if (!eff) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (int rc = list_check_args(who, select, GF2_FT_CLASS_BITS, capacity, records_out, found_out)) return rc;
+    if (int rc = ft_enumerate_check(who, eff, locations, ldr, nsteps, measure_mask, r1, keys1, flips1, entries1, r2, keys2, flips2, entries2, w, first_rank, count))
+        return rc;
+    const int trials = __builtin_popcountll(measure_mask);
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    *found_out = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    return gadget_list_walk(who, eff, locations, ldr, w, first_rank, count, select, capacity, records_out, found_out, [&](const uint64_t* out) {
+        uint64_t unused[GF2_FT_FIELDS] = {0};
+        return ft_tally_sample(out, ldr, nsteps, measure_mask, trials, mask, tab, unused);
+    });
 }
 
 }  // extern "C"

@@ -393,6 +393,12 @@ class CSSCode(QECC):
         from . import ec_noise
         return ec_noise.circuit_for(self, rounds, idle_data).enumerate_strata(weights, **options)
 
+    def error_correct_malignant_faults(self, weight, rounds=1, idle_data=False, **options):
+        """The fault sets of exactly `weight` faults of the cycle that are accepted and, by default, flip the logical state, listed
+        (ec_noise.ECCircuit.malignant_faults; DESIGN.md "Malignant fault sets of the cycle"): a montecarlo.FaultList."""
+        from . import ec_noise
+        return ec_noise.circuit_for(self, rounds, idle_data).malignant_faults(weight, **options)
+
     def error_correct_strata(self, weights, samples, rounds=1, idle_data=False, **options):
         """Sampled strata `weights` of the cycle, samples[s] stratified samples each (ec_noise.ECCircuit.strata; DESIGN.md "Sampled
         strata of the cycle"): a montecarlo.SampledPostSelectedStrata.  error_correct_strata_exact(...).merged(it) combines them
@@ -420,6 +426,13 @@ class CSSCode(QECC):
         coefficients of the probability that the measured bit is wrong."""
         from . import ft_noise
         return ft_noise.program_for(self, ops).enumerate_strata(weights, **options)
+
+    def logical_program_malignant_faults(self, ops, weight, **options):
+        """The fault sets of exactly `weight` faults of the rewritten program `ops; MEASURE` that are accepted and, by default, make
+        the measured bit wrong, listed (ft_noise.FTProgram.malignant_faults; DESIGN.md "Malignant fault sets of the measurement"):
+        a montecarlo.FaultList."""
+        from . import ft_noise
+        return ft_noise.program_for(self, ops).malignant_faults(weight, **options)
 
     def logical_program_strata(self, ops, weights, samples, **options):
         """Sampled strata `weights` of the rewritten program `ops; MEASURE`, samples[s] stratified samples each

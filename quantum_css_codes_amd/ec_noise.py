@@ -23,6 +23,8 @@ everything but the table lookups is linear over GF(2) and one effect table carri
 t's syndrome decoded relative to what earlier rounds recorded, the final data frame judged against the record -- is stated in
 DESIGN.md and include/gf2hip.h; gf2_ec_tally_host is its serial form and gf2_mc_ec_decode the device kernel.
 """
+import contextlib
+
 import numpy as np
 
 from . import _native
@@ -35,18 +37,28 @@ EC_FIELDS = ('accepted', 'logical_x', 'logical_z', 'logical_any', 'uncorrectable
 ROW_UNUSED, ROW_FINAL, ROW_ROUND, ROW_FLAG = 0, 1, 2, 3
 KINDS = ('X', 'Y', 'Z')                             # the columns of single_faults' class bytes
 CLASS_ACCEPTED, CLASS_FLIP_X, CLASS_FLIP_Z, CLASS_UNCORRECTABLE_X, CLASS_UNCORRECTABLE_Z = 1, 2, 4, 8, 16
+CLASS_NAMES = ('accepted', 'flip_x', 'flip_z', 'uncorrectable_x', 'uncorrectable_z')      # the class byte's bits, from bit 0
 
 
 class ECGates(object):
     """What error_correct_gates returns: `gates` (g, 3) int32 rows (kind, a, b) on `qubits` = 3n qubits; the outcome rows `rows_x`,
     `rows_z` (64 * ldr, 3n) uint8, row r being bit r & 63 of outcome word r >> 6, with their times `row_time`; `row_kind` (ROW_UNUSED,
     ROW_FINAL, ROW_ROUND, ROW_FLAG) and `row_round` (1 .. rounds for round and flag rows, else 0); `flag_rows`, the rows of the
-    verifications in measurement order."""
+    verifications in measurement order; `spans`, the parts of the gadget as (first gate, end gate, path) with path a tuple of names
+    from the outermost part in (GadgetBuilder.span)."""
 
-    def __init__(self, gates, qubits, rounds, ldr, rows_x, rows_z, row_time, row_kind, row_round, flag_rows):
+    def __init__(self, gates, qubits, rounds, ldr, rows_x, rows_z, row_time, row_kind, row_round, flag_rows, spans=()):
         self.gates, self.qubits, self.rounds, self.ldr = gates, qubits, rounds, ldr
         self.rows_x, self.rows_z, self.row_time, self.row_kind, self.row_round = rows_x, rows_z, row_time, row_kind, row_round
         self.flag_rows = flag_rows
+        self.spans = tuple(spans)
+
+    def gate_paths(self):
+        """Per gate, the path of the innermost part it belongs to (() for a gate in none): what a fault list is grouped by."""
+        paths = [()] * len(self.gates)
+        for first, end, path in sorted(self.spans, key=lambda span: len(span[2])):     # inner parts overwrite the parts around them
+            paths[first:end] = [path] * (end - first)
+        return paths
 
     @property
     def num_rows(self):
@@ -73,43 +85,75 @@ class GadgetBuilder(object):
         self.data, self.anc_1, self.anc_2 = (list(range(b * self.n, (b + 1) * self.n)) for b in range(3))
         self.gates = []
         self.rows = []
+        self.spans, self._path = [], []
+
+    @contextlib.contextmanager
+    def span(self, name):
+        """The gates emitted inside are the part `name` of the part around them (ECGates.spans)."""
+        self._path.append(name)
+        first = len(self.gates)
+        try:
+            yield
+        finally:
+            self.spans.append((first, len(self.gates), tuple(self._path)))
+            self._path.pop()
 
     def measure(self, block, matrix, kind, rnd, bits):
-        self.gates.extend((GATE_IDLE, q, 0) for q in block)         # measurement error
+        with self.span("measure (idle)"):
+            self.gates.extend((GATE_IDLE, q, 0) for q in block)     # measurement error
         for row, bit in zip(matrix, bits):
             self.rows.append((bit, kind, rnd, len(self.gates), block, 0, row))
 
     def detect_x(self, block, verifier, rnd, include_operators):    # css_code.py:472-501
-        self.gates.extend((GATE_RESET, q, 0) for q in verifier)
-        self.gates.extend(_encoder(self.code, 'zero' if include_operators else 'plus', verifier))
-        self.gates.extend((GATE_CNOT, b, a) for b, a in zip(block, verifier))
-        matrix = np.concatenate([self.h_2, self.z_op]) if include_operators else self.h_2
-        self.measure(verifier, matrix, ROW_FLAG, rnd, [None] * len(matrix))
+        state = 'zero' if include_operators else 'plus'
+        with self.span("detect_x"):
+            with self.span("verifier reset"):
+                self.gates.extend((GATE_RESET, q, 0) for q in verifier)
+            with self.span("verifier encode_%s" % state):
+                self.gates.extend(_encoder(self.code, state, verifier))
+            with self.span("CNOT block -> verifier"):
+                self.gates.extend((GATE_CNOT, b, a) for b, a in zip(block, verifier))
+            matrix = np.concatenate([self.h_2, self.z_op]) if include_operators else self.h_2
+            self.measure(verifier, matrix, ROW_FLAG, rnd, [None] * len(matrix))
 
     def detect_z(self, block, verifier, rnd, include_operators):    # css_code.py:503-533
-        self.gates.extend((GATE_RESET, q, 0) for q in verifier)
-        self.gates.extend(_encoder(self.code, 'plus' if include_operators else 'zero', verifier))
-        self.gates.extend((GATE_CNOT, a, b) for b, a in zip(block, verifier))
-        self.gates.extend((GATE_H, a, 0) for a in verifier)
-        matrix = np.concatenate([self.h_1, self.x_op]) if include_operators else self.h_1
-        self.measure(verifier, matrix, ROW_FLAG, rnd, [None] * len(matrix))
+        state = 'plus' if include_operators else 'zero'
+        with self.span("detect_z"):
+            with self.span("verifier reset"):
+                self.gates.extend((GATE_RESET, q, 0) for q in verifier)
+            with self.span("verifier encode_%s" % state):
+                self.gates.extend(_encoder(self.code, state, verifier))
+            with self.span("CNOT verifier -> block"):
+                self.gates.extend((GATE_CNOT, a, b) for b, a in zip(block, verifier))
+            with self.span("H verifier"):
+                self.gates.extend((GATE_H, a, 0) for a in verifier)
+            matrix = np.concatenate([self.h_1, self.x_op]) if include_operators else self.h_1
+            self.measure(verifier, matrix, ROW_FLAG, rnd, [None] * len(matrix))
 
     def prep(self, block, state, rnd, verifier=None):               # css_code.py:314-366, one attempt
         verifier = self.anc_2 if verifier is None else verifier
-        self.gates.extend((GATE_RESET, q, 0) for q in block)
-        self.gates.extend(_encoder(self.code, state, block))
-        self.detect_x(block, verifier, rnd, include_operators=state == 'zero')
-        self.detect_z(block, verifier, rnd, include_operators=state == 'plus')
+        with self.span("prep %s" % state):
+            with self.span("reset"):
+                self.gates.extend((GATE_RESET, q, 0) for q in block)
+            with self.span("encode_%s" % state):
+                self.gates.extend(_encoder(self.code, state, block))
+            self.detect_x(block, verifier, rnd, include_operators=state == 'zero')
+            self.detect_z(block, verifier, rnd, include_operators=state == 'plus')
 
     def error_correct(self, rnd, word):                             # css_code.py:458-470; the keys go to outcome word `word`
         r_1, r_2 = self.r_1, self.r_2
-        self.prep(self.anc_1, 'plus', rnd)
-        self.gates.extend((GATE_CNOT, d, a) for d, a in zip(self.data, self.anc_1))
-        self.measure(self.anc_1, self.h_2, ROW_ROUND, rnd, [64 * word + r_2 - 1 - i for i in range(r_2)])
-        self.prep(self.anc_1, 'zero', rnd)
-        self.gates.extend((GATE_CNOT, a, d) for d, a in zip(self.data, self.anc_1))
-        self.gates.extend((GATE_H, a, 0) for a in self.anc_1)
-        self.measure(self.anc_1, self.h_1, ROW_ROUND, rnd, [64 * word + 32 + r_1 - 1 - i for i in range(r_1)])
+        with self.span("x half"):
+            self.prep(self.anc_1, 'plus', rnd)
+            with self.span("CNOT data -> ancilla"):
+                self.gates.extend((GATE_CNOT, d, a) for d, a in zip(self.data, self.anc_1))
+            self.measure(self.anc_1, self.h_2, ROW_ROUND, rnd, [64 * word + r_2 - 1 - i for i in range(r_2)])
+        with self.span("z half"):
+            self.prep(self.anc_1, 'zero', rnd)
+            with self.span("CNOT ancilla -> data"):
+                self.gates.extend((GATE_CNOT, a, d) for d, a in zip(self.data, self.anc_1))
+            with self.span("H ancilla"):
+                self.gates.extend((GATE_H, a, 0) for a in self.anc_1)
+            self.measure(self.anc_1, self.h_1, ROW_ROUND, rnd, [64 * word + 32 + r_1 - 1 - i for i in range(r_1)])
 
     @property
     def num_flags(self):
@@ -144,9 +188,11 @@ def error_correct_gates(code, rounds=1, idle_data=False):
         raise ValueError("the error-correction cycle needs 1 <= rounds <= %d" % MAX_ROUNDS)
     r_1, r_2, data = build.r_1, build.r_2, build.data
     for t in range(1, rounds + 1):                                  # css_code.py:458-470
-        if idle_data:
-            build.gates.extend((GATE_IDLE, q, 0) for q in data)
-        build.error_correct(t, t)
+        with build.span("round %d" % t):
+            if idle_data:
+                with build.span("data idle"):
+                    build.gates.extend((GATE_IDLE, q, 0) for q in data)
+            build.error_correct(t, t)
     end = len(build.gates)
     for i in range(r_2):                                            # vec_to_int: row 0 is the most significant bit
         build.rows.append((r_2 - 1 - i, ROW_FINAL, 0, end, data, 0, build.h_2[i]))
@@ -161,7 +207,7 @@ def error_correct_gates(code, rounds=1, idle_data=False):
         raise ValueError("%d rounds with %d flag rows need %d outcome words per sample, more than %d"
                          % (rounds, flags, ldr, _native.CIRCUIT_MAX_LDR))
     gates, rows_x, rows_z, row_time, row_kind, row_round, flag_rows = build.arrays(ldr, 1 + rounds)
-    return ECGates(gates, 3 * build.n, rounds, ldr, rows_x, rows_z, row_time, row_kind, row_round, flag_rows)
+    return ECGates(gates, 3 * build.n, rounds, ldr, rows_x, rows_z, row_time, row_kind, row_round, flag_rows, build.spans)
 
 
 class ECCircuit(object):
@@ -243,6 +289,25 @@ class ECCircuit(object):
         return montecarlo.PostSelectedStrata(self.num_locations, weights, [run(w, f, n) for w, f, n in zip(weights, firsts, counts)],
                                              EC_FIELDS)
 
+    def malignant_faults(self, weight, select=CLASS_FLIP_X | CLASS_FLIP_Z, first_rank=None, count=None, max_configurations=None, host=False):
+        """The malignant fault sets of the cycle (DESIGN.md "Malignant fault sets of the cycle"): enumerate_strata's walk of the
+        configurations of exactly `weight` <= 8 faults over ranks [first_rank, first_rank + count) (default: everything), but the
+        accepted ones whose class byte has a bit of `select` (CLASS_* bits; CLASS_ACCEPTED lists every accepted one) are listed,
+        not counted (gf2_ec_enumerate_list; host=True: gf2_ec_enumerate_list_host, no GPU).  Budget as enumerate_strata's; more
+        than 2^26 records is a ValueError.  Returns a montecarlo.FaultList over nb = L, which describe() puts into words."""
+        from . import montecarlo
+        if host:
+            run = lambda w, f, n, select, capacity: _native.ec_enumerate_list_host(self.effects, self.rounds, *self._tables(), w, f, n, select, capacity)
+        else:
+            ctx, circ = _native.default_context(), self.device()
+            run = lambda w, f, n, select, capacity: ctx.ec_enumerate_list(circ, self.rounds, *self._tables(), w, f, n, select, capacity)
+        return montecarlo.malignant_faults(self.num_locations, weight, CLASS_NAMES, select, first_rank, count, max_configurations, "cycle", run)
+
+    def describe(self, fault_list):
+        """Every record of a FaultList of this cycle as a tuple over its picks of (gate index, gate (kind, a, b), qubit, 'X' / 'Y' /
+        'Z'): single_faults' format, so the weight-1 list of the default select reads as single_faults()[1]."""
+        return describe_faults(self, fault_list)
+
     def strata(self, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0, host=False):
         """Sampled strata of the cycle (DESIGN.md "Sampled strata of the cycle"): stratum s draws samples [first_sample, first_sample +
         samples[s]) of exactly weights[s] <= 16 faults among the L locations, kinds X : Y : Z = kinds, and judges them by
@@ -271,6 +336,20 @@ class ECCircuit(object):
             g, q = (int(v) for v in self.locations[l])
             flipping.append((g, tuple(int(v) for v in self.gadget.gates[g]), q, KINDS[k]))
         return classes, flipping
+
+
+def describe_faults(gadget, fault_list):
+    """ECCircuit.describe and FTProgram.describe: `gadget` has num_locations, locations (location -> gate, qubit) and gadget.gates."""
+    if fault_list.nb != gadget.num_locations:
+        raise ValueError("the list is over %d locations, the gadget has %d" % (fault_list.nb, gadget.num_locations))
+    out = []
+    for picks, kinds in zip(fault_list.locations().tolist(), fault_list.kinds().tolist()):
+        row = []
+        for l, k in zip(picks, kinds):
+            g, q = (int(v) for v in gadget.locations[l])
+            row.append((g, tuple(int(v) for v in gadget.gadget.gates[g]), q, KINDS[k]))
+        out.append(tuple(row))
+    return out
 
 
 def circuit_for(code, rounds=1, idle_data=False):

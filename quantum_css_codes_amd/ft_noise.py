@@ -35,6 +35,7 @@ from .errors import UnsupportedProgramError
 MAX_LDR = _native.FT_MAX_LDR
 FT_FIELDS = ('accepted', 'wrong', 'trial_wrong', 'first_trial_wrong', 'split_vote', 'unmatched_x', 'unmatched_z')
 CLASS_ACCEPTED, CLASS_WRONG, CLASS_FIRST_TRIAL_WRONG, CLASS_SPLIT_VOTE, CLASS_UNMATCHED_X, CLASS_UNMATCHED_Z = 1, 2, 4, 8, 16, 32
+CLASS_NAMES = ('accepted', 'wrong', 'first_trial_wrong', 'split_vote', 'unmatched_x', 'unmatched_z')   # the class byte's bits, from bit 0
 PAULIS = ('I', 'X', 'Y', 'Z')
 
 
@@ -70,22 +71,28 @@ def program_gates(code, ops):
     trials = 2 * int(code.t) + 1
     nsteps = len(ops) + 2 * trials
     r_2, data, anc_1 = build.r_2, build.data, build.anc_1
-    build.prep(data, 'zero', 0, verifier=anc_1)                     # ftqc.py:78
+    with build.span("prepare data"):
+        build.prep(data, 'zero', 0, verifier=anc_1)                 # ftqc.py:78
     step, measure_mask, pauli_gates = 0, 0, []
     for op in ops:                                                  # ftqc.py:80-83
-        for q in logical_pauli_qubits(code, op):
-            pauli_gates.append(len(build.gates))
-            build.gates.append((GATE_IDLE, data[q], 0))
-        build.error_correct(step + 1, step)
+        with build.span("step %d: logical %s, EC" % (step, op)):
+            with build.span("logical Pauli"):
+                for q in logical_pauli_qubits(code, op):
+                    pauli_gates.append(len(build.gates))
+                    build.gates.append((GATE_IDLE, data[q], 0))
+            build.error_correct(step + 1, step)
         step += 1
-    for _ in range(trials):                                         # ftqc.py:84-89, css_code.py:576-579
-        build.prep(anc_1, 'zero', step + 1)                         # css_code.py:629
-        build.gates.extend((GATE_CNOT, d, a) for d, a in zip(data, anc_1))
-        build.measure(anc_1, np.concatenate([build.h_2, build.z_op[:1]]), ROW_ROUND, step + 1,
-                      [64 * step + r_2 - 1 - i for i in range(r_2)] + [64 * step + 31])
+    for trial in range(trials):                                     # ftqc.py:84-89, css_code.py:576-579
+        with build.span("step %d: MEASURE trial %d" % (step, trial)):
+            build.prep(anc_1, 'zero', step + 1)                     # css_code.py:629
+            with build.span("CNOT data -> ancilla"):
+                build.gates.extend((GATE_CNOT, d, a) for d, a in zip(data, anc_1))
+            build.measure(anc_1, np.concatenate([build.h_2, build.z_op[:1]]), ROW_ROUND, step + 1,
+                          [64 * step + r_2 - 1 - i for i in range(r_2)] + [64 * step + 31])
         measure_mask |= 1 << step
         step += 1
-        build.error_correct(step + 1, step)
+        with build.span("step %d: EC after trial %d" % (step, trial)):
+            build.error_correct(step + 1, step)
         step += 1
     assert step == nsteps
     flags = build.num_flags
@@ -94,7 +101,7 @@ def program_gates(code, ops):
         raise ValueError("%d logical gates give %d steps and %d flag rows: %d outcome words per sample (ldr %d), more than %d"
                          % (len(ops), nsteps, flags, ldr, ldr, MAX_LDR))
     gates, rows_x, rows_z, row_time, row_kind, row_round, flag_rows = build.arrays(ldr, nsteps)
-    out = FTGates(gates, 3 * build.n, nsteps - trials, ldr, rows_x, rows_z, row_time, row_kind, row_round, flag_rows)
+    out = FTGates(gates, 3 * build.n, nsteps - trials, ldr, rows_x, rows_z, row_time, row_kind, row_round, flag_rows, build.spans)
     out.ops, out.nsteps, out.measure_mask, out.trials, out.pauli_gates = ops, nsteps, measure_mask, trials, pauli_gates
     return out
 
@@ -205,6 +212,26 @@ class FTProgram(object):
             run = lambda w, f, n: ctx.ft_enumerate(circ, self.nsteps, self.measure_mask, *self._tables(), w, f, n)
         return montecarlo.PostSelectedStrata(self.num_locations, weights, [run(w, f, n) for w, f, n in zip(weights, firsts, counts)],
                                              FT_FIELDS)
+
+    def malignant_faults(self, weight, select=CLASS_WRONG, first_rank=None, count=None, max_configurations=None, host=False):
+        """The malignant fault sets of the measurement (DESIGN.md "Malignant fault sets of the measurement"): the accepted
+        configurations of exactly `weight` <= 8 faults of the rewritten program whose class byte has a bit of `select` (CLASS_*
+        bits), listed (gf2_ft_enumerate_list; host=True: gf2_ft_enumerate_list_host, no GPU).  Arguments and result as
+        ECCircuit.malignant_faults': a montecarlo.FaultList over nb = L."""
+        from . import montecarlo
+        if host:
+            run = lambda w, f, n, select, capacity: _native.ft_enumerate_list_host(self.effects, self.nsteps, self.measure_mask, *self._tables(),
+                                                                                   w, f, n, select, capacity)
+        else:
+            ctx, circ = _native.default_context(), self.device()
+            run = lambda w, f, n, select, capacity: ctx.ft_enumerate_list(circ, self.nsteps, self.measure_mask, *self._tables(), w, f, n,
+                                                                          select, capacity)
+        return montecarlo.malignant_faults(self.num_locations, weight, CLASS_NAMES, select, first_rank, count, max_configurations, "program", run)
+
+    def describe(self, fault_list):
+        """Every record of a FaultList of this program as a tuple over its picks of (gate index, gate (kind, a, b), qubit, 'X' / 'Y' /
+        'Z'): single_faults' format, so the weight-1 list of the default select reads as single_faults()[1]."""
+        return ec_noise.describe_faults(self, fault_list)
 
     def strata(self, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0, host=False):
         """Sampled strata of the measurement (DESIGN.md "Sampled strata of the measurement"): stratum s draws samples [first_sample,

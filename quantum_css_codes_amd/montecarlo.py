@@ -587,6 +587,132 @@ class PostSelectedStrata(object):
         return MergedPostSelectedStrata(self, [sampled] if isinstance(sampled, SampledPostSelectedStrata) else list(sampled), kinds)
 
 
+# ---- malignant fault sets of a post-selected gadget (DESIGN.md "Malignant fault sets of the cycle", "... of the measurement") --------
+
+class FaultList(object):
+    """The listed fault configurations of a post-selected gadget (ec_noise.ECCircuit / ft_noise.FTProgram.malignant_faults): the
+    accepted configurations of exactly `weight` faults among `nb` locations whose class byte has a bit of the call's `select`, over
+    the rank `ranges` ((first_rank, count) pairs, ascending and disjoint).  `records` is the (found, 2) uint64 array of
+    include/gf2hip.h "malignant fault sets", sorted by (rank, kinds code); `class_names` names the bits of the class byte from bit 0
+    ('accepted') up.  ranks, kind_codes and classes are its columns.  The object and its arrays are read-only."""
+
+    def __init__(self, nb, weight, records, class_names, ranges=None):
+        records = np.array(records, dtype=np.uint64).reshape(-1, _native.FAULT_RECORD_WORDS)
+        nb, weight = int(nb), int(weight)
+        if not 0 <= weight <= min(nb, _native.ENUMERATE_MAX_WEIGHT):
+            raise ValueError("a fault list's weight lies in [0, min(nb, %d)]" % _native.ENUMERATE_MAX_WEIGHT)
+        class_names = tuple(class_names)
+        if not class_names or class_names[0] != 'accepted' or len(class_names) > 8:
+            raise ValueError("the class byte's bit 0 is 'accepted', and it has at most 8 bits")
+        total = math.comb(nb, weight)
+        ranges = ((0, total),) if ranges is None else tuple((int(f), int(n)) for f, n in ranges)
+        if any(f < 0 or n < 0 or f + n > total for f, n in ranges) or any(a[0] + a[1] > b[0] for a, b in zip(ranges[:-1], ranges[1:])):
+            raise ValueError("the rank ranges of a fault list are ascending, disjoint and within [0, C(nb, weight))")
+        ranks = records[:, 0].copy()
+        codes = (records[:, 1] & np.uint64(0xFFFF)).astype(np.int64)
+        classes = ((records[:, 1] >> np.uint64(32)) & np.uint64(0xFF)).astype(np.uint8)
+        if len(records):
+            ordered = (ranks[1:] > ranks[:-1]) | ((ranks[1:] == ranks[:-1]) & (codes[1:] > codes[:-1]))
+            covered = np.zeros(len(records), dtype=bool)
+            for f, n in ranges:
+                covered |= (ranks >= np.uint64(f)) & (ranks < np.uint64(f + n))
+            if (not covered.all() or int(codes.max()) >= 3**weight or not ordered.all()
+                    or (records[:, 1] & ~np.uint64(0xFF0000FFFF)).any() or not (classes & 1).all()):
+                raise ValueError("records must be accepted configurations of the ranges, sorted by (rank, kinds code), stray bits zero")
+        for arr in (records, ranks, codes, classes):
+            arr.setflags(write=False)
+        for name, value in (('nb', nb), ('weight', weight), ('records', records), ('class_names', class_names), ('ranges', ranges),
+                            ('ranks', ranks), ('kind_codes', codes), ('classes', classes)):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a FaultList is immutable")
+
+    def __len__(self):
+        return len(self.records)
+
+    def __add__(self, other):
+        """The list over both lists' ranges: `other`'s ranges lie above this one's; the records are concatenated in order."""
+        if not isinstance(other, FaultList):
+            return NotImplemented
+        if (self.nb, self.weight, self.class_names) != (other.nb, other.weight, other.class_names):
+            raise ValueError("only lists of one (nb, weight) and one gadget's classes concatenate")
+        return FaultList(self.nb, self.weight, np.concatenate((self.records, other.records)), self.class_names, self.ranges + other.ranges)
+
+    def _hit(self, mask):
+        return np.ones(len(self), dtype=bool) if mask is None else (self.classes & np.uint8(int(mask) & 0xFF)) != 0
+
+    def locations(self):
+        """(found, weight) int64: the locations of every record, ascending along a row -- its rank unranked in the combinatorial
+        number system (pick k is the largest s with C(s, k + 1) <= what is left of the rank), on the host."""
+        out = np.zeros((len(self), self.weight), dtype=np.int64)
+        left = self.ranks.copy()
+        top = (1 << 63) - 1                                          # ranks lie below 2^63; larger binomials only need to compare above
+        for k in range(self.weight, 0, -1):
+            table = np.array([min(math.comb(s, k), top) for s in range(self.nb + 1)], dtype=np.uint64)
+            pick = np.searchsorted(table, left, side='right') - 1
+            out[:, k - 1] = pick
+            left = left - table[pick]
+        return out
+
+    def kinds(self):
+        """(found, weight) uint8: the kind (0 X, 1 Y, 2 Z) of every pick, in the order of locations()."""
+        codes = self.kind_codes.copy()
+        out = np.zeros((len(self), self.weight), dtype=np.uint8)
+        for j in range(self.weight):
+            out[:, j] = codes % 3
+            codes //= 3
+        return out
+
+    def composition_counts(self, mask=None):
+        """(weight + 1, weight + 1) int64 [n_x][n_y]: the records whose class byte has a bit of `mask` (None: all), per kind
+        composition -- PostSelectedStrata's counts of the matching indicator field."""
+        kinds = self.kinds()[self._hit(mask)]
+        out = np.zeros((self.weight + 1, self.weight + 1), dtype=np.int64)
+        np.add.at(out, ((kinds == 0).sum(axis=1), (kinds == 1).sum(axis=1)), 1)
+        return out
+
+    def location_counts(self, mask=None):
+        """(nb,) int64: in how many of the listed sets (with a class bit of `mask`; None: all) each location takes part."""
+        return np.bincount(self.locations()[self._hit(mask)].reshape(-1), minlength=self.nb).astype(np.int64)
+
+    def coefficient(self, kinds=(1, 1, 1), mask=None):
+        """sum over the records (with a class bit of `mask`) of prod_picks k_kind / s^weight as a fractions.Fraction (a float when
+        the kinds are not rational): PostSelectedStrata.coefficients' A_w of the matching indicator field when the list is whole."""
+        kinds = _kind_ratio(kinds)
+        exact = all(isinstance(k, numbers.Rational) for k in kinds)
+        k_x, k_y, k_z = (_fractions.Fraction(k) for k in kinds) if exact else (float(k) for k in kinds)
+        w, counts = self.weight, self.composition_counts(mask)
+        total = _fractions.Fraction(0) if exact else 0.0
+        for n_x in range(w + 1):
+            for n_y in range(w + 1 - n_x):
+                if counts[n_x, n_y]:
+                    total += int(counts[n_x, n_y]) * k_x**n_x * k_y**n_y * k_z**(w - n_x - n_y)
+        return total / (k_x + k_y + k_z)**w
+
+
+FAULT_LIST_FIRST_CAPACITY = 1 << 16                                  # records of malignant_faults' first call
+FAULT_LIST_MAX_RECORDS = 1 << 26                                     # ... and the most it returns
+
+
+def malignant_faults(nb, weight, class_names, select, first_rank, count, max_configurations, what, run):
+    """What ECCircuit.malignant_faults and FTProgram.malignant_faults share: the request checked as the exact strata's
+    (circuit_noise.gadget_enumerate_request), run(w, first, count, select, capacity) -> (found, records or None) called with
+    FAULT_LIST_FIRST_CAPACITY records and, if they do not hold the list, once more with exactly `found`."""
+    from . import circuit_noise
+    (weight,), (first,), (count,) = circuit_noise.gadget_enumerate_request(nb, [int(weight)], first_rank, count, max_configurations, what)
+    select = int(select)
+    if select <= 0 or select >> len(class_names):
+        raise ValueError("select is a non-empty subset of the class bits 0x%x (%s)" % ((1 << len(class_names)) - 1, ', '.join(class_names)))
+    found, records = run(weight, first, count, select, FAULT_LIST_FIRST_CAPACITY)
+    if records is None:
+        if found > FAULT_LIST_MAX_RECORDS:
+            raise ValueError("%d fault configurations to list, more than %d (2^26): choose a narrower select or a smaller rank range"
+                             % (found, FAULT_LIST_MAX_RECORDS))
+        found, records = run(weight, first, count, select, found)
+    return FaultList(nb, weight, records, class_names, [(first, count)])
+
+
 # ---- sampled strata of a post-selected gadget (DESIGN.md "Sampled strata of the cycle", "Sampled strata of the measurement") --------
 
 # MergedPostSelectedStrata.rate's result: the conditional rate lies in [lower, upper] up to the statistical error `stderr` of `estimate`.
