@@ -621,6 +621,76 @@ int gf2_mc_ft_decode_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t ns
                             const uint8_t* flips2, int64_t entries2, uint64_t seed, int64_t first_sample, int64_t nstrata,
                             const int32_t* weights, const int64_t* counts, double k_x, double k_y, double k_z, uint64_t* counts_out);
 
+/* ---- streamed gadgets: error-correction cycles and programs of any length, block by block ---------------
+ * [build-defined, DESIGN.md "Streamed gadgets"]  Both ancilla blocks are RESET at the start of every preparation, so only the data
+ * block survives from one block of a gadget -- the first preparation, an EC round, a MEASURE trial -- to the next.  A fault inside a
+ * block therefore acts through three words: `local`, what it flips of its own block's measured word (the layout of an EC or a
+ * MEASURE step's word above); `tail`, what it leaves on the data frame at the block's end (word 0 of a cycle's layout: key_x in bits
+ * 0 .. r_2 - 1, z_operator . e_x in bit 31, key_z in bits 32 .. 32 + r_1 - 1, x_operator . e_z in bit 63); `flags`, what it flips
+ * of its own block's flag rows in measurement order (at most 64 rows per block).  A gadget is a sequence of blocks, each of a block
+ * TYPE (a table of 2 * locations * 3 words: per location the three words of an X fault, then those of a Z fault -- gf2_circuit_effects_timed's
+ * table of the block's gate list at ldr = 3) and a KIND that says what its word is:
+ *   GF2_STREAM_NONE     no word (the first preparation); its local words must be zero
+ *   GF2_STREAM_EC       a round of error_correct: an EC step
+ *   GF2_STREAM_MEASURE  a trial of the logical measurement: a MEASURE step
+ *   GF2_STREAM_FINAL    the judgement of the final data frame: a pseudo-block of no locations, block type -1, the last block
+ * Fault locations are numbered through the blocks in order, L <= GF2_CIRCUIT_MAX_LOCATIONS in all, and sample i has the faults
+ * gf2_circuit_outcomes_dev draws for a circuit of L locations.  With T = 0, the blocks in order: the block's step word is
+ * mask_kind(T) ^ (XOR of its faults' local words) -- an EC step reads T's two keys, a MEASURE step key_x and bit 31, the FINAL step all
+ * of T -- then T ^= XOR of its faults' tail words.  Stream layout of a sample, nsteps + F words: [step 0 .. nsteps - 1] [F >= 1 flag
+ * words: the flag rows of all blocks in order, 64 per word].  A sequence has either one FINAL step as its last step or an odd number
+ * of MEASURE steps and no FINAL step.  Tally rule per sample: gf2_ec_tally_host's and gf2_ft_tally_host's, word for word -- accepted
+ * iff every flag word is zero; one record (K, P) per side through the steps in order; an EC step updates both sides, a MEASURE
+ * step the x side only and reads its trial against the updated record; the FINAL step judges T against the record.
+ * counts[GF2_STREAM_FIELDS]: accepted; the FINAL step's logical_x, logical_z, logical_any, uncorrectable_x, uncorrectable_z;
+ * unmatched_x, unmatched_z over the EC and MEASURE steps; wrong, trial_wrong, first_trial_wrong, split_vote over the MEASURE steps
+ * (zero without any) -- all but the first among accepted samples. */
+#define GF2_STREAM_FIELDS 12
+#define GF2_STREAM_NONE 0
+#define GF2_STREAM_EC 1
+#define GF2_STREAM_MEASURE 2
+#define GF2_STREAM_FINAL 3
+#define GF2_STREAM_MAX_TYPES 64
+#define GF2_STREAM_MAX_OVERLAP 8
+typedef struct gf2_stream gf2_stream;
+
+/* The words on the host, serial, no GPU needed: sample i has the faults fault_first[i] .. fault_first[i + 1] - 1 (fault_first[0] = 0),
+ * each a location in [0, L) and a kind 1 (X), 2 (Z) or 3 (Y); words_out is count x ldw (ldw >= nsteps + F), words past nsteps + F are
+ * left as they were.  type_eff holds the types' tables one after the other; type_flags[t] <= 64 is the number of flag rows of type
+ * t.  GF2_E_ARG, naming the limit: ntypes outside [1, GF2_STREAM_MAX_TYPES], a type without locations, more than 64 flag rows in a
+ * block, flag bits at or above a type's rows, a block type or kind out of range, a FINAL step that is not last or has a type,
+ * neither a FINAL step nor an odd number of MEASURE steps, L > 2^20, a fault outside [0, L) or of no kind. */
+int gf2_stream_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                          const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* fault_first,
+                          const int32_t* fault_location, const uint8_t* fault_kind, int64_t count, uint64_t* words_out, int64_t ldw);
+
+/* The tally rule on the host over stream-layout words (count x ldw, ldw >= nsteps + flag_words), serial, no GPU needed and no bound
+ * on the steps; the steps are the blocks whose kind is not NONE.  Tables as gf2_ec_tally_host takes them.  class_out (may be
+ * null): one byte per sample, bit 0 accepted, bit 1 flip_x, bit 2 flip_z, bit 3 uncorrectable x, bit 4 uncorrectable z, bit 5 wrong,
+ * bit 6 first trial wrong, bit 7 split vote (0 for a rejected sample).  GF2_E_ARG, naming the limit: r > 31, the kind rules above,
+ * flag_words < 1, a key twice in a table. */
+int gf2_stream_tally_host(const uint64_t* words, int64_t count, int64_t ldw, const int32_t* block_kind, int64_t nblocks, int64_t flag_words,
+                          int64_t r1, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                          const uint8_t* flips2, int64_t entries2, uint64_t* counts_out, uint8_t* class_out);
+
+/* A sequence on the device: the types' tables and where every block lies.  Argument rules as gf2_stream_words_host's; in addition
+ * no 512-location segment of the sampler may overlap more than GF2_STREAM_MAX_OVERLAP blocks (the FINAL step counts with the last
+ * segment): GF2_E_ARG, naming it.  Destroyed by gf2_stream_destroy. */
+int gf2_stream_create(gf2_ctx* ctx, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                      const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, gf2_stream** stream_out);
+int gf2_stream_destroy(gf2_ctx* ctx, gf2_stream* stream);
+
+/* The stream-layout words of samples first_sample .. first_sample + count - 1, rejected ones included: ldo >= nsteps + F words per
+ * sample in device memory. */
+int gf2_stream_outcomes_dev(gf2_ctx* ctx, const gf2_stream* stream, uint64_t seed, int64_t first_sample, int64_t count, double p_x,
+                            double p_y, double p_z, uint64_t* out_dev, int64_t ldo);
+
+/* The tally of those samples on the device, no word stored: time and memory per sample are linear in the number of blocks.
+ * GF2_E_ARG when the sequence's effects set a bit outside the layout given r_1 and r_2.  counts_out[GF2_STREAM_FIELDS] on the host. */
+int gf2_mc_stream_decode(gf2_ctx* ctx, const gf2_stream* stream, int64_t r1, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1,
+                         int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed, int64_t first_sample,
+                         int64_t count, double p_x, double p_y, double p_z, uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

@@ -23,6 +23,8 @@ GATE_H, GATE_CNOT, GATE_IDLE = 0, 1, 2
 GATE_RESET = 3                                      # circuit_effects_timed only
 EC_FIELDS_COUNT, EC_MAX_ROUNDS = 8, 6
 FT_FIELDS_COUNT, FT_MAX_LDR = 7, 16
+STREAM_FIELDS_COUNT, STREAM_MAX_TYPES, STREAM_MAX_OVERLAP = 12, 64, 8
+STREAM_NONE, STREAM_EC, STREAM_MEASURE, STREAM_FINAL = 0, 1, 2, 3
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 ENUMERATE_MAX_WEIGHT = 8
@@ -156,6 +158,13 @@ SIGNATURES = {
                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
     "gf2_mc_ft_decode_strata": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, _p, _p,
                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
+    "gf2_stream_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _c_i64, _p, _c_i64],
+    "gf2_stream_tally_host": [_p, _c_i64, _c_i64, _p, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _p],
+    "gf2_stream_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _pp],
+    "gf2_stream_destroy": [_p, _p],
+    "gf2_stream_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p, _c_i64],
+    "gf2_mc_stream_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
+                             ctypes.c_double, _p],
     "gf2_comm_unique_id": [_p, ctypes.c_size_t],
     "gf2_comm_create": [_p, _p, ctypes.c_int, ctypes.c_int, _pp],
     "gf2_comm_create_all": [_pp, ctypes.c_int, _pp],
@@ -392,6 +401,52 @@ def ft_tally_host(words, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, fli
     check(lib().gf2_ft_tally_host(_ptr(words) if len(words) else None, len(words), words.shape[1], words.shape[1] if ldr is None else int(ldr),
                                   int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2), *t2, _ptr(counts),
                                   _ptr(cls) if classes else None))
+    return (counts, cls[:len(words)]) if classes else counts
+
+
+def _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind):
+    """The arrays of a block sequence as the gf2_stream_* entry points take them, and their pointer arguments."""
+    eff = np.ascontiguousarray(type_eff, dtype="<u8")
+    if eff.ndim != 3 or eff.shape[1:] != (2, 3):
+        raise ValueError("type_eff must be (locations of all types, 2, 3)")
+    locs = np.ascontiguousarray(type_locations, dtype=np.int64).reshape(-1)
+    flags = np.ascontiguousarray(type_flags, dtype=np.int64).reshape(-1)
+    types = np.ascontiguousarray(block_type, dtype=np.int32).reshape(-1)
+    kinds = np.ascontiguousarray(block_kind, dtype=np.int32).reshape(-1)
+    if len(locs) != len(flags) or len(types) != len(kinds) or int(locs.sum()) != len(eff):
+        raise ValueError("one location count and one flag count per type, one type and one kind per block, type_eff as long as the types")
+    keep = (eff, locs, flags, types, kinds)
+    return keep, (_ptr(eff), _ptr(locs), _ptr(flags), len(locs), _ptr(types), _ptr(kinds), len(kinds))
+
+
+def stream_words_host(type_eff, type_locations, type_flags, block_type, block_kind, fault_first, fault_location, fault_kind, ldw):
+    """gf2_stream_words_host (host code, no GPU): the (samples, ldw) stream-layout words of samples given by their faults -- sample i
+    has faults fault_first[i] .. fault_first[i + 1] - 1, each a location and a kind 1 (X), 2 (Z) or 3 (Y)."""
+    keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+    first = np.ascontiguousarray(fault_first, dtype=np.int64).reshape(-1)
+    where = np.ascontiguousarray(fault_location, dtype=np.int32).reshape(-1)
+    kind = np.ascontiguousarray(fault_kind, dtype=np.uint8).reshape(-1)
+    count = len(first) - 1
+    if count < 0 or len(where) != len(kind) or (count >= 0 and len(first) and int(first[-1]) != len(where)):
+        raise ValueError("fault_first has one entry per sample and one more, the last the number of faults")
+    out = np.zeros((max(1, count), max(1, int(ldw))), dtype="<u8")
+    check(lib().gf2_stream_words_host(*seq, _ptr(first), _ptr(where) if len(where) else None, _ptr(kind) if len(where) else None, count,
+                                      _ptr(out), int(ldw)))
+    return out[:count]
+
+
+def stream_tally_host(words, block_kind, flag_words, r1, keys1, flips1, r2, keys2, flips2, classes=False):
+    """gf2_stream_tally_host (host code, no GPU): the twelve counts of the streamed tally rule over stream-layout words (count, ldw).
+    classes=True also returns the class byte of every sample."""
+    words = np.ascontiguousarray(words, dtype="<u8")
+    if words.ndim != 2:
+        raise ValueError("words must be (samples, ldw)")
+    kinds = np.ascontiguousarray(block_kind, dtype=np.int32).reshape(-1)
+    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+    counts = np.zeros(STREAM_FIELDS_COUNT, dtype=np.uint64)
+    cls = np.zeros(max(1, len(words)), dtype=np.uint8)
+    check(lib().gf2_stream_tally_host(_ptr(words) if len(words) else None, len(words), words.shape[1], _ptr(kinds), len(kinds), int(flag_words),
+                                      int(r1), *t1, int(r2), *t2, _ptr(counts), _ptr(cls) if classes else None))
     return (counts, cls[:len(words)]) if classes else counts
 
 
@@ -637,6 +692,29 @@ class Circuit(object):
         try:
             if self.handle and self.ctx.handle:
                 lib().gf2_circuit_destroy(self.ctx.handle, self.handle)
+        except Exception:
+            pass
+
+
+class Stream(object):
+    """A block sequence on the device (gf2_stream_create): the block types' tables (locations of all types, 2, 3) and the blocks."""
+
+    def __init__(self, ctx, type_eff, type_locations, type_flags, block_type, block_kind):
+        self.ctx = ctx
+        keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+        out = ctypes.c_void_p()
+        check(lib().gf2_stream_create(ctx.handle, *seq, ctypes.byref(out)))
+        self.handle = out.value
+
+    def free(self):
+        if self.handle:
+            check(lib().gf2_stream_destroy(self.ctx.handle, self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            if self.handle and self.ctx.handle:
+                lib().gf2_stream_destroy(self.ctx.handle, self.handle)
         except Exception:
             pass
 
@@ -940,6 +1018,20 @@ class Context(object):
         counts = np.zeros(FT_FIELDS_COUNT, dtype=np.uint64)
         check(lib().gf2_mc_ft_decode(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2), *t2,
                                      seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, _ptr(counts)))
+        return counts
+
+    def stream_create(self, type_eff, type_locations, type_flags, block_type, block_kind):
+        return Stream(self, type_eff, type_locations, type_flags, block_type, block_kind)
+
+    def stream_outcomes_dev(self, stream, seed, first, count, p_x, p_y, p_z, out_buf, ldo):
+        check(lib().gf2_stream_outcomes_dev(self.handle, stream.handle, seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, out_buf.ptr, ldo))
+
+    def mc_stream_decode(self, stream, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z):
+        """gf2_mc_stream_decode: the twelve counts of the streamed tally over samples [first, first + count)."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        counts = np.zeros(STREAM_FIELDS_COUNT, dtype=np.uint64)
+        check(lib().gf2_mc_stream_decode(self.handle, stream.handle, int(r1), *t1, int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF, first, count,
+                                         p_x, p_y, p_z, _ptr(counts)))
         return counts
 
     def mc_circuit_decode_strata(self, circ, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x, k_y, k_z):

@@ -883,3 +883,259 @@ int gf2_ft_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t l
 }
 
 }  // extern "C"
+
+// ---- streamed gadgets (include/gf2hip.h "streamed gadgets") -------------------------------------------
+#include "gf2_stream_plan.h"
+
+int gf2_stream_plan(const char* who, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                    const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, StreamPlan* plan) {
+    if (!type_eff || !type_locations || !type_flags || !block_type || !block_kind || !plan) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (ntypes < 1 || ntypes > GF2_STREAM_MAX_TYPES)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= ntypes <= %d block types, got %lld", who, GF2_STREAM_MAX_TYPES, (long long)ntypes);
+    if (nblocks < 1 || nblocks > GF2_CIRCUIT_MAX_LOCATIONS + 1)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= nblocks <= %d blocks, got %lld", who, GF2_CIRCUIT_MAX_LOCATIONS + 1, (long long)nblocks);
+    try {
+        plan->type_offset.assign((size_t)ntypes, 0);
+        plan->start.assign((size_t)nblocks + 1, 0);
+        plan->step.assign((size_t)nblocks, -1);
+        plan->flag.assign((size_t)nblocks, 0);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    int64_t table = 0;
+    for (int64_t t = 0; t < ntypes; ++t) {
+        if (type_locations[t] < 1 || type_locations[t] > GF2_CIRCUIT_MAX_LOCATIONS)
+            GF2_FAIL(GF2_E_ARG, "%s: block type %lld needs 1 <= locations <= %d (2^20), got %lld", who, (long long)t, GF2_CIRCUIT_MAX_LOCATIONS,
+                     (long long)type_locations[t]);
+        if (type_flags[t] < 0 || type_flags[t] > 64)
+            GF2_FAIL(GF2_E_ARG, "%s: block type %lld has %lld flag rows, a block holds at most 64 (one flag word)", who, (long long)t,
+                     (long long)type_flags[t]);
+        plan->type_offset[(size_t)t] = table;
+        table += type_locations[t];
+        if (table > GF2_CIRCUIT_MAX_LOCATIONS)
+            GF2_FAIL(GF2_E_ARG, "%s: the block types have more than %d (2^20) locations in all", who, GF2_CIRCUIT_MAX_LOCATIONS);
+    }
+    // OR of every type's three words
+    std::vector<uint64_t> any;
+    try {
+        any.assign((size_t)ntypes * 3, 0);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    for (int64_t t = 0; t < ntypes; ++t)
+        for (int64_t i = 0; i < 2 * type_locations[t]; ++i)
+            for (int q = 0; q < 3; ++q) any[(size_t)(3 * t + q)] |= type_eff[(2 * plan->type_offset[(size_t)t] + i) * 3 + q];
+    plan->any_tail = 0;
+    for (int k = 0; k < 4; ++k) plan->any_local[k] = 0;
+    int64_t at = 0, steps = 0, rows = 0, trials = 0, finals = 0;
+    for (int64_t b = 0; b < nblocks; ++b) {
+        const int kind = block_kind[b];
+        if (kind < GF2_STREAM_NONE || kind > GF2_STREAM_FINAL)
+            GF2_FAIL(GF2_E_ARG, "%s: block %lld has kind %d, not NONE (0), EC (1), MEASURE (2) or FINAL (3)", who, (long long)b, kind);
+        plan->start[(size_t)b] = (int32_t)at;
+        plan->flag[(size_t)b] = (int32_t)rows;
+        if (kind != GF2_STREAM_NONE) plan->step[(size_t)b] = (int32_t)steps++;
+        if (kind == GF2_STREAM_FINAL) {
+            if (b != nblocks - 1) GF2_FAIL(GF2_E_ARG, "%s: the FINAL step must be the last step, block %lld of %lld is one", who, (long long)b, (long long)nblocks);
+            if (block_type[b] != -1) GF2_FAIL(GF2_E_ARG, "%s: the FINAL step has no locations, its block type must be -1", who);
+            finals += 1;
+            continue;
+        }
+        const int64_t t = block_type[b];
+        if (t < 0 || t >= ntypes) GF2_FAIL(GF2_E_ARG, "%s: block %lld has type %lld outside [0, %lld)", who, (long long)b, (long long)t, (long long)ntypes);
+        trials += kind == GF2_STREAM_MEASURE;
+        at += type_locations[t];
+        rows += type_flags[t];
+        if (at > GF2_CIRCUIT_MAX_LOCATIONS)
+            GF2_FAIL(GF2_E_ARG, "%s: the sequence has more than L = %d (2^20) fault locations", who, GF2_CIRCUIT_MAX_LOCATIONS);
+        plan->any_local[kind] |= any[(size_t)(3 * t)];
+        plan->any_tail |= any[(size_t)(3 * t + 1)];
+        if (type_flags[t] < 64 && (any[(size_t)(3 * t + 2)] >> type_flags[t]) != 0)
+            GF2_FAIL(GF2_E_ARG, "%s: the effects of block type %lld set flag bits at or above its %lld flag rows", who, (long long)t, (long long)type_flags[t]);
+    }
+    plan->start[(size_t)nblocks] = (int32_t)at;
+    if (at < 1) GF2_FAIL(GF2_E_ARG, "%s: the sequence has no fault location", who);
+    if (!finals && trials % 2 == 0)
+        GF2_FAIL(GF2_E_ARG, "%s: a sequence needs one FINAL step as its last step, or an odd number of MEASURE steps (a majority vote) and no FINAL step; "
+                 "it has no FINAL step and %lld MEASURE steps", who, (long long)trials);
+    plan->locations = at;
+    plan->nsteps = steps;
+    plan->flag_rows = rows;
+    plan->flag_words = rows > 64 ? (rows + 63) / 64 : 1;
+    plan->trials = trials;
+    plan->has_final = finals != 0;
+    return GF2_OK;
+}
+
+int gf2_stream_check_bits(const char* who, const StreamPlan& plan, int64_t r1, int64_t r2) {
+    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
+    const uint64_t key_x = (1ull << r2) - 1, keys = key_x | ((1ull << r1) - 1) << 32;
+    if (plan.any_local[GF2_STREAM_NONE] || (plan.any_local[GF2_STREAM_EC] & ~keys) || (plan.any_local[GF2_STREAM_MEASURE] & ~(key_x | 1ull << 31)) ||
+        (plan.any_tail & ~(keys | 1ull << 31 | 1ull << 63)))
+        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (a NONE block no local bit, an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key "
+                 "bits and bit 31, a tail's key bits and the two parity bits)", who);
+    return GF2_OK;
+}
+
+namespace {
+// One sample of the streamed tally rule: gf2_ec_tally_host's and gf2_ft_tally_host's per-sample rules, the steps' kinds read from a
+// list and no bound on their number.  w: the sample's stream-layout words.
+uint8_t stream_tally_sample(const uint64_t* w, const std::vector<int>& kinds, int64_t flag_words, int64_t trials, const uint64_t* mask,
+                            const HostTable* tab, uint64_t* counts) {
+    const int64_t nsteps = (int64_t)kinds.size();
+    uint64_t flags = 0;
+    for (int64_t q = 0; q < flag_words; ++q) flags |= w[nsteps + q];
+    if (flags) return 0;
+    uint64_t K[2] = {0, 0}, P[2] = {0, 0}, unmatched[2] = {0, 0};
+    int64_t wrong_trials = 0, seen_trials = 0;
+    bool first_wrong = false, flip[2] = {false, false}, miss[2] = {false, false};
+    for (int64_t s = 0; s < nsteps; ++s) {
+        const int kind = kinds[(size_t)s];
+        if (kind == GF2_STREAM_FINAL) {
+            for (int c = 0; c < 2; ++c) {
+                const uint64_t v = ((w[s] >> (32 * c)) & mask[c]) ^ K[c];
+                const int found = tab[c].find(0, v);
+                miss[c] = found < 0;
+                flip[c] = (((w[s] >> (32 * c + 31)) & 1ull) ^ P[c] ^ (uint64_t)(found > 0)) != 0;
+            }
+            continue;
+        }
+        const bool measure = kind == GF2_STREAM_MEASURE;
+        for (int c = 0; c < (measure ? 1 : 2); ++c) {
+            const uint64_t v = ((w[s] >> (32 * c)) & mask[c]) ^ K[c];
+            const int found = tab[c].find(0, v);
+            if (found < 0)
+                unmatched[c] += 1;                                       // css_code.py:655-657: no match, nothing recorded
+            else
+                K[c] ^= v, P[c] ^= (uint64_t)found;
+        }
+        if (measure) {
+            const bool bad = (((w[s] >> 31) & 1ull) ^ P[0]) != 0;
+            if (seen_trials == 0) first_wrong = bad;
+            wrong_trials += bad;
+            seen_trials += 1;
+        }
+    }
+    const bool wrong = 2 * wrong_trials > trials, split = wrong_trials != 0 && wrong_trials != trials;
+    counts[0] += 1;
+    counts[1] += flip[0];
+    counts[2] += flip[1];
+    counts[3] += flip[0] | flip[1];
+    counts[4] += miss[0];
+    counts[5] += miss[1];
+    counts[6] += unmatched[0];
+    counts[7] += unmatched[1];
+    counts[8] += wrong;
+    counts[9] += (uint64_t)wrong_trials;
+    counts[10] += first_wrong;
+    counts[11] += split;
+    return (uint8_t)(1 | flip[0] << 1 | flip[1] << 2 | miss[0] << 3 | miss[1] << 4 | wrong << 5 | first_wrong << 6 | split << 7);
+}
+}  // namespace
+
+extern "C" {
+
+// The definition of gf2_stream_outcomes_dev's words given a sample's faults, serial: the faults are XOR-ed
+// into (local, tail, flags) of their blocks, then the blocks are closed in order -- word = mask_kind(T) ^ local, T ^= tail.
+int gf2_stream_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                          const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* fault_first,
+                          const int32_t* fault_location, const uint8_t* fault_kind, int64_t count, uint64_t* words_out, int64_t ldw) {
+    const char* who = "gf2_stream_words_host";
+    StreamPlan plan;
+    if (int rc = gf2_stream_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, &plan)) return rc;
+    const int64_t ldr = plan.nsteps + plan.flag_words;
+    if (count < 0 || ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: needs count >= 0 samples of ldw >= nsteps + F = %lld words", who, (long long)ldr);
+    if (count == 0) return GF2_OK;
+    if (!fault_first || !words_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (fault_first[0] != 0) GF2_FAIL(GF2_E_ARG, "%s: fault_first[0] must be 0", who);
+    for (int64_t i = 0; i < count; ++i)
+        if (fault_first[i + 1] < fault_first[i]) GF2_FAIL(GF2_E_ARG, "%s: fault_first must not descend (sample %lld)", who, (long long)i);
+    const int64_t nfaults = fault_first[count];
+    if (nfaults > 0 && (!fault_location || !fault_kind)) GF2_FAIL(GF2_E_ARG, "%s: null fault list", who);
+    for (int64_t f = 0; f < nfaults; ++f) {
+        if (fault_location[f] < 0 || fault_location[f] >= plan.locations)
+            GF2_FAIL(GF2_E_ARG, "%s: fault %lld is at location %lld outside [0, L = %lld)", who, (long long)f, (long long)fault_location[f], (long long)plan.locations);
+        if (fault_kind[f] < 1 || fault_kind[f] > 3) GF2_FAIL(GF2_E_ARG, "%s: fault %lld has kind %d, not 1 (X), 2 (Z) or 3 (Y)", who, (long long)f, (int)fault_kind[f]);
+    }
+    std::vector<uint64_t> acc;
+    try {
+        acc.assign((size_t)nblocks * 3, 0);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    for (int64_t i = 0; i < count; ++i) {
+        uint64_t* out = words_out + i * ldw;
+        for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
+        for (int64_t f = fault_first[i]; f < fault_first[i + 1]; ++f) {
+            const int32_t g = fault_location[f];
+            const int64_t b = (std::upper_bound(plan.start.begin(), plan.start.end(), g) - plan.start.begin()) - 1;   // start[b] <= g < start[b + 1]
+            const uint64_t* e = type_eff + (size_t)(plan.type_offset[(size_t)block_type[b]] + (g - plan.start[(size_t)b])) * 6;
+            for (int comp = 0; comp < 2; ++comp)
+                if (fault_kind[f] >> comp & 1)
+                    for (int q = 0; q < 3; ++q) acc[(size_t)(3 * b + q)] ^= e[3 * comp + q];
+        }
+        uint64_t T = 0;
+        for (int64_t b = 0; b < nblocks; ++b) {
+            uint64_t* a = &acc[(size_t)(3 * b)];
+            if (plan.step[(size_t)b] >= 0) out[plan.step[(size_t)b]] = (T & gf2_stream_frame_mask(block_kind[b])) ^ a[0];
+            if (a[2]) {
+                const int64_t row = plan.flag[(size_t)b];
+                out[plan.nsteps + (row >> 6)] |= a[2] << (row & 63);
+                if (row & 63) {
+                    const uint64_t over = a[2] >> (64 - (row & 63));
+                    if (over) out[plan.nsteps + (row >> 6) + 1] |= over;
+                }
+            }
+            T ^= a[1];
+            a[0] = a[1] = a[2] = 0;
+        }
+    }
+    return GF2_OK;
+}
+
+// The tally rule of a streamed gadget over stream-layout words, serial: gf2_ec_tally_host's and
+// gf2_ft_tally_host's rules step by step, the kinds of the steps taken from the block kinds.
+int gf2_stream_tally_host(const uint64_t* words, int64_t count, int64_t ldw, const int32_t* block_kind, int64_t nblocks, int64_t flag_words,
+                          int64_t r1, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                          const uint8_t* flips2, int64_t entries2, uint64_t* counts_out, uint8_t* class_out) {
+    const char* who = "gf2_stream_tally_host";
+    if (!counts_out || !block_kind) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
+    if (nblocks < 1 || nblocks > GF2_CIRCUIT_MAX_LOCATIONS + 1)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= nblocks <= %d blocks, got %lld", who, GF2_CIRCUIT_MAX_LOCATIONS + 1, (long long)nblocks);
+    std::vector<int> kinds;
+    int64_t trials = 0, finals = 0;
+    try {
+        for (int64_t b = 0; b < nblocks; ++b) {
+            const int kind = block_kind[b];
+            if (kind < GF2_STREAM_NONE || kind > GF2_STREAM_FINAL)
+                GF2_FAIL(GF2_E_ARG, "%s: block %lld has kind %d, not NONE (0), EC (1), MEASURE (2) or FINAL (3)", who, (long long)b, kind);
+            if (kind == GF2_STREAM_FINAL && b != nblocks - 1)
+                GF2_FAIL(GF2_E_ARG, "%s: the FINAL step must be the last step, block %lld of %lld is one", who, (long long)b, (long long)nblocks);
+            trials += kind == GF2_STREAM_MEASURE;
+            finals += kind == GF2_STREAM_FINAL;
+            if (kind != GF2_STREAM_NONE) kinds.push_back(kind);
+        }
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    if (!finals && trials % 2 == 0)
+        GF2_FAIL(GF2_E_ARG, "%s: a sequence needs one FINAL step as its last step, or an odd number of MEASURE steps (a majority vote) and no FINAL step; "
+                 "it has no FINAL step and %lld MEASURE steps", who, (long long)trials);
+    const int64_t ldr = (int64_t)kinds.size() + flag_words;
+    if (flag_words < 1) GF2_FAIL(GF2_E_ARG, "%s: needs F >= 1 flag words, got %lld", who, (long long)flag_words);
+    if (count < 0 || ldw < ldr || (count > 0 && !words)) GF2_FAIL(GF2_E_ARG, "%s: needs count >= 0 samples of ldw >= nsteps + F = %lld words", who, (long long)ldr);
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    for (int k = 0; k < GF2_STREAM_FIELDS; ++k) counts_out[k] = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    for (int64_t i = 0; i < count; ++i) {
+        const uint8_t cls = stream_tally_sample(words + i * ldw, kinds, flag_words, trials, mask, tab, counts_out);
+        if (class_out) class_out[i] = cls;
+    }
+    return GF2_OK;
+}
+
+}  // extern "C"

@@ -446,6 +446,22 @@ class CSSCode(QECC):
         from . import ft_noise
         return ft_noise.program_for(self, ops).single_faults()
 
+    # -- build-defined: both gadgets at any length, block by block (stream_noise.py; DESIGN.md "Streamed gadgets") ---------------
+    def error_correct_streamed_error_rates(self, num_samples, p_x, p_y, p_z, rounds, seed=0, first_sample=0, idle_data=False):
+        """[build-defined]  error_correct_logical_error_rates for any number of rounds (L = rounds L_b <= 2^20 locations): the same
+        samples, the same tally and the same dict, computed block by block (stream_noise.StreamedGadget.cycle), so time and memory
+        are linear in `rounds`.  Acceptance falls like exp(-c p rounds): long runs are for p <~ 1e-4."""
+        from . import stream_noise
+        gadget = stream_noise.stream_for(self, "cycle", (int(rounds), bool(idle_data)))
+        return gadget.error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample)
+
+    def logical_program_streamed_error_rates(self, ops, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """[build-defined]  logical_program_error_rates for any number of logical gates and trials, likewise
+        (stream_noise.StreamedGadget.program)."""
+        from . import ft_noise, stream_noise
+        gadget = stream_noise.stream_for(self, "program", ft_noise.check_ops(ops))
+        return gadget.error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample)
+
 
 # -- free functions -----------------------------------------------------------------------------------------
 

@@ -1,0 +1,277 @@
+"""
+Streamed gadgets: error-correction cycles and rewritten programs of any length, block by block [build-defined; DESIGN.md "Streamed
+gadgets"].
+
+ec_noise.py and ft_noise.py keep one dense effect table for a whole gadget and one sample's outcome words in registers, which stops
+the cycle at 6 rounds and a program at 7 logical gates.  This module is a third route beside them, for the questions those sizes
+cannot ask: the logical error per round over tens to thousands of rounds, the cost of a long program.  Nothing of the two resident
+routes changes.
+
+Both ancilla blocks are RESET at the start of every preparation, so only the data block survives from one BLOCK of a gadget -- the
+first preparation, a round of error_correct (with the physical Paulis of a logical gate or the idle locations before it), a trial of
+the logical measurement -- to the next.  A fault inside a block acts through three words, BlockType.effects[l, c]:
+    local   what it flips of its own block's measured word (an EC step: key_x in bits 0 .. r_2 - 1, key_z in bits 32 ..; a MEASURE
+            step: key_x and, in bit 31, the measured z_operator parity)
+    tail    what it leaves on the data frame at the block's end (key_x, z_operator . e_x in bit 31, key_z from bit 32,
+            x_operator . e_z in bit 63: the final-frame word of ec_noise's layout)
+    flags   what it flips of its own block's verifications, in measurement order (at most 64 rows)
+and they come from gf2_circuit_effects_timed on the block's own gate list at ldr = 3.  With T = 0 at the start, block after block:
+its step word is mask_kind(T) ^ (XOR of its faults' local words), then T ^= (XOR of their tail words).  A cycle ends with a FINAL step,
+a pseudo-block of no locations whose word is T itself.  At most seven block types occur, whatever the length.
+
+Stream layout of a sample's words: [step 0 .. nsteps - 1] [flag words: the flag rows of all blocks in order, 64 per word, at least
+one word]; to_cycle_layout / to_program_layout permute them into ec_noise's and ft_noise's layouts.  The sampler, the fault location
+numbering (the blocks' locations one after the other: that of error_correct_gates / program_gates) and the tally rules are the
+resident routes', so sample i is the same sample on all of them.
+
+Acceptance falls like exp(-c p rounds): every preparation is post-selected, roughly 200 locations per Steane round reject the
+sample when they fail, so a run of `rounds` rounds keeps about exp(-200 p_kind rounds) of its samples.  Long runs are for p <~ 1e-4.
+"""
+import numpy as np
+
+from . import _native
+from . import circuit_noise
+from . import ec_noise
+from . import ft_noise
+from .ec_noise import GATE_CNOT, GATE_IDLE, ROW_FINAL, ROW_ROUND
+
+NONE, EC, MEASURE, FINAL = _native.STREAM_NONE, _native.STREAM_EC, _native.STREAM_MEASURE, _native.STREAM_FINAL
+STREAM_FIELDS = ('accepted', 'logical_x', 'logical_z', 'logical_any', 'uncorrectable_x', 'uncorrectable_z', 'unmatched_x', 'unmatched_z',
+                 'wrong', 'trial_wrong', 'first_trial_wrong', 'split_vote')
+MAX_FLAG_ROWS = 64
+_BIT31, _BIT63 = np.uint64(1 << 31), np.uint64(1 << 63)
+FRAME_MASK = {NONE: np.uint64(0), EC: ~(_BIT31 | _BIT63), MEASURE: np.uint64(0xFFFFFFFF), FINAL: ~np.uint64(0)}   # what a step reads of T
+# the fields of the two resident routes, as indices into STREAM_FIELDS
+_CYCLE_FIELDS = (0, 1, 2, 3, 4, 5, 6, 7)
+_PROGRAM_FIELDS = (0, 8, 9, 10, 11, 6, 7)
+
+
+class BlockType(object):
+    """One type of block: `name`, `kind` (NONE, EC or MEASURE), its gate list `gates` (g, 3) int32 on 3n qubits, `locations` (L_b, 2)
+    rows (gate, qubit), `num_flags` flag rows and `effects` (L_b, 2, 3) uint64: (local, tail, flags) of an X and of a Z fault."""
+
+    def __init__(self, code, name, kind, emit):
+        build = ec_noise.GadgetBuilder(code)
+        emit(build)
+        end, data, r_1, r_2 = len(build.gates), build.data, build.r_1, build.r_2
+        for i in range(r_2):                                        # word 1: the data frame at the block's end (error_correct_gates' final frame)
+            build.rows.append((64 + r_2 - 1 - i, ROW_FINAL, 0, end, data, 0, build.h_2[i]))
+        build.rows.append((64 + 31, ROW_FINAL, 0, end, data, 0, build.z_op[0]))
+        for i in range(r_1):
+            build.rows.append((64 + 32 + r_1 - 1 - i, ROW_FINAL, 0, end, data, 1, build.h_1[i]))
+        build.rows.append((64 + 63, ROW_FINAL, 0, end, data, 1, build.x_op[0]))
+        self.name, self.kind, self.num_flags = name, kind, build.num_flags
+        if self.num_flags > MAX_FLAG_ROWS:
+            raise ValueError("a block (%s) has %d flag rows (an EC block 2 (r_1 + r_2) + 2), more than the %d one flag word holds"
+                             % (name, self.num_flags, MAX_FLAG_ROWS))
+        gates, rows_x, rows_z, row_time, _, _, _ = build.arrays(3, 2)
+        self.gates = gates
+        self.effects, self.locations = _native.circuit_effects_timed(gates, 3 * build.n, _native.pack_rows(rows_x), _native.pack_rows(rows_z),
+                                                                     row_time, ldr=3)
+
+    @property
+    def num_locations(self):
+        return len(self.locations)
+
+
+def _emit_prepare(build):
+    build.prep(build.data, 'zero', 0, verifier=build.anc_1)        # ftqc.py:78
+
+
+def _emit_ec(qubits):
+    """A round of error_correct after one IDLE location on each of the data block's `qubits` (a logical gate's physical Paulis, or
+    idle_data's locations)."""
+    def emit(build):
+        build.gates.extend((GATE_IDLE, build.data[q], 0) for q in qubits)
+        build.error_correct(1, 0)
+    return emit
+
+
+def _emit_measure(build):
+    r_2 = build.r_2
+    build.prep(build.anc_1, 'zero', 1)                              # css_code.py:629
+    build.gates.extend((GATE_CNOT, d, a) for d, a in zip(build.data, build.anc_1))
+    build.measure(build.anc_1, np.concatenate([build.h_2, build.z_op[:1]]), ROW_ROUND, 1, [r_2 - 1 - i for i in range(r_2)] + [31])
+
+
+class StreamedGadget(object):
+    """A sequence of blocks prepared for the Monte-Carlo: `types` (BlockType), `block_type` (index into types, -1 for the FINAL step)
+    and `block_kind` per block; `block_start`, `block_step`, `block_flag`: a block's first location, its step (-1: none) and its
+    first flag row; `nsteps`, `flag_rows`, `flag_words` and `ldw` = nsteps + flag_words, the words of a sample in the stream layout.
+    Made by StreamedGadget.cycle or StreamedGadget.program."""
+
+    def __init__(self, code, what, types, block_type, block_kind):
+        self.code, self.what, self.types = code, what, list(types)
+        self.block_type = np.array(block_type, dtype=np.int32)
+        self.block_kind = np.array(block_kind, dtype=np.int32)
+        sizes = np.array([0 if t < 0 else self.types[t].num_locations for t in block_type], dtype=np.int64)
+        flags = np.array([0 if t < 0 else self.types[t].num_flags for t in block_type], dtype=np.int64)
+        self.block_start = np.concatenate([[0], np.cumsum(sizes)])
+        self.block_flag = np.concatenate([[0], np.cumsum(flags)])[:-1]
+        has_step = self.block_kind != NONE
+        self.block_step = np.where(has_step, np.cumsum(has_step) - 1, -1)
+        self.num_locations = int(self.block_start[-1])
+        self.nsteps = int(has_step.sum())
+        self.flag_rows = int(flags.sum())
+        self.flag_words = max(1, (self.flag_rows + 63) // 64)
+        self.ldw = self.nsteps + self.flag_words
+        self.trials = int((self.block_kind == MEASURE).sum())
+        if not 1 <= self.num_locations <= circuit_noise.MAX_LOCATIONS:
+            raise ValueError("the Monte-Carlo needs 1 <= L <= %d (2^20) fault locations, the %s has %d"
+                             % (circuit_noise.MAX_LOCATIONS, what, self.num_locations))
+        self.type_eff = np.ascontiguousarray(np.concatenate([t.effects for t in self.types]))
+        self.type_locations = np.array([t.num_locations for t in self.types], dtype=np.int64)
+        self.type_flags = np.array([t.num_flags for t in self.types], dtype=np.int64)
+        self._device = None
+
+    @classmethod
+    def cycle(cls, code, rounds, idle_data=False):
+        """`rounds` rounds of CSSCode.error_correct (ec_noise.error_correct_gates' gadget; idle_data: one IDLE per data qubit at the
+        start of each round), then the FINAL step.  Any rounds >= 1 with L = rounds L_b <= 2^20."""
+        rounds = int(rounds)
+        if rounds < 1:
+            raise ValueError("the error-correction cycle needs rounds >= 1")
+        block = BlockType(code, "EC, idle data" if idle_data else "EC", EC, _emit_ec(range(int(code.n)) if idle_data else ()))
+        out = cls(code, "cycle", [block], [0] * rounds + [-1], [EC] * rounds + [FINAL])
+        out.rounds = rounds
+        return out
+
+    @classmethod
+    def program(cls, code, ops):
+        """The rewritten program `ops; MEASURE` (ft_noise.program_gates' block sequence: the first preparation, an EC block per logical
+        gate, then 2t + 1 times a MEASURE trial and an EC block).  Any number of gates; ft_noise.check_ops' refusals."""
+        ops = ft_noise.check_ops(ops)
+        types, index = [], {}
+
+        def use(name, kind, emit):
+            if name not in index:
+                index[name] = len(types)
+                types.append(BlockType(code, name, kind, emit))
+            return index[name]
+
+        ec = lambda op: use("EC" if op == 'I' else "logical %s, EC" % op, EC, _emit_ec(ft_noise.logical_pauli_qubits(code, op)))
+        block_type, block_kind = [use("prepare data", NONE, _emit_prepare)], [NONE]
+        for op in ops:                                              # ftqc.py:80-83
+            block_type.append(ec(op))
+            block_kind.append(EC)
+        for _ in range(2 * int(code.t) + 1):                        # ftqc.py:84-89, css_code.py:576-579
+            block_type += [use("MEASURE trial", MEASURE, _emit_measure), ec('I')]
+            block_kind += [MEASURE, EC]
+        out = cls(code, "program", types, block_type, block_kind)
+        out.ops = ops
+        return out
+
+    # -- the whole gadget, as the resident routes see it ---------------------------------------------------------------------
+    def gates(self):
+        """The gate list of the whole sequence: error_correct_gates' / program_gates'."""
+        return np.concatenate([self.types[t].gates for t in self.block_type if t >= 0])
+
+    def locations(self):
+        """(L, 2) rows (gate, qubit) of the whole sequence's fault locations, the blocks' one after the other."""
+        parts, first_gate = [], 0
+        for t in self.block_type:
+            if t >= 0:
+                parts.append(self.types[t].locations + np.array([first_gate, 0]))
+                first_gate += len(self.types[t].gates)
+        return np.concatenate(parts)
+
+    def dense_effects(self):
+        """The dense effect table (L, 2, ldw) of the whole sequence in the stream layout, rebuilt from the block tables: a fault's
+        local word in its own step, its tail under every later step's mask, its flags among its block's flag rows."""
+        out = np.zeros((self.num_locations, 2, self.ldw), dtype=np.uint64)
+        steps = self.block_step
+        masks = np.array([FRAME_MASK[int(k)] for k in self.block_kind[steps >= 0]], dtype=np.uint64)
+        for b, t in enumerate(self.block_type):
+            if t < 0:
+                continue
+            eff = self.types[t].effects
+            rows = slice(int(self.block_start[b]), int(self.block_start[b + 1]))
+            if steps[b] >= 0:
+                out[rows, :, steps[b]] = eff[:, :, 0]
+            later = int(steps[b + 1:].max(initial=-1))
+            first = int(steps[b]) + 1 if steps[b] >= 0 else int((steps[:b] >= 0).sum())
+            if later >= first:
+                out[rows, :, first:later + 1] = eff[:, :, 1, None] & masks[first:later + 1]
+            word, shift = divmod(int(self.block_flag[b]), 64)
+            out[rows, :, self.nsteps + word] |= eff[:, :, 2] << np.uint64(shift)
+            if shift and word + 1 < self.flag_words:
+                out[rows, :, self.nsteps + word + 1] |= eff[:, :, 2] >> np.uint64(64 - shift)
+        return out
+
+    def to_cycle_layout(self, words):
+        """Stream-layout words (.., ldw) of a cycle as ec_noise's [final frame] [round 1 .. rounds] [flag words]."""
+        if self.what != "cycle":
+            raise ValueError("not a cycle")
+        words = np.asarray(words)
+        order = [self.nsteps - 1] + list(range(self.nsteps - 1)) + list(range(self.nsteps, self.ldw))
+        return np.ascontiguousarray(words[..., order])
+
+    def to_program_layout(self, words):
+        """Stream-layout words (.., ldw) of a program as ft_noise's [step 0 .. nsteps - 1] [flag words]: the same order."""
+        if self.what != "program":
+            raise ValueError("not a program")
+        return np.ascontiguousarray(np.asarray(words)[..., :self.ldw])
+
+    # -- the Monte-Carlo -----------------------------------------------------------------------------------------------------
+    def _sequence(self):
+        return self.type_eff, self.type_locations, self.type_flags, self.block_type, self.block_kind
+
+    def device(self):
+        if self._device is None:
+            self._device = _native.default_context().stream_create(*self._sequence())
+        return self._device
+
+    def _tables(self):
+        keys1, flips1, keys2, flips2 = circuit_noise.code_tables(self.code)
+        return self.code.r_1, keys1, flips1, self.code.r_2, keys2, flips2
+
+    def _dict(self, counts, samples):
+        names = ec_noise.EC_FIELDS if self.what == "cycle" else ft_noise.FT_FIELDS
+        out = {name: int(counts[k]) for name, k in zip(names, _CYCLE_FIELDS if self.what == "cycle" else _PROGRAM_FIELDS)}
+        out['samples'] = int(samples)
+        return out
+
+    def outcomes(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """The stream-layout words of samples [first_sample, first_sample + num_samples), rejected ones included: a (num_samples,
+        ldw) uint64 array (gf2_stream_outcomes_dev)."""
+        ctx = _native.default_context()
+        stream = self.device()
+        count = int(num_samples)
+        buf = ctx.alloc(max(1, count) * self.ldw * 8)
+        ctx.stream_outcomes_dev(stream, int(seed), int(first_sample), count, float(p_x), float(p_y), float(p_z), buf, self.ldw)
+        out = buf.download((count, self.ldw), np.uint64)
+        buf.free()
+        return out
+
+    def counts(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """The twelve STREAM_FIELDS counts of samples [first_sample, first_sample + num_samples) on the device (gf2_mc_stream_decode)."""
+        return _native.default_context().mc_stream_decode(self.device(), *self._tables(), int(seed), int(first_sample), int(num_samples),
+                                                          float(p_x), float(p_y), float(p_z))
+
+    def error_rates(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """The tally of samples [first_sample, first_sample + num_samples) on the device: a dict of ec_noise.EC_FIELDS for a cycle, of
+        ft_noise.FT_FIELDS for a program, plus 'samples'; what ECCircuit.logical_error_rates / FTProgram.measurement_error_rates
+        give where they accept the size.  The counts of sample ranges add."""
+        return self._dict(self.counts(num_samples, p_x, p_y, p_z, seed, first_sample), num_samples)
+
+    def words_of_faults(self, fault_first, fault_location, fault_kind):
+        """The stream-layout words of samples given by their faults, on the host (gf2_stream_words_host, no GPU): sample i has faults
+        fault_first[i] .. fault_first[i + 1] - 1, each a location and a kind 1 (X), 2 (Z) or 3 (Y)."""
+        return _native.stream_words_host(*self._sequence(), fault_first, fault_location, fault_kind, self.ldw)
+
+    def tally_host(self, words, classes=False, fields=False):
+        """The tally rule over stream-layout words (samples, ldw) on the host (gf2_stream_tally_host, no GPU): error_rates' dict;
+        fields=True gives the twelve STREAM_FIELDS counts instead, classes=True (result, class byte per sample)."""
+        words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, self.ldw)
+        got = _native.stream_tally_host(words, self.block_kind, self.flag_words, *self._tables(), classes=classes)
+        counts = got[0] if classes else got
+        out = counts if fields else self._dict(counts, len(words))
+        return (out, got[1]) if classes else out
+
+
+def stream_for(code, what, key):
+    """StreamedGadget.cycle(code, *key) or StreamedGadget.program(code, key), cached on the code object."""
+    cache = code.__dict__.setdefault("_streamed_gadgets", {})
+    if (what, key) not in cache:
+        cache[(what, key)] = StreamedGadget.cycle(code, *key) if what == "cycle" else StreamedGadget.program(code, key)
+    return cache[(what, key)]
