@@ -541,6 +541,47 @@ int gf2_ft_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, u
                      const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
                      int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out);
 
+/* ---- exact strata of the two post-selected gadgets under gate-level faults -----------------------------
+ * [build-defined, DESIGN.md section 5e]  The same effect tables, outcome layouts and tally rules, but what fails is a gate, not a
+ * location.  A site is one gate of the gadget's gate list: a one-operand gate (H, IDLE, RESET) with its one location l, or a CNOT
+ * with its two locations l (control) and l + 1 (target).  Sites are numbered with the n_1 one-operand gates first, then the n_2
+ * CNOTs, each in gate order; site_loc[s] is the first location of site s, and the sites partition [0, L): n_1 + 2 n_2 = L.  A kind
+ * is a non-zero mask kappa: 2 bits on a one-operand site (1 = X, 2 = Z, 3 = Y), 4 bits on a CNOT site (bits 0, 1: the control's X
+ * and Z components; bits 2, 3: the target's).  A pick's outcome words are the XOR over the set bits t of
+ * eff[site_loc + (t >> 1)][t & 1].  A CNOT kind is two-operand when both halves of kappa are non-zero (9 of the 15).
+ * A configuration of weight w and CNOT count b is a = w - b distinct one-operand sites, b distinct CNOT sites and a kind per pick
+ * (3^a 15^b per subset), judged by the gadget's tally rule, post-selection included.  rank = r_s + C(n_1, a) r_c with r_s, r_c the
+ * ranks of the one-operand picks among [0, n_1) and of the CNOT picks among [0, n_2) in the combinatorial number system.  A call
+ * covers ranks [first_rank, first_rank + count) of one (w, b), 0 <= b <= w <= GF2_GATE_ENUMERATE_MAX_WEIGHT.
+ * counts_out[(b + 1)][F], F = GF2_EC_FIELDS or GF2_FT_FIELDS: entry [c][field] is the tally of `field` over the configurations of
+ * the range in which exactly c of the b CNOT picks carry a two-operand kind.  Counts of disjoint ranges add.
+ * GF2_E_ARG if C(n_1, a) C(n_2, b) >= 2^63, if count 3^a 15^b >= 2^63, if the range leaves the rank space or if the site table is no
+ * partition of [0, L); layout, table and effect errors as gf2_ec_enumerate_host's / gf2_ft_enumerate_host's.
+ *
+ * The definitions on the host, serial, no GPU needed (they stand for running the gadget once per gate-fault configuration,
+ * css_code.py:436-470 and ftqc.py:76-95 as above). */
+#define GF2_GATE_ENUMERATE_MAX_WEIGHT 4
+int gf2_ec_gate_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                               const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                               int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b, int64_t first_rank,
+                               int64_t count, uint64_t* counts_out);
+int gf2_ft_gate_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                               const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                               const uint8_t* flips2, int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b,
+                               int64_t first_rank, int64_t count, uint64_t* counts_out);
+
+/* The same counts on the device.  Circuit, layout and tables as gf2_ec_enumerate / gf2_ft_enumerate check them; the hash tables and
+ * the device copy of site_loc are made once per call, the range is cut into launches of at most 2^28 configurations, the counts
+ * come back once. */
+int gf2_ec_gate_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                          int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                          const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b, int64_t first_rank, int64_t count,
+                          uint64_t* counts_out);
+int gf2_ft_gate_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, uint64_t measure_mask, int64_t r1, const uint64_t* keys1,
+                          const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                          const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b, int64_t first_rank, int64_t count,
+                          uint64_t* counts_out);
+
 /* ---- malignant fault sets of the two post-selected gadgets ---------------------------------------------
  * [build-defined, DESIGN.md "Malignant fault sets of the cycle" and "Malignant fault sets of the measurement"]  The walk of "exact
  * strata of the two post-selected gadgets" above, unchanged -- ranks [first_rank, first_rank + count) of weight w, all 3^w kind

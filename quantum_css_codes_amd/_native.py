@@ -28,6 +28,7 @@ STREAM_NONE, STREAM_EC, STREAM_MEASURE, STREAM_FINAL = 0, 1, 2, 3
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 ENUMERATE_MAX_WEIGHT = 8
+GATE_ENUMERATE_MAX_WEIGHT = 4                       # GF2_GATE_ENUMERATE_MAX_WEIGHT
 FAULT_RECORD_WORDS, FAULT_LIST_MAX_CAPACITY = 2, 1 << 28       # GF2_FAULT_RECORD_WORDS, GF2_FAULT_LIST_MAX_CAPACITY
 K_SYNDROME, K_HIST, K_SAMPLER, K_ELIM = 0, 1, 2, 3
 # routing flags of a context and its tunables: the few a caller needs are in include/gf2hip.h (F_MC_DENSE, F_RREF_SEQUENTIAL,
@@ -144,6 +145,13 @@ SIGNATURES = {
     "gf2_ft_enumerate_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
     "gf2_ec_enumerate": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
     "gf2_ft_enumerate": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _p],
+    "gf2_ec_gate_enumerate_host": [_p, _c_i64, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
+                                   _c_i64, _p],
+    "gf2_ft_gate_enumerate_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_i64, _c_i64,
+                                   _c_i64, _c_i64, _p],
+    "gf2_ec_gate_enumerate": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _p],
+    "gf2_ft_gate_enumerate": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
+                              _p],
     "gf2_ec_enumerate_list_host": [_p, _c_i64, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64,
                                    _p, ctypes.POINTER(_c_i64)],
     "gf2_ft_enumerate_list_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_u64,
@@ -540,6 +548,40 @@ def ft_enumerate_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, f
     """gf2_ft_enumerate_host (host code, no GPU): the (w + 1, w + 1, 7) counts of the logical measurement's tally rule, likewise."""
     return _gadget_enumerate_host(lib().gf2_ft_enumerate_host, FT_FIELDS_COUNT, eff, (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF),
                                   (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count)
+
+
+def _gate_sites(site_loc, n1, n2):
+    sites = np.ascontiguousarray(site_loc, dtype=np.int32).reshape(-1)
+    if len(sites) != int(n1) + int(n2):
+        raise ValueError("site_loc must have n1 + n2 entries")
+    return sites
+
+
+def _gate_enumerate_host(fn, fields, eff, head, tables, sites, w, b, first_rank, count):
+    eff = np.ascontiguousarray(eff, dtype="<u8")
+    if eff.ndim != 3 or eff.shape[1] != 2:
+        raise ValueError("eff must be (locations, 2, ldr)")
+    r1, keys1, flips1, r2, keys2, flips2 = tables
+    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+    site_loc, n1, n2 = sites
+    site_loc = _gate_sites(site_loc, n1, n2)
+    out = np.zeros((max(0, min(int(b), GATE_ENUMERATE_MAX_WEIGHT)) + 1, fields), dtype=np.uint64)
+    check(fn(_ptr(eff), eff.shape[0], eff.shape[2], *head, int(r1), *t1, int(r2), *t2, _ptr(site_loc), int(n1), int(n2), int(w), int(b),
+             int(first_rank), int(count), _ptr(out)))
+    return out
+
+
+def ec_gate_enumerate_host(eff, rounds, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count):
+    """gf2_ec_gate_enumerate_host (host code, no GPU): the (b + 1, 8) uint64 counts [c][field] of the error-correction cycle's tally
+    rule over the site subsets of ranks [first_rank, first_rank + count) of (w, b), each with all 3^(w - b) 15^b kind assignments."""
+    return _gate_enumerate_host(lib().gf2_ec_gate_enumerate_host, EC_FIELDS_COUNT, eff, (int(rounds),), (r1, keys1, flips1, r2, keys2, flips2),
+                                (site_loc, n1, n2), w, b, first_rank, count)
+
+
+def ft_gate_enumerate_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count):
+    """gf2_ft_gate_enumerate_host (host code, no GPU): the (b + 1, 7) counts of the logical measurement's tally rule, likewise."""
+    return _gate_enumerate_host(lib().gf2_ft_gate_enumerate_host, FT_FIELDS_COUNT, eff, (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF),
+                                (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), w, b, first_rank, count)
 
 
 def _fault_list_call(fn, head, select, capacity, limit=None):
@@ -1090,6 +1132,24 @@ class Context(object):
         out = np.zeros((side, side, FT_FIELDS_COUNT), dtype=np.uint64)
         check(lib().gf2_ft_enumerate(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2), *t2,
                                      int(w), int(first_rank), int(count), _ptr(out)))
+        return out
+
+    def ec_gate_enumerate(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count):
+        """gf2_ec_gate_enumerate: ec_gate_enumerate_host's counts from the device."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        site_loc = _gate_sites(site_loc, n1, n2)
+        out = np.zeros((max(0, min(int(b), GATE_ENUMERATE_MAX_WEIGHT)) + 1, EC_FIELDS_COUNT), dtype=np.uint64)
+        check(lib().gf2_ec_gate_enumerate(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, _ptr(site_loc), int(n1), int(n2),
+                                          int(w), int(b), int(first_rank), int(count), _ptr(out)))
+        return out
+
+    def ft_gate_enumerate(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count):
+        """gf2_ft_gate_enumerate: ft_gate_enumerate_host's counts from the device."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        site_loc = _gate_sites(site_loc, n1, n2)
+        out = np.zeros((max(0, min(int(b), GATE_ENUMERATE_MAX_WEIGHT)) + 1, FT_FIELDS_COUNT), dtype=np.uint64)
+        check(lib().gf2_ft_gate_enumerate(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2),
+                                          *t2, _ptr(site_loc), int(n1), int(n2), int(w), int(b), int(first_rank), int(count), _ptr(out)))
         return out
 
     def ec_enumerate_list(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):

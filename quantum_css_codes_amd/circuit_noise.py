@@ -103,6 +103,39 @@ def gadget_enumerate_request(total, weights, first_rank, count, max_configuratio
     return weights, firsts, counts
 
 
+def gate_sites(gates, locations):
+    """The sites of the gate-level fault model of a gate list whose fault locations are `locations`, (L, 2)
+    rows (gate index, qubit) in location order: (site_loc, n1, n2, site_gate).  The n1 one-operand gates come first, then the n2
+    CNOTs, each in gate order; site_loc[s] (int32) is the first location of site s -- a CNOT's control, its target being
+    site_loc[s] + 1 -- and site_gate[s] its gate index.  The sites partition [0, L): n1 + 2 n2 = L."""
+    gates = _gates(gates)
+    loc_gate = np.asarray(locations, dtype=np.int64).reshape(-1, 2)[:, 0]
+    two = gates[:, 0] == GATE_CNOT
+    if len(loc_gate) and (loc_gate.min() < 0 or loc_gate.max() >= len(gates) or np.any(np.diff(loc_gate) < 0)):
+        raise ValueError("the locations must be in gate order, each on a gate of the list")
+    per_gate = np.bincount(loc_gate, minlength=len(gates))
+    if np.any(per_gate != np.where(two, 2, 1)):
+        raise ValueError("every gate needs its own fault locations: two for a CNOT, one for any other gate")
+    first = np.concatenate(([0], np.cumsum(per_gate)[:-1])).astype(np.int64)
+    site_gate = np.concatenate((np.nonzero(~two)[0], np.nonzero(two)[0])).astype(np.int64)
+    return first[site_gate].astype(np.int32), int(np.count_nonzero(~two)), int(np.count_nonzero(two)), site_gate
+
+
+def gate_enumerate_request(n1, n2, weights, max_configurations, what):
+    """The argument rules of ECCircuit / FTProgram.enumerate_gate_strata: the weights as a list of ints, ValueError for a weight or a
+    size that is refused (the size is named)."""
+    weights = [int(w) for w in np.asarray(weights).reshape(-1)]
+    if any(w < 0 or w > _native.GATE_ENUMERATE_MAX_WEIGHT for w in weights):
+        raise ValueError("a gate-fault stratum's weight lies in [0, %d]" % _native.GATE_ENUMERATE_MAX_WEIGHT)
+    if not 1 <= n1 + 2 * n2 <= MAX_LOCATIONS:
+        raise ValueError("the enumeration needs 1 <= L <= %d (2^20) fault locations, the %s has %d" % (MAX_LOCATIONS, what, n1 + 2 * n2))
+    size = sum(math.comb(n1, w - b) * math.comb(n2, b) * 3**(w - b) * 15**b for w in weights for b in range(w + 1))
+    budget = ENUMERATE_BUDGET if max_configurations is None else int(max_configurations)
+    if size > budget:
+        raise ValueError("%d gate-fault configurations to enumerate, more than max_configurations = %d" % (size, budget))
+    return weights
+
+
 class FaultCircuit(object):
     """
     A gate list on n qubits with outcome rows, prepared for the Monte-Carlo: the effect table (host) and, on first use, its

@@ -627,14 +627,8 @@ int make_host_tables(const char* who, HostTable* tab, const uint64_t* keys1, con
     return GF2_OK;
 }
 
-// The argument rules gf2_ec_enumerate_host and gf2_ec_enumerate_list_host share (eff not null) ...
-int ec_enumerate_check(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
-                       const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
-                       int64_t w, int64_t first_rank, int64_t count) {
-    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
-    if (int rc = ec_check_layout(who, ldr, rounds, r1, r2)) return rc;
-    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
-    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
+// No effect of the cycle's table may set a bit outside the layout (the layout already checked) ...
+int ec_check_effects(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, int64_t r2) {
     const uint64_t keys = ((1ull << r2) - 1) | ((1ull << r1) - 1) << 32;
     uint64_t any[GF2_CIRCUIT_MAX_LDR] = {0};
     for (int64_t i = 0; i < 2 * locations; ++i)
@@ -645,14 +639,9 @@ int ec_enumerate_check(const char* who, const uint64_t* eff, int64_t locations, 
     return GF2_OK;
 }
 
-// ... and those of gf2_ft_enumerate_host and gf2_ft_enumerate_list_host.
-int ft_enumerate_check(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
-                       const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
-                       int64_t entries2, int64_t w, int64_t first_rank, int64_t count) {
-    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
-    if (int rc = ft_check_layout(who, ldr, nsteps, measure_mask, r1, r2)) return rc;
-    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
-    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
+// ... nor one of the measurement's.
+int ft_check_effects(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                     int64_t r2) {
     const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
     uint64_t any[GF2_FT_MAX_LDR] = {0};
     for (int64_t i = 0; i < 2 * locations; ++i)
@@ -663,6 +652,28 @@ int ft_enumerate_check(const char* who, const uint64_t* eff, int64_t locations, 
     if (beyond)
         GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key bits and bit 31)", who);
     return GF2_OK;
+}
+
+// The argument rules gf2_ec_enumerate_host and gf2_ec_enumerate_list_host share (eff not null) ...
+int ec_enumerate_check(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                       const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                       int64_t w, int64_t first_rank, int64_t count) {
+    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
+    if (int rc = ec_check_layout(who, ldr, rounds, r1, r2)) return rc;
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
+    return ec_check_effects(who, eff, locations, ldr, rounds, r1, r2);
+}
+
+// ... and those of gf2_ft_enumerate_host and gf2_ft_enumerate_list_host.
+int ft_enumerate_check(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                       const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                       int64_t entries2, int64_t w, int64_t first_rank, int64_t count) {
+    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
+    if (int rc = ft_check_layout(who, ldr, nsteps, measure_mask, r1, r2)) return rc;
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    if (int rc = gf2_enum_check_range(who, locations, w, first_rank, count)) return rc;
+    return ft_check_effects(who, eff, locations, ldr, nsteps, measure_mask, r1, r2);
 }
 }  // namespace
 
@@ -880,6 +891,146 @@ int gf2_ft_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t l
         uint64_t unused[GF2_FT_FIELDS] = {0};
         return ft_tally_sample(out, ldr, nsteps, measure_mask, trials, mask, tab, unused);
     });
+}
+
+}  // extern "C"
+
+// ---- exact strata under gate-level faults (include/gf2hip.h "gate-level faults") ------------------------
+// The argument rules of a rank range of sites, shared by the host statements below and the device entry points
+// (gf2_gate_enumerate.hip).
+int gf2_gate_check_range(const char* who, int64_t locations, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b,
+                         int64_t first_rank, int64_t count) {
+    if (locations < 1 || locations > GF2_CIRCUIT_MAX_LOCATIONS)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= L <= %d (2^20) locations, got %lld", who, GF2_CIRCUIT_MAX_LOCATIONS, (long long)locations);
+    if (w < 0 || w > GF2_GATE_ENUMERATE_MAX_WEIGHT) GF2_FAIL(GF2_E_ARG, "%s: weight %lld outside [0, %d]", who, (long long)w, GF2_GATE_ENUMERATE_MAX_WEIGHT);
+    if (b < 0 || b > w) GF2_FAIL(GF2_E_ARG, "%s: %lld CNOT picks outside [0, w = %lld]", who, (long long)b, (long long)w);
+    if (!site_loc || n1 < 0 || n2 < 0 || n1 + 2 * n2 != locations)
+        GF2_FAIL(GF2_E_ARG, "%s: the site table is no partition of [0, L): n_1 + 2 n_2 = %lld + 2 * %lld, L = %lld", who, (long long)n1, (long long)n2,
+                 (long long)locations);
+    try {
+        std::vector<uint8_t> seen((size_t)locations, 0);
+        for (int64_t s = 0; s < n1 + n2; ++s) {
+            const int64_t l = site_loc[s], width = s < n1 ? 1 : 2;
+            if (l < 0 || l + width > locations || seen[(size_t)l] || seen[(size_t)(l + width - 1)])
+                GF2_FAIL(GF2_E_ARG, "%s: the site table is no partition of [0, L): site %lld at location %lld", who, (long long)s, (long long)l);
+            seen[(size_t)l] = seen[(size_t)(l + width - 1)] = 1;
+        }
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    const int64_t a = w - b;
+    const unsigned __int128 total = (unsigned __int128)binom_sat(n1, (int)a) * binom_sat(n2, (int)b);
+    if (total >> 63) GF2_FAIL(GF2_E_ARG, "%s: C(%lld, %lld) C(%lld, %lld) subsets do not fit 63 bits", who, (long long)n1, (long long)a, (long long)n2, (long long)b);
+    if (first_rank < 0 || count < 0 || (uint64_t)first_rank > (uint64_t)total || (uint64_t)count > (uint64_t)total - (uint64_t)first_rank)
+        GF2_FAIL(GF2_E_ARG, "%s: ranks [%lld, %lld + %lld) leave the range [0, C(%lld, %lld) C(%lld, %lld) = %llu)", who, (long long)first_rank,
+                 (long long)first_rank, (long long)count, (long long)n1, (long long)a, (long long)n2, (long long)b, (unsigned long long)total);
+    int64_t kinds = 1;
+    for (int64_t k = 0; k < w; ++k) kinds *= k < a ? 3 : 15;
+    if (count > INT64_MAX / kinds)
+        GF2_FAIL(GF2_E_ARG, "%s: %lld subsets of 3^%lld 15^%lld kind assignments do not fit 63 bits", who, (long long)count, (long long)a, (long long)b);
+    return GF2_OK;
+}
+
+namespace {
+// One step of the colexicographic successor of k ascending picks (gadget_walk's).
+void subset_successor(int64_t k, int32_t* pos) {
+    int64_t j = 0;
+    while (j < k - 1 && pos[j] + 1 == pos[j + 1]) pos[j] = (int32_t)j, ++j;
+    pos[j] += 1;
+}
+
+// The walk of a rank range of sites, serial: the first subset unranked part by part (rank = r_s + C(n_1, a) r_c), the others by
+// the successor of the product order (the one-operand part steps; when it wraps, the CNOT part does), every kind assignment by an
+// odometer over [1, 3]^a x [1, 15]^b, the outcome words XOR-ed from scratch and handed to visit(site, kappa, c, out): site[k] and
+// kappa[k] the site and kind mask of pick k (the a one-operand picks first), c the number of two-operand kinds.
+template <class Visit>
+void gate_walk(const uint64_t* eff, int64_t ldr, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b, int64_t first_rank,
+               int64_t count, Visit visit) {
+    const int64_t a = w - b;
+    const uint64_t c1 = binom_sat(n1, (int)a);
+    int32_t ps[GF2_GATE_ENUMERATE_MAX_WEIGHT] = {0}, pc[GF2_GATE_ENUMERATE_MAX_WEIGHT] = {0}, site[GF2_GATE_ENUMERATE_MAX_WEIGHT] = {0};
+    int kappa[GF2_GATE_ENUMERATE_MAX_WEIGHT];
+    subset_unrank(n1, (int)a, (uint64_t)first_rank % c1, ps);
+    subset_unrank(n2, (int)b, (uint64_t)first_rank / c1, pc);
+    for (int64_t i = 0; i < count; ++i) {
+        if (i > 0) {
+            if (a == 0 || ps[0] == n1 - a) {                                // the one-operand part is at its last subset: it wraps
+                for (int64_t k = 0; k < a; ++k) ps[k] = (int32_t)k;
+                subset_successor(b, pc);
+            } else {
+                subset_successor(a, ps);
+            }
+        }
+        for (int64_t k = 0; k < w; ++k) site[k] = k < a ? ps[k] : (int32_t)n1 + pc[k - a], kappa[k] = 1;
+        for (;;) {
+            uint64_t out[GF2_FT_MAX_LDR] = {0};
+            int64_t c = 0;
+            for (int64_t k = 0; k < w; ++k) {
+                for (int bit = 0; bit < 4; ++bit) {
+                    if (!((kappa[k] >> bit) & 1)) continue;
+                    const uint64_t* e = eff + (size_t)(2 * (site_loc[site[k]] + (bit >> 1)) + (bit & 1)) * ldr;
+                    for (int64_t q = 0; q < ldr; ++q) out[q] ^= e[q];
+                }
+                c += (kappa[k] & 3) != 0 && (kappa[k] >> 2) != 0;
+            }
+            visit(site, kappa, c, out);
+            int64_t k = 0;                                                   // odometer over 1 .. 3 or 1 .. 15
+            while (k < w && kappa[k] == (k < a ? 3 : 15)) kappa[k++] = 1;
+            if (k == w) break;
+            kappa[k] += 1;
+        }
+    }
+}
+}  // namespace
+
+extern "C" {
+
+// The definition of gf2_ec_gate_enumerate, serial: gate_walk, every configuration's outcome words judged by
+// gf2_ec_tally_host's per-sample rule.
+int gf2_ec_gate_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                               const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                               int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b, int64_t first_rank,
+                               int64_t count, uint64_t* counts_out) {
+    const char* who = "gf2_ec_gate_enumerate_host";
+    if (!eff || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
+    if (int rc = ec_check_layout(who, ldr, rounds, r1, r2)) return rc;
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    if (int rc = gf2_gate_check_range(who, locations, site_loc, n1, n2, w, b, first_rank, count)) return rc;
+    if (int rc = ec_check_effects(who, eff, locations, ldr, rounds, r1, r2)) return rc;
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    for (int64_t k = 0; k < (b + 1) * GF2_EC_FIELDS; ++k) counts_out[k] = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    gate_walk(eff, ldr, site_loc, n1, n2, w, b, first_rank, count, [&](const int32_t*, const int*, int64_t c, const uint64_t* out) {
+        (void)ec_tally_sample(out, ldr, rounds, mask, tab, counts_out + c * GF2_EC_FIELDS);
+    });
+    return GF2_OK;
+}
+
+// The definition of gf2_ft_gate_enumerate, likewise with gf2_ft_tally_host's rule.
+int gf2_ft_gate_enumerate_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                               const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                               const uint8_t* flips2, int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b,
+                               int64_t first_rank, int64_t count, uint64_t* counts_out) {
+    const char* who = "gf2_ft_gate_enumerate_host";
+    if (!eff || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
+    if (int rc = ft_check_layout(who, ldr, nsteps, measure_mask, r1, r2)) return rc;
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    if (int rc = gf2_gate_check_range(who, locations, site_loc, n1, n2, w, b, first_rank, count)) return rc;
+    if (int rc = ft_check_effects(who, eff, locations, ldr, nsteps, measure_mask, r1, r2)) return rc;
+    const int trials = __builtin_popcountll(measure_mask);
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    for (int64_t k = 0; k < (b + 1) * GF2_FT_FIELDS; ++k) counts_out[k] = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    gate_walk(eff, ldr, site_loc, n1, n2, w, b, first_rank, count, [&](const int32_t*, const int*, int64_t c, const uint64_t* out) {
+        (void)ft_tally_sample(out, ldr, nsteps, measure_mask, trials, mask, tab, counts_out + c * GF2_FT_FIELDS);
+    });
+    return GF2_OK;
 }
 
 }  // extern "C"

@@ -411,6 +411,18 @@ class CSSCode(QECC):
         from . import ec_noise
         return ec_noise.circuit_for(self, rounds).single_faults()
 
+    def error_correct_gate_strata_exact(self, weights, rounds=1, idle_data=False, **options):
+        """The exact strata `weights` of the cycle under gate-level faults, a CNOT failing as one event with one of the 15 two-qubit
+        Paulis (ec_noise.ECCircuit.enumerate_gate_strata): a montecarlo.GateStrata, whose
+        series(('depolarising', 1), 'logical_any') gives the Taylor coefficients of the logical error rate per cycle."""
+        from . import ec_noise
+        return ec_noise.circuit_for(self, rounds, idle_data).enumerate_gate_strata(weights, **options)
+
+    def error_correct_gate_single_faults(self, rounds=1):
+        """[build-defined]  The census of every single gate fault of the cycle, no GPU needed: ECCircuit.gate_single_faults."""
+        from . import ec_noise
+        return ec_noise.circuit_for(self, rounds).gate_single_faults()
+
     # -- build-defined: the rewritten program's measured bit under faults (ft_noise.py; DESIGN.md "Logical measurement") ---------
     def logical_program_error_rates(self, ops, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
         """[build-defined]  How often the bit measured by ftqc.rewrite_program of `ops; MEASURE` (ops: logical 'I', 'X', 'Y', 'Z' on
@@ -445,6 +457,19 @@ class CSSCode(QECC):
         """[build-defined]  The census of every single fault of the rewritten program, no GPU needed: FTProgram.single_faults."""
         from . import ft_noise
         return ft_noise.program_for(self, ops).single_faults()
+
+    def logical_program_gate_strata_exact(self, ops, weights, **options):
+        """The exact strata `weights` of the rewritten program `ops; MEASURE` under gate-level faults
+        (ft_noise.FTProgram.enumerate_gate_strata): a montecarlo.GateStrata, whose
+        series(('depolarising', 1), 'wrong') gives the Taylor coefficients of the probability that the measured bit is wrong."""
+        from . import ft_noise
+        return ft_noise.program_for(self, ops).enumerate_gate_strata(weights, **options)
+
+    def logical_program_gate_single_faults(self, ops):
+        """[build-defined]  The census of every single gate fault of the rewritten program, no GPU needed:
+        FTProgram.gate_single_faults."""
+        from . import ft_noise
+        return ft_noise.program_for(self, ops).gate_single_faults()
 
     # -- build-defined: both gadgets at any length, block by block (stream_noise.py; DESIGN.md "Streamed gadgets") ---------------
     def error_correct_streamed_error_rates(self, num_samples, p_x, p_y, p_z, rounds, seed=0, first_sample=0, idle_data=False):

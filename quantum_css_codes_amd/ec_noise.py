@@ -24,6 +24,7 @@ t's syndrome decoded relative to what earlier rounds recorded, the final data fr
 DESIGN.md and include/gf2hip.h; gf2_ec_tally_host is its serial form and gf2_mc_ec_decode the device kernel.
 """
 import contextlib
+import math
 
 import numpy as np
 
@@ -223,6 +224,7 @@ class ECCircuit(object):
             self.gadget.gates, self.gadget.qubits, _native.pack_rows(self.gadget.rows_x), _native.pack_rows(self.gadget.rows_z),
             self.gadget.row_time, ldr=self.ldr)
         self._device = None
+        self._sites = None
 
     @property
     def num_locations(self):
@@ -323,6 +325,35 @@ class ECCircuit(object):
             run = lambda first, ws, ns, ks: ctx.mc_ec_decode_strata(circ, self.rounds, *tables, int(seed), int(first), ws, ns, *ks)
         return montecarlo.gadget_strata_local(self.num_locations, EC_FIELDS, weights, samples, kinds, first_sample, run)
 
+    def gate_sites(self):
+        """(site_loc, n1, n2, site_gate) of the cycle's gates (circuit_noise.gate_sites), made once."""
+        if self._sites is None:
+            self._sites = circuit_noise.gate_sites(self.gadget.gates, self.locations)
+        return self._sites
+
+    def enumerate_gate_range(self, w, b, first_rank, count, host=False):
+        """One call of the gate-fault enumeration: the (b + 1, 8) uint64 counts [c][field] over the site
+        subsets of ranks [first_rank, first_rank + count) of weight w with b CNOT picks, c the number of two-operand kinds
+        (gf2_ec_gate_enumerate; host=True: gf2_ec_gate_enumerate_host, no GPU).  Counts of disjoint ranges add."""
+        sites = self.gate_sites()[:3]
+        if host:
+            return _native.ec_gate_enumerate_host(self.effects, self.rounds, *self._tables(), *sites, w, b, first_rank, count)
+        return _native.default_context().ec_gate_enumerate(self.device(), self.rounds, *self._tables(), *sites, w, b, first_rank, count)
+
+    def enumerate_gate_strata(self, weights, max_configurations=None, host=False):
+        """Exact strata of the cycle under gate-level faults: every configuration of exactly weights[s] <= 4
+        faulty gates -- a one-operand gate with X, Y or Z, a CNOT with one of the 15 two-qubit Paulis -- judged by
+        logical_error_rates' tally rule, post-selection included, whole strata, every CNOT count b.  More than `max_configurations`
+        (default circuit_noise.ENUMERATE_BUDGET) configurations in all is a ValueError.  Returns a montecarlo.GateStrata."""
+        return gate_strata(self, EC_FIELDS, weights, max_configurations, host, "cycle")
+
+    def gate_single_faults(self):
+        """The census of every single gate fault, no GPU: (classes, flipping) -- classes (G, 15) uint8, the class byte (CLASS_* bits)
+        of kind mask kappa (column kappa - 1; a one-operand gate uses columns 0 .. 2, the others stay 0) at every gate of the list;
+        flipping, the accepted faults with a logical flip as (gate index, gate (kind, a, b), Paulis) with Paulis one letter for a
+        one-operand gate and control then target, e.g. 'XI' or 'ZY', for a CNOT."""
+        return gate_single_faults(self, CLASS_FLIP_X | CLASS_FLIP_Z)
+
     def single_faults(self):
         """The census of all 3 L single faults, no GPU: (classes, flipping) -- classes (L, 3) uint8, the class byte (CLASS_* bits)
         of an X, Y, Z fault (the columns, KINDS) at every location; flipping, the accepted faults with a logical flip as
@@ -350,6 +381,52 @@ def describe_faults(gadget, fault_list):
             row.append((g, tuple(int(v) for v in gadget.gadget.gates[g]), q, KINDS[k]))
         out.append(tuple(row))
     return out
+
+
+def gate_strata(gadget, fields, weights, max_configurations, host, what):
+    """ECCircuit / FTProgram.enumerate_gate_strata: whole strata through gadget.enumerate_gate_range, stacked per weight into
+    (w + 1, w + 1, F) counts [b][c]."""
+    from . import montecarlo
+    _, n1, n2, _ = gadget.gate_sites()
+    weights = circuit_noise.gate_enumerate_request(n1, n2, weights, max_configurations, what)
+    if not host:
+        gadget.device()
+    counts = []
+    for w in weights:
+        stack = np.zeros((w + 1, w + 1, len(fields)), dtype=np.uint64)
+        for b in range(w + 1):
+            stack[b, :b + 1] = gadget.enumerate_gate_range(w, b, 0, math.comb(n1, w - b) * math.comb(n2, b), host=host)
+        counts.append(stack)
+    return montecarlo.GateStrata(n1, n2, weights, counts, fields)
+
+
+PAULI_OF_MASK = ('I', 'X', 'Z', 'Y')                # the two bits of a kind mask: 1 = X, 2 = Z, 3 = Y
+
+
+def gate_single_faults(gadget, flip_mask):
+    """ECCircuit / FTProgram.gate_single_faults: `flip_mask` the class bits that make an accepted fault one to list."""
+    site_loc, n1, n2, site_gate = gadget.gate_sites()
+    eff = gadget.effects
+    gates = gadget.gadget.gates
+    classes = np.zeros((len(gates), 15), dtype=np.uint8)
+    for sites, nbits in ((slice(0, n1), 2), (slice(n1, n1 + n2), 4)):
+        locs = site_loc[sites].astype(np.int64)
+        if not len(locs):
+            continue
+        words = np.zeros((len(locs), (1 << nbits) - 1, gadget.ldr), dtype=np.uint64)
+        for kappa in range(1, 1 << nbits):
+            for bit in range(nbits):
+                if (kappa >> bit) & 1:
+                    words[:, kappa - 1] ^= eff[locs + (bit >> 1), bit & 1]
+        _, cls = gadget.tally_host(words.reshape(-1, gadget.ldr), classes=True)
+        classes[site_gate[sites], :(1 << nbits) - 1] = cls.reshape(len(locs), -1)
+    flipping = []
+    for g, k in zip(*np.nonzero((classes & CLASS_ACCEPTED != 0) & (classes & flip_mask != 0))):
+        kappa = int(k) + 1
+        gate = tuple(int(v) for v in gates[g])
+        paulis = PAULI_OF_MASK[kappa & 3] + (PAULI_OF_MASK[kappa >> 2] if gate[0] == GATE_CNOT else '')
+        flipping.append((int(g), gate, paulis))
+    return classes, flipping
 
 
 def circuit_for(code, rounds=1, idle_data=False):

@@ -142,6 +142,7 @@ class FTProgram(object):
             self.gadget.gates, self.gadget.qubits, _native.pack_rows(self.gadget.rows_x), _native.pack_rows(self.gadget.rows_z),
             self.gadget.row_time, ldr=self.ldr)
         self._device = None
+        self._sites = None
 
     @classmethod
     def from_quil(cls, raw_prog, code):
@@ -248,6 +249,34 @@ class FTProgram(object):
             ctx, circ = _native.default_context(), self.device()
             run = lambda first, ws, ns, ks: ctx.mc_ft_decode_strata(circ, self.nsteps, self.measure_mask, *tables, int(seed), int(first), ws, ns, *ks)
         return montecarlo.gadget_strata_local(self.num_locations, FT_FIELDS, weights, samples, kinds, first_sample, run)
+
+    def gate_sites(self):
+        """(site_loc, n1, n2, site_gate) of the program's gates (circuit_noise.gate_sites), made once."""
+        if self._sites is None:
+            self._sites = circuit_noise.gate_sites(self.gadget.gates, self.locations)
+        return self._sites
+
+    def enumerate_gate_range(self, w, b, first_rank, count, host=False):
+        """One call of the gate-fault enumeration: the (b + 1, 7) uint64 counts [c][field] over the site
+        subsets of ranks [first_rank, first_rank + count) of weight w with b CNOT picks, c the number of two-operand kinds
+        (gf2_ft_gate_enumerate; host=True: gf2_ft_gate_enumerate_host, no GPU).  Counts of disjoint ranges add."""
+        sites = self.gate_sites()[:3]
+        if host:
+            return _native.ft_gate_enumerate_host(self.effects, self.nsteps, self.measure_mask, *self._tables(), *sites, w, b, first_rank, count)
+        return _native.default_context().ft_gate_enumerate(self.device(), self.nsteps, self.measure_mask, *self._tables(), *sites, w, b,
+                                                           first_rank, count)
+
+    def enumerate_gate_strata(self, weights, max_configurations=None, host=False):
+        """Exact strata of the measurement under gate-level faults: every configuration of exactly
+        weights[s] <= 4 faulty gates of the rewritten program judged by measurement_error_rates' tally rule, post-selection
+        included, whole strata, every CNOT count b.  Arguments as ECCircuit.enumerate_gate_strata's.  Returns a montecarlo.GateStrata."""
+        return ec_noise.gate_strata(self, FT_FIELDS, weights, max_configurations, host, "program")
+
+    def gate_single_faults(self):
+        """The census of every single gate fault, no GPU: (classes, wrong) -- classes (G, 15) uint8, the class byte (CLASS_* bits) of
+        kind mask kappa (column kappa - 1; a one-operand gate uses columns 0 .. 2) at every gate of the list; wrong, the accepted
+        faults that make the measured bit wrong, as (gate index, gate (kind, a, b), Paulis) in ECCircuit.gate_single_faults' format."""
+        return ec_noise.gate_single_faults(self, CLASS_WRONG)
 
     def single_faults(self):
         """The census of all 3 L single faults, no GPU: (classes, wrong) -- classes (L, 3) uint8, the class byte (CLASS_* bits) of

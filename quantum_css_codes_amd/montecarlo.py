@@ -587,6 +587,182 @@ class PostSelectedStrata(object):
         return MergedPostSelectedStrata(self, [sampled] if isinstance(sampled, SampledPostSelectedStrata) else list(sampled), kinds)
 
 
+# ---- exact strata under gate-level faults ---------------------------------------------------------------
+
+def _series_mul(f, g, m):
+    """The product of two power series given by their coefficients, truncated after order m."""
+    out = [_fractions.Fraction(0)] * (m + 1)
+    for i, a in enumerate(f[:m + 1]):
+        if a:
+            for j, b in enumerate(g[:m + 1 - i]):
+                out[i + j] += a * b
+    return out
+
+
+class GateStrata(object):
+    """Exact strata of a post-selected gadget under gate-level faults (ec_noise.ECCircuit / ft_noise.FTProgram.enumerate_gate_strata):
+    `n1` one-operand gates and `n2` CNOTs, `weights` (distinct, <= 4) and, per weight w, the (w + 1, w + 1, F) uint64 counts
+    [b][c][field] over ALL configurations of w faulty gates of which b are CNOTs, c of those with a two-operand kind; `fields` names
+    the F columns, field 0 is 'accepted'.  A model gives the odds (x, y1, y2) of one specific kind against "no fault at this site" --
+    x on a one-operand gate, y1 for a one-operand CNOT kind, y2 for a two-operand one -- and
+    P(accepted and field) = Z sum counts[w][b][c] x^(w - b) y1^(b - c) y2^c,  Z = (1 + 3 x)^-n1 (1 + 6 y1 + 9 y2)^-n2."""
+
+    SUM_FIELDS = PostSelectedStrata.SUM_FIELDS
+
+    def __init__(self, n1, n2, weights, counts, fields):
+        self.n1, self.n2 = int(n1), int(n2)
+        self.fields = tuple(fields)
+        if not self.fields or self.fields[0] != 'accepted':
+            raise ValueError("the first field of a post-selected tally is 'accepted'")
+        self.weights = [int(w) for w in np.asarray(weights).reshape(-1)]
+        if len(set(self.weights)) != len(self.weights):
+            raise ValueError("the weights of the strata must be distinct")
+        if any(w < 0 or w > self.n1 + self.n2 for w in self.weights):
+            raise ValueError("a stratum's weight lies in [0, n1 + n2]")
+        counts = list(counts)
+        if len(counts) != len(self.weights):
+            raise ValueError("one array of counts per weight")
+        self.counts = [np.asarray(c, dtype=np.uint64).reshape(w + 1, w + 1, len(self.fields)).copy() for w, c in zip(self.weights, counts)]
+
+    def configurations(self):
+        """sum_b C(n1, w - b) C(n2, b) 3^(w - b) 15^b per weight."""
+        return [sum(math.comb(self.n1, w - b) * math.comb(self.n2, b) * 3**(w - b) * 15**b for b in range(w + 1)) for w in self.weights]
+
+    def _column(self, field):
+        if field not in self.fields:
+            raise ValueError("no field %r (the fields are %s)" % (field, ', '.join(self.fields)))
+        return self.fields.index(field)
+
+    @staticmethod
+    def depolarising_odds(p1, p2):
+        """Depolarising gate faults: a one-operand gate fails with probability p1 (X, Y, Z alike), a CNOT with p2 (its 15 Paulis alike)."""
+        p1, p2 = float(p1), float(p2)
+        if not (0.0 <= p1 < 1.0 and 0.0 <= p2 < 1.0):
+            raise ValueError("the odds need 0 <= p < 1")
+        y = p2 / (15.0 * (1.0 - p2))
+        return p1 / (3.0 * (1.0 - p1)), y, y
+
+    @staticmethod
+    def independent_odds(p):
+        """The independent-operand model of the location strata at total probability p per location: a CNOT's two operands fail
+        independently, so a two-operand kind has the odds of two faults."""
+        p = float(p)
+        if not 0.0 <= p < 1.0:
+            raise ValueError("the odds need 0 <= p < 1")
+        x = p / (3.0 * (1.0 - p))
+        return x, x, x * x
+
+    def _terms(self, col):
+        for w, counts in zip(self.weights, self.counts):
+            for b in range(w + 1):
+                for c in range(b + 1):
+                    n = int(counts[b, c, col])
+                    if n:
+                        yield n, w - b, b - c, c
+
+    def joint(self, odds, field='accepted'):
+        """P(accepted and field) over the enumerated weights at the odds (x, y1, y2), every term in log space like binomial_weights:
+        accurate at p = 1e-12 and below.  For a sum field, the expectation of the field over accepted configurations times
+        P(accepted)."""
+        x, y1, y2 = (float(v) for v in odds)
+        if min(x, y1, y2) < 0.0:
+            raise ValueError("odds are not negative")
+        log_z = -self.n1 * math.log1p(3.0 * x) - self.n2 * math.log1p(6.0 * y1 + 9.0 * y2)
+        terms = []
+        for n, e_x, e_1, e_2 in self._terms(self._column(field)):
+            if any(e and not v for e, v in ((e_x, x), (e_1, y1), (e_2, y2))):
+                continue
+            log_t = sum(e * math.log(v) for e, v in ((e_x, x), (e_1, y1), (e_2, y2)) if e)
+            terms.append(n * math.exp(log_t + log_z))
+        return math.fsum(terms)
+
+    def _missing_mass(self, odds):
+        """T: the probability that the number of faulty gates is not an enumerated weight (the sum of two binomials)."""
+        x, y1, y2 = (float(v) for v in odds)
+        q_1, q_2 = 3.0 * x / (1.0 + 3.0 * x), (6.0 * y1 + 9.0 * y2) / (1.0 + 6.0 * y1 + 9.0 * y2)
+        total = np.convolve(binomial_weights(self.n1, q_1), binomial_weights(self.n2, q_2))
+        have = np.zeros(len(total), dtype=bool)
+        have[self.weights] = True
+        return math.fsum(total[~have])
+
+    def acceptance(self, odds):
+        """(D, D + T): bounds on the probability that an attempt is accepted."""
+        d = self.joint(odds, 'accepted')
+        return d, d + self._missing_mass(odds)
+
+    def rate(self, odds, field='wrong'):
+        """The conditional rate P(field | accepted) of an indicator field as (estimate, lower, upper), PostSelectedStrata.rate's
+        argument: with N = joint(field), D = joint('accepted') and T the probability that the number of faulty gates is not an
+        enumerated weight, estimate = N / D, lower = N / (D + T), upper = (N + T) / (D + T)."""
+        if field in self.SUM_FIELDS:
+            raise ValueError("rate() is defined for indicator fields; %r is a sum (series() gives its conditional expectation)" % (field,))
+        n, d, t = self.joint(odds, field), self.joint(odds, 'accepted'), self._missing_mass(odds)
+        if not d > 0:
+            raise ValueError("no accepted configuration among the enumerated weights at the odds %r" % (tuple(odds),))
+        return n / d, n / (d + t), (n + t) / (d + t)
+
+    def _odds_series(self, model, m):
+        """(x, y1, y2) as power series in p truncated after order m, exact."""
+        one = _fractions.Fraction(1)
+        geometric = lambda r, scale: [_fractions.Fraction(0)] + [r**k / scale for k in range(1, m + 1)]   # r p / (scale (1 - r p))
+        if model == 'independent':
+            x = geometric(one, 3)
+            return x, x, _series_mul(x, x, m)
+        if isinstance(model, (tuple, list)) and len(model) == 2 and model[0] == 'depolarising' and isinstance(model[1], numbers.Rational):
+            if model[1] < 0:
+                raise ValueError("the ratio p_2 / p_1 is not negative")
+            y = geometric(_fractions.Fraction(model[1]), 15)
+            return geometric(one, 3), y, y
+        raise ValueError("a model is 'independent' or ('depolarising', r) with r = p_2 / p_1 rational, got %r" % (model,))
+
+    def series(self, model, field='wrong', order=None):
+        """The Taylor coefficients [c_0, ..., c_m] in p of the conditional rate of `field` (for a sum field: of its conditional
+        expectation), exact fractions.Fraction.  model: ('depolarising', r) with p_1 = p, p_2 = r p, r rational, or 'independent'
+        (p per location).  m (or `order`, if smaller) is the largest order with every weight 0 .. m enumerated: a configuration
+        of w faulty gates enters at order w or above.  Z cancels in N / D, which leaves a quotient of polynomials in the odds,
+        themselves truncated power series in p.  Needs counts[0]['accepted'] = 1 (no fault: accepted), ValueError otherwise."""
+        have = set(self.weights)
+        m = -1
+        while m + 1 in have:
+            m += 1
+        if m < 0:
+            raise ValueError("a series needs the stratum of weight 0")
+        if order is not None:
+            if int(order) < 0 or int(order) > m:
+                raise ValueError("order %d outside [0, %d], the weights enumerated without a gap" % (int(order), m))
+            m = int(order)
+        odds = self._odds_series(model, m)
+        unit = [_fractions.Fraction(1)] + [_fractions.Fraction(0)] * m
+        powers = [[unit], [unit], [unit]]
+        for v, table in zip(odds, powers):
+            for _ in range(m):
+                table.append(_series_mul(table[-1], v, m))
+
+        def poly(col):
+            total = [_fractions.Fraction(0)] * (m + 1)
+            for n, e_x, e_1, e_2 in self._terms(col):
+                if e_x + e_1 + e_2 > m:
+                    continue
+                term = _series_mul(_series_mul(powers[0][e_x], powers[1][e_1], m), powers[2][e_2], m)
+                total = [t + n * v for t, v in zip(total, term)]
+            return total
+
+        num, den = poly(self._column(field)), poly(0)
+        if den[0] != 1:
+            raise ValueError("a series needs one accepted configuration of weight 0, got %r" % (den[0],))
+        out = []
+        for k in range(m + 1):
+            out.append(num[k] - sum(out[i] * den[k - i] for i in range(k)))
+        return out
+
+    def leading_order(self, model, field='wrong'):
+        """(m, c_m): the first non-zero coefficient of series(); None when every coefficient is zero."""
+        for k, c in enumerate(self.series(model, field)):
+            if c != 0:
+                return k, c
+        return None
+
+
 # ---- malignant fault sets of a post-selected gadget (DESIGN.md "Malignant fault sets of the cycle", "... of the measurement") --------
 
 class FaultList(object):
