@@ -1,8 +1,9 @@
-// What gf2_circuit.hip (the fault Monte-Carlo), gf2_enumerate.hip (the exact strata), gf2_ec.hip (the error-correction cycle),
-// gf2_ft.hip (the fault-tolerant logical measurement), gf2_gadget_enumerate.hip (the exact strata of those two) and
-// gf2_gadget_strata.hip (their sampled strata) share: the circuit
-// object, the Monte-Carlo layout of its outcome words, the device side of the tally's syndrome tables and the gather loop of a
-// Monte-Carlo sample.
+// What the kernels over a circuit's effect table share -- gf2_circuit.hip (the fault Monte-Carlo), gf2_enumerate.hip (the exact
+// strata), gf2_stream.hip (the streamed route) and the entry points of the two post-selected gadgets: gf2_ec.hip (the
+// error-correction cycle), gf2_ft.hip (the fault-tolerant logical measurement), gf2_gadget_strata.hip (their sampled strata),
+// gf2_gadget_enumerate.hip (their exact strata), gf2_gate_enumerate.hip (those under gate-level faults) and gf2_gadget_list.hip
+// (their malignant fault sets): the circuit object, the Monte-Carlo layout of its outcome words, whether a launch stages the effect
+// table in LDS, the device side of the tally's syndrome tables and the gather loop of a Monte-Carlo sample.
 #pragma once
 
 #include "gf2_internal.h"
@@ -22,6 +23,15 @@ struct gf2_circuit {
 // gf2_circuit.hip: gf2_circuit_create for 1 <= ldr <= max_ldr (gf2_ft_circuit_create's GF2_FT_MAX_LDR: gf2_ft.hip)
 int gf2_circuit_create_upto(const char* who, gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t max_ldr,
                             gf2_circuit** circuit_out);
+
+// Whether a launch stages the circuit's effect table in LDS (allowed: the kernel has a staged form; the table must fit
+// CIRC_EFF_LDS_BYTES), and the launch's dynamic LDS: the staged table plus `other` bytes.
+static bool circuit_staged(const gf2_circuit* circ, bool allowed, size_t other, size_t* lds) {
+    const size_t eff_bytes = (size_t)2 * circ->locations * circ->ldr * 8;
+    const bool staged = allowed && eff_bytes <= CIRC_EFF_LDS_BYTES;
+    *lds = (staged ? eff_bytes : 0) + other;
+    return staged;
+}
 
 // gf2_host.cpp: the argument rules of an enumerated rank range (include/gf2hip.h "exact strata")
 int gf2_enum_check_range(const char* who, int64_t nb, int64_t w, int64_t first_rank, int64_t count);

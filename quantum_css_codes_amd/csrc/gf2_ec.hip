@@ -15,7 +15,7 @@
 // taken maps, and the eight counts.  Per-lane tallies stay in registers; a workgroup does 8 LDS atomics per lane with something to
 // add and 8 global atomics.
 #include "gf2_internal.h"
-#include "gf2_circuit_dev.h"
+#include "gf2_gadget_dev.h"
 
 #define EC_FIELDS GF2_EC_FIELDS
 #define EC_MAX_ROUNDS GF2_EC_MAX_ROUNDS
@@ -101,30 +101,20 @@ __global__ __launch_bounds__(CIRC_THREADS) void ec_kernel(EcArgs a) {
     if (threadIdx.x < EC_FIELDS && bins[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (u64)bins[threadIdx.x]);
 }
 
-template <int LDR>
-static void ec_launch_ldr(gf2_ctx* ctx, const EcArgs& a, bool staged, unsigned blocks, size_t lds) {
-    if (staged)
-        hipLaunchKernelGGL((ec_kernel<LDR, true>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
-    else
-        hipLaunchKernelGGL((ec_kernel<LDR, false>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
-}
-
 static int ec_launch(gf2_ctx* ctx, const gf2_circuit* circ, const EcArgs& a) {
-    const size_t eff_bytes = (size_t)2 * circ->locations * circ->ldr * 8;
-    const bool staged = eff_bytes <= CIRC_EFF_LDS_BYTES;
-    const size_t lds = (size_t)2 * GF2_SEG_CDF * 8 + (size_t)CIRC_THREADS * CIRC_TAKEN_STRIDE * 4 + (staged ? eff_bytes : 0) + EC_FIELDS * 4;
+    size_t lds;
+    const bool staged = circuit_staged(circ, true, (size_t)2 * GF2_SEG_CDF * 8 + (size_t)CIRC_THREADS * CIRC_TAKEN_STRIDE * 4 + EC_FIELDS * 4, &lds);
     int64_t blocks = gf2_cdiv(a.count, CIRC_THREADS * 16);
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
     GF2_TRY(gf2_prof_begin(ctx, GF2_K_SAMPLER));
-    switch (circ->ldr) {
-        case 3: ec_launch_ldr<3>(ctx, a, staged, (unsigned)blocks, lds); break;
-        case 4: ec_launch_ldr<4>(ctx, a, staged, (unsigned)blocks, lds); break;
-        case 5: ec_launch_ldr<5>(ctx, a, staged, (unsigned)blocks, lds); break;
-        case 6: ec_launch_ldr<6>(ctx, a, staged, (unsigned)blocks, lds); break;
-        case 7: ec_launch_ldr<7>(ctx, a, staged, (unsigned)blocks, lds); break;
-        case 8: ec_launch_ldr<8>(ctx, a, staged, (unsigned)blocks, lds); break;
-    }
+    gadget_for_ldr<RULE_EC>(circ->ldr, [&](auto ldr) {
+        constexpr int LDR = decltype(ldr)::value;
+        if (staged)
+            hipLaunchKernelGGL((ec_kernel<LDR, true>), dim3((unsigned)blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+        else
+            hipLaunchKernelGGL((ec_kernel<LDR, false>), dim3((unsigned)blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+    });
     GF2_TRY(gf2_prof_end(ctx));
     GF2_HIP(hipGetLastError());
     return GF2_OK;
@@ -137,23 +127,8 @@ int gf2_mc_ec_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, i
                      int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, uint64_t* counts_out) {
     const char* who = "gf2_mc_ec_decode";
     if (!ctx || !circuit || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (rounds < 1 || rounds > EC_MAX_ROUNDS) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= rounds <= %d, got %lld", who, EC_MAX_ROUNDS, (long long)rounds);
-    if (circuit->ldr > GF2_CIRCUIT_MAX_LDR)
-        GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per sample, got %lld", who, GF2_CIRCUIT_MAX_LDR, (long long)circuit->ldr);
-    if (circuit->ldr < rounds + 2)
-        GF2_FAIL(GF2_E_ARG, "%s: %lld rounds need ldr = 1 + rounds + F words with F >= 1 flag words, the circuit has %lld", who,
-                 (long long)rounds, (long long)circuit->ldr);
     EcArgs a = {};
-    a.rounds = (int)rounds;
-    a.mask[0] = (1ull << r2) - 1;
-    a.mask[1] = (1ull << r1) - 1;
-    a.kwx = a.kwz = 1;
-    const u64 keys = a.mask[0] | a.mask[1] << 32;
-    bool beyond = (circuit->any[0] & ~(keys | 1ull << 31 | 1ull << 63)) != 0;
-    for (int64_t t = 1; t <= rounds; ++t) beyond |= (circuit->any[t] & ~keys) != 0;
-    if (beyond) GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits, the two parity bits and the flag words", who);
+    GF2_TRY(ec_rule_args(who, circuit, rounds, r1, r2, &a));
     GF2_TRY(circuit_check_tables(who, keys1, flips1, entries1, keys2, flips2, entries2));
     if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "%s: negative range", who);
     GF2_TRY(check_probabilities(p_x, p_y, p_z));

@@ -120,22 +120,19 @@ extern "C" int gf2_circuit_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, i
     a.pow3 = 1;
     for (int64_t k = 0; k < w; ++k) a.pow3 *= 3u;
     a.counts = tables.counts_dev;
-    const size_t eff_bytes = (size_t)2 * circuit->locations * circuit->ldr * 8;
-    const bool staged = eff_bytes <= CIRC_EFF_LDS_BYTES;
-    const size_t lds = (staged ? eff_bytes : 0) + (size_t)ncounts * 4;
+    size_t lds;
+    const bool staged = circuit_staged(circuit, true, (size_t)ncounts * 4, &lds);
     const int64_t per_launch = ENUM_LAUNCH_CONFIGS / a.pow3;                             // subsets (at least 2^30 / 3^8)
     for (int64_t done = 0; done < count; done += per_launch) {
         a.first_rank = (u64)(first_rank + done);
         a.count = count - done < per_launch ? count - done : per_launch;
-        int64_t run = a.count / ((int64_t)ENUM_MAX_BLOCKS * CIRC_THREADS);               // short runs until every lane has one
-        a.run = (int)(run < 1 ? 1 : run > ENUM_MAX_RUN ? ENUM_MAX_RUN : run);
-        int64_t blocks = gf2_cdiv(gf2_cdiv(a.count, a.run), CIRC_THREADS);
-        if (blocks > ENUM_MAX_BLOCKS) blocks = ENUM_MAX_BLOCKS;
+        unsigned blocks;
+        enum_launch_shape(a.count, &a.run, &blocks);
         GF2_TRY(gf2_prof_begin(ctx, GF2_K_SAMPLER));
         switch (circuit->ldr) {                                                          // (circuit_layout: 3, 4 or 5)
-            case 3: enumerate_launch_ldr<3>(ctx, a, staged, (unsigned)blocks, lds); break;
-            case 4: enumerate_launch_ldr<4>(ctx, a, staged, (unsigned)blocks, lds); break;
-            case 5: enumerate_launch_ldr<5>(ctx, a, staged, (unsigned)blocks, lds); break;
+            case 3: enumerate_launch_ldr<3>(ctx, a, staged, blocks, lds); break;
+            case 4: enumerate_launch_ldr<4>(ctx, a, staged, blocks, lds); break;
+            case 5: enumerate_launch_ldr<5>(ctx, a, staged, blocks, lds); break;
         }
         GF2_TRY(gf2_prof_end(ctx));
         GF2_HIP(hipGetLastError());

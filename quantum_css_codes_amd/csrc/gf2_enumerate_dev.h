@@ -1,7 +1,9 @@
-// The walk of an enumerated rank range (DESIGN.md "Exact strata"), shared by enumerate_kernel (gf2_enumerate.hip) and
-// gadget_enumerate_kernel (gf2_gadget_enumerate.hip): exact binomials, unranking in the combinatorial number system, the
-// colexicographic successor and one step of the reflected ternary Gray code over the digit order X, Y, Z.  Everything is
-// __forceinline__, works on eight picks held in VGPRs and indexes them with constants or with selects on a scalar only.
+// The walk of an enumerated rank range (DESIGN.md "Exact strata"), shared by enumerate_kernel (gf2_enumerate.hip),
+// gadget_enumerate_kernel (gf2_gadget_enumerate.hip), gadget_list_kernel (gf2_gadget_list.hip) and, for its unranking and its launch
+// shape, gate_enumerate_kernel (gf2_gate_enumerate.hip): how a launch is cut into runs and workgroups (host side), exact binomials,
+// unranking in the combinatorial number system, the colexicographic successor and one step of the reflected ternary Gray code over
+// the digit order X, Y, Z.  Every device function is __forceinline__, works on eight picks held in VGPRs and indexes them with
+// constants or with selects on a scalar only.
 #pragma once
 
 #include "gf2_circuit_dev.h"
@@ -10,6 +12,15 @@
 #define ENUM_LAUNCH_CONFIGS (1ll << 30)        // configurations per launch (DESIGN.md "Exact strata")
 #define ENUM_MAX_RUN 32                        // ranks per lane and unranking
 #define ENUM_MAX_BLOCKS 2048                   // 8 workgroups of 256 lanes on each of the 256 CUs
+
+// The shape of a launch over `count` subsets: *run consecutive ranks per lane -- short runs until every lane of ENUM_MAX_BLOCKS
+// workgroups has one, at most ENUM_MAX_RUN -- and the workgroups that cover the runs.
+static void enum_launch_shape(int64_t count, int* run, unsigned* blocks) {
+    const int64_t r = count / ((int64_t)ENUM_MAX_BLOCKS * CIRC_THREADS);
+    *run = (int)(r < 1 ? 1 : r > ENUM_MAX_RUN ? ENUM_MAX_RUN : r);
+    const int64_t b = gf2_cdiv(gf2_cdiv(count, *run), CIRC_THREADS);
+    *blocks = (unsigned)(b > ENUM_MAX_BLOCKS ? ENUM_MAX_BLOCKS : b);
+}
 
 // C(s, K) for s < L, exact: c_i = C(s - K + i, i) -> c_{i+1} = c_i (s - K + 1 + i) / (i + 1), the division split so that no
 // intermediate exceeds the result (below C(L, w) < 2^63).  The divisors are constants after unrolling.

@@ -17,10 +17,9 @@
 // through L2: the smallest program's (Steane, no gates: 2 * 1630 * 8 words) is ten times CIRC_EFF_LDS_BYTES.  A workgroup does
 // at most 7 LDS atomics per lane with something to add and 7 global atomics.
 #include "gf2_internal.h"
-#include "gf2_circuit_dev.h"
+#include "gf2_gadget_dev.h"
 
 #define FT_FIELDS GF2_FT_FIELDS
-#define FT_MIN_LDR 8
 #define FT_LAUNCH_SAMPLES (1ll << 36)          // per launch: keeps a lane's and a workgroup's 32-bit tallies far from wrapping
 
 enum { FT_STORE = 0, FT_TALLY = 1 };
@@ -121,12 +120,9 @@ static int ft_launch(gf2_ctx* ctx, const gf2_circuit* circ, const FtArgs& a) {
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
     GF2_TRY(gf2_prof_begin(ctx, GF2_K_SAMPLER));
-#define FT_CASE(L) \
-    case L: hipLaunchKernelGGL((ft_kernel<L, EPI>), dim3((unsigned)blocks), dim3(CIRC_THREADS), lds, ctx->stream, a); break;
-    switch (circ->ldr) {
-        FT_CASE(8) FT_CASE(9) FT_CASE(10) FT_CASE(11) FT_CASE(12) FT_CASE(13) FT_CASE(14) FT_CASE(15) FT_CASE(16)
-    }
-#undef FT_CASE
+    gadget_for_ldr<RULE_FT>(circ->ldr, [&](auto ldr) {
+        hipLaunchKernelGGL((ft_kernel<decltype(ldr)::value, EPI>), dim3((unsigned)blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+    });
     GF2_TRY(gf2_prof_end(ctx));
     GF2_HIP(hipGetLastError());
     return GF2_OK;
@@ -168,29 +164,8 @@ int gf2_mc_ft_decode(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, u
                      uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, uint64_t* counts_out) {
     const char* who = "gf2_mc_ft_decode";
     if (!ctx || !circuit || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (circuit->ldr < FT_MIN_LDR || circuit->ldr > GF2_FT_MAX_LDR)
-        GF2_FAIL(GF2_E_ARG, "%s: needs %d <= ldr <= %d words per sample, got %lld", who, FT_MIN_LDR, GF2_FT_MAX_LDR, (long long)circuit->ldr);
-    if (nsteps < 1 || circuit->ldr < nsteps + 1)
-        GF2_FAIL(GF2_E_ARG, "%s: needs nsteps >= 1 and ldr = nsteps + F words with F >= 1 flag words, got nsteps = %lld, the circuit has %lld", who,
-                 (long long)nsteps, (long long)circuit->ldr);
-    if (measure_mask >> nsteps) GF2_FAIL(GF2_E_ARG, "%s: measure_mask has bits at or above nsteps = %lld", who, (long long)nsteps);
-    const int trials = __builtin_popcountll(measure_mask);
-    if (trials % 2 == 0) GF2_FAIL(GF2_E_ARG, "%s: a majority vote needs an odd number of trials, measure_mask has %d", who, trials);
     FtArgs a = {};
-    a.nsteps = (int)nsteps;
-    a.trials = trials;
-    a.first_measure = __builtin_ctzll(measure_mask);
-    a.measure_mask = (unsigned int)measure_mask;
-    a.mask[0] = (1ull << r2) - 1;
-    a.mask[1] = (1ull << r1) - 1;
-    a.kwx = a.kwz = 1;
-    bool beyond = false;
-    for (int64_t s = 0; s < nsteps; ++s)
-        beyond |= (circuit->any[s] & ~((measure_mask >> s) & 1ull ? a.mask[0] | 1ull << 31 : a.mask[0] | a.mask[1] << 32)) != 0;
-    if (beyond)
-        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key bits and bit 31)", who);
+    GF2_TRY(ft_rule_args(who, circuit, nsteps, measure_mask, r1, r2, &a));
     GF2_TRY(circuit_check_tables(who, keys1, flips1, entries1, keys2, flips2, entries2));
     if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "%s: negative range", who);
     GF2_TRY(check_probabilities(p_x, p_y, p_z));

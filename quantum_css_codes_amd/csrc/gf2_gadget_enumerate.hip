@@ -27,8 +27,6 @@
 static_assert(GADGET_MAX_ADD * GADGET_LAUNCH_CONFIGS < (1ll << 32), "a workgroup's 32-bit bins must hold a whole launch");
 static_assert(GF2_FT_MAX_LDR - 1 <= GADGET_MAX_ADD && GF2_EC_MAX_ROUNDS <= GADGET_MAX_ADD, "a sum field's value per configuration");
 
-enum { RULE_EC = 0, RULE_FT = 1 };
-
 struct GadgetEnumArgs {
     const u64* eff;
     int locations, weight;
@@ -45,21 +43,6 @@ struct GadgetEnumArgs {
     const unsigned char* flips[2];             // operator . correction of every table entry
     u64* counts;                               // [(weight + 1)][(weight + 1)][F]
 };
-
-// One lane adds the wavefront's count of an indicator ...
-__device__ __forceinline__ void gadget_add_votes(unsigned int* bin, bool first_lane, bool vote) {
-    const u64 votes = __ballot(vote);
-    if (votes != 0ull && first_lane) atomicAdd(bin, (unsigned int)__popcll(votes));
-}
-
-// ... or of a sum field below 2^BITS among the accepted lanes.
-template <int BITS>
-__device__ __forceinline__ void gadget_add_sum(unsigned int* bin, bool first_lane, bool acc, unsigned int value) {
-    unsigned int sum = 0;
-#pragma unroll
-    for (int b = 0; b < BITS; ++b) sum += (unsigned int)__popcll(__ballot(acc && ((value >> b) & 1u))) << b;
-    if (sum != 0u && first_lane) atomicAdd(bin, sum);
-}
 
 template <int LDR, int RULE, bool STAGED>
 __global__ __launch_bounds__(CIRC_THREADS) void gadget_enumerate_kernel(GadgetEnumArgs a) {
@@ -106,22 +89,11 @@ __global__ __launch_bounds__(CIRC_THREADS) void gadget_enumerate_kernel(GadgetEn
                     bool flip[2], miss[2];
                     unsigned int unmatched[2] = {0, 0};
                     ec_chain<LDR>(a, out, flip, miss, unmatched);
-                    gadget_add_votes(&bin[1], first_lane, acc && flip[0]);
-                    gadget_add_votes(&bin[2], first_lane, acc && flip[1]);
-                    gadget_add_votes(&bin[3], first_lane, acc && (flip[0] || flip[1]));
-                    gadget_add_votes(&bin[4], first_lane, acc && miss[0]);
-                    gadget_add_votes(&bin[5], first_lane, acc && miss[1]);
-                    gadget_add_sum<3>(&bin[6], first_lane, acc, unmatched[0]);         // <= GF2_EC_MAX_ROUNDS = 6
-                    gadget_add_sum<3>(&bin[7], first_lane, acc, unmatched[1]);
+                    ec_add_tally(bin, first_lane, acc, flip, miss, unmatched);
                 } else {
                     unsigned int wrong_trials = 0, first_wrong = 0, unmatched[2] = {0, 0};
                     ft_walk<LDR>(a, out, wrong_trials, first_wrong, unmatched);
-                    gadget_add_votes(&bin[1], first_lane, acc && 2 * wrong_trials > (unsigned int)a.trials);
-                    gadget_add_sum<4>(&bin[2], first_lane, acc, wrong_trials);         // <= trials <= 15 steps
-                    gadget_add_votes(&bin[3], first_lane, acc && first_wrong != 0u);
-                    gadget_add_votes(&bin[4], first_lane, acc && wrong_trials != 0u && wrong_trials != (unsigned int)a.trials);
-                    gadget_add_sum<4>(&bin[5], first_lane, acc, unmatched[0]);         // <= nsteps <= 15
-                    gadget_add_sum<4>(&bin[6], first_lane, acc, unmatched[1]);
+                    ft_add_tally(bin, first_lane, acc, wrong_trials, first_wrong, unmatched, (unsigned int)a.trials);
                 }
             }
         }
@@ -129,17 +101,6 @@ __global__ __launch_bounds__(CIRC_THREADS) void gadget_enumerate_kernel(GadgetEn
     __syncthreads();
     for (int i = threadIdx.x; i < nbins; i += blockDim.x)
         if (bins[i]) atomicAdd(&a.counts[i], (u64)bins[i]);
-}
-
-template <int LDR, int RULE>
-static void gadget_launch_ldr(gf2_ctx* ctx, const GadgetEnumArgs& a, bool staged, unsigned blocks, size_t lds) {
-    if constexpr (RULE == RULE_EC) {
-        if (staged) {
-            hipLaunchKernelGGL((gadget_enumerate_kernel<LDR, RULE, true>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((gadget_enumerate_kernel<LDR, RULE, false>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
 }
 
 // The launches of a checked call: tables made once, the range cut into launches of at most GADGET_LAUNCH_CONFIGS configurations.
@@ -162,31 +123,27 @@ static int gadget_enumerate(const char* who, gf2_ctx* ctx, const gf2_circuit* ci
     a.pow3 = 1;
     for (int64_t k = 0; k < w; ++k) a.pow3 *= 3u;
     a.counts = tables.counts_dev;
-    const size_t eff_bytes = (size_t)2 * circuit->locations * circuit->ldr * 8;
-    const bool staged = RULE == RULE_EC && eff_bytes <= CIRC_EFF_LDS_BYTES;             // (the measurement's tables never fit)
-    const size_t lds = (staged ? eff_bytes : 0) + (size_t)ncounts * 4;
+    size_t lds;
+    const bool staged = circuit_staged(circuit, RULE == RULE_EC, (size_t)ncounts * 4, &lds);   // (the measurement's tables never fit)
     const int64_t per_launch = GADGET_LAUNCH_CONFIGS / a.pow3;                           // subsets (at least 2^28 / 3^8)
     if (per_launch < 1 || per_launch * a.pow3 * GADGET_MAX_ADD >= (1ll << 32))          // (a workgroup's 32-bit bins: the comment above)
         GF2_FAIL(GF2_E_ARG, "%s: a launch of %lld configurations would overflow a 32-bit bin", who, (long long)(per_launch * a.pow3));
     for (int64_t done = 0; done < count; done += per_launch) {
         a.first_rank = (u64)(first_rank + done);
         a.count = count - done < per_launch ? count - done : per_launch;
-        int64_t run = a.count / ((int64_t)ENUM_MAX_BLOCKS * CIRC_THREADS);               // short runs until every lane has one
-        a.run = (int)(run < 1 ? 1 : run > ENUM_MAX_RUN ? ENUM_MAX_RUN : run);
-        int64_t blocks = gf2_cdiv(gf2_cdiv(a.count, a.run), CIRC_THREADS);
-        if (blocks > ENUM_MAX_BLOCKS) blocks = ENUM_MAX_BLOCKS;
+        unsigned blocks;
+        enum_launch_shape(a.count, &a.run, &blocks);
         GF2_TRY(gf2_prof_begin(ctx, GF2_K_SAMPLER));
-#define GADGET_CASE(L) \
-    case L: gadget_launch_ldr<L, RULE>(ctx, a, staged, (unsigned)blocks, lds); break;
-        if constexpr (RULE == RULE_EC) {
-            switch (circuit->ldr) { GADGET_CASE(3) GADGET_CASE(4) GADGET_CASE(5) GADGET_CASE(6) GADGET_CASE(7) GADGET_CASE(8) }
-        } else {
-            switch (circuit->ldr) {
-                GADGET_CASE(8) GADGET_CASE(9) GADGET_CASE(10) GADGET_CASE(11) GADGET_CASE(12) GADGET_CASE(13) GADGET_CASE(14) GADGET_CASE(15)
-                GADGET_CASE(16)
+        gadget_for_ldr<RULE>(circuit->ldr, [&](auto ldr) {
+            constexpr int LDR = decltype(ldr)::value;
+            if constexpr (RULE == RULE_EC) {
+                if (staged) {
+                    hipLaunchKernelGGL((gadget_enumerate_kernel<LDR, RULE, true>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+                    return;
+                }
             }
-        }
-#undef GADGET_CASE
+            hipLaunchKernelGGL((gadget_enumerate_kernel<LDR, RULE, false>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+        });
         GF2_TRY(gf2_prof_end(ctx));
         GF2_HIP(hipGetLastError());
     }
@@ -200,23 +157,8 @@ int gf2_ec_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, i
                      int64_t first_rank, int64_t count, uint64_t* counts_out) {
     const char* who = "gf2_ec_enumerate";
     if (!ctx || !circuit || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (rounds < 1 || rounds > GF2_EC_MAX_ROUNDS) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= rounds <= %d, got %lld", who, GF2_EC_MAX_ROUNDS, (long long)rounds);
-    if (circuit->ldr > GF2_CIRCUIT_MAX_LDR)
-        GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per effect, got %lld", who, GF2_CIRCUIT_MAX_LDR, (long long)circuit->ldr);
-    if (circuit->ldr < rounds + 2)
-        GF2_FAIL(GF2_E_ARG, "%s: %lld rounds need ldr = 1 + rounds + F words with F >= 1 flag words, the circuit has %lld", who,
-                 (long long)rounds, (long long)circuit->ldr);
     GadgetEnumArgs a = {};
-    a.rounds = (int)rounds;
-    a.mask[0] = (1ull << r2) - 1;
-    a.mask[1] = (1ull << r1) - 1;
-    a.kwx = a.kwz = 1;
-    const u64 keys = a.mask[0] | a.mask[1] << 32;
-    bool beyond = (circuit->any[0] & ~(keys | 1ull << 31 | 1ull << 63)) != 0;
-    for (int64_t t = 1; t <= rounds; ++t) beyond |= (circuit->any[t] & ~keys) != 0;
-    if (beyond) GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits, the two parity bits and the flag words", who);
+    GF2_TRY(ec_rule_args(who, circuit, rounds, r1, r2, &a));
     return gadget_enumerate<RULE_EC>(who, ctx, circuit, a, keys1, flips1, entries1, keys2, flips2, entries2, w, first_rank, count, counts_out);
 }
 
@@ -225,29 +167,8 @@ int gf2_ft_enumerate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, u
                      int64_t w, int64_t first_rank, int64_t count, uint64_t* counts_out) {
     const char* who = "gf2_ft_enumerate";
     if (!ctx || !circuit || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (circuit->ldr < 8 || circuit->ldr > GF2_FT_MAX_LDR)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 8 <= ldr <= %d words per effect, got %lld", who, GF2_FT_MAX_LDR, (long long)circuit->ldr);
-    if (nsteps < 1 || circuit->ldr < nsteps + 1)
-        GF2_FAIL(GF2_E_ARG, "%s: needs nsteps >= 1 and ldr = nsteps + F words with F >= 1 flag words, got nsteps = %lld, the circuit has %lld", who,
-                 (long long)nsteps, (long long)circuit->ldr);
-    if (measure_mask >> nsteps) GF2_FAIL(GF2_E_ARG, "%s: measure_mask has bits at or above nsteps = %lld", who, (long long)nsteps);
-    const int trials = __builtin_popcountll(measure_mask);
-    if (trials % 2 == 0) GF2_FAIL(GF2_E_ARG, "%s: a majority vote needs an odd number of trials, measure_mask has %d", who, trials);
     GadgetEnumArgs a = {};
-    a.nsteps = (int)nsteps;
-    a.trials = trials;
-    a.first_measure = __builtin_ctzll(measure_mask);
-    a.measure_mask = (unsigned int)measure_mask;
-    a.mask[0] = (1ull << r2) - 1;
-    a.mask[1] = (1ull << r1) - 1;
-    a.kwx = a.kwz = 1;
-    bool beyond = false;
-    for (int64_t s = 0; s < nsteps; ++s)
-        beyond |= (circuit->any[s] & ~((measure_mask >> s) & 1ull ? a.mask[0] | 1ull << 31 : a.mask[0] | a.mask[1] << 32)) != 0;
-    if (beyond)
-        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key bits and bit 31)", who);
+    GF2_TRY(ft_rule_args(who, circuit, nsteps, measure_mask, r1, r2, &a));
     return gadget_enumerate<RULE_FT>(who, ctx, circuit, a, keys1, flips1, entries1, keys2, flips2, entries2, w, first_rank, count, counts_out);
 }
 

@@ -24,8 +24,6 @@
 
 #define GADGET_LAUNCH_CONFIGS (1ll << 28)      // configurations per launch, as gf2_gadget_enumerate.hip cuts them
 
-enum { RULE_EC = 0, RULE_FT = 1 };
-
 struct GadgetListArgs {
     const u64* eff;
     int locations, weight;
@@ -198,21 +196,12 @@ static int gadget_list(const char* who, gf2_ctx* ctx, const gf2_circuit* circuit
     for (int64_t done = 0; done < count; done += per_launch) {
         a.first_rank = (u64)(first_rank + done);
         a.count = count - done < per_launch ? count - done : per_launch;
-        int64_t run = a.count / ((int64_t)ENUM_MAX_BLOCKS * CIRC_THREADS);               // short runs until every lane has one
-        a.run = (int)(run < 1 ? 1 : run > ENUM_MAX_RUN ? ENUM_MAX_RUN : run);
-        int64_t blocks = gf2_cdiv(gf2_cdiv(a.count, a.run), CIRC_THREADS);
-        if (blocks > ENUM_MAX_BLOCKS) blocks = ENUM_MAX_BLOCKS;
+        unsigned blocks;
+        enum_launch_shape(a.count, &a.run, &blocks);
         GF2_TRY(gf2_prof_begin(ctx, GF2_K_SAMPLER));
-#define LIST_CASE(L) \
-    case L: hipLaunchKernelGGL((gadget_list_kernel<L, RULE>), dim3((unsigned)blocks), dim3(CIRC_THREADS), 0, ctx->stream, a); break;
-        if constexpr (RULE == RULE_EC) {
-            switch (circuit->ldr) { LIST_CASE(3) LIST_CASE(4) LIST_CASE(5) LIST_CASE(6) LIST_CASE(7) LIST_CASE(8) }
-        } else {
-            switch (circuit->ldr) {
-                LIST_CASE(8) LIST_CASE(9) LIST_CASE(10) LIST_CASE(11) LIST_CASE(12) LIST_CASE(13) LIST_CASE(14) LIST_CASE(15) LIST_CASE(16)
-            }
-        }
-#undef LIST_CASE
+        gadget_for_ldr<RULE>(circuit->ldr, [&](auto ldr) {
+            hipLaunchKernelGGL((gadget_list_kernel<decltype(ldr)::value, RULE>), dim3(blocks), dim3(CIRC_THREADS), 0, ctx->stream, a);
+        });
         GF2_TRY(gf2_prof_end(ctx));
         GF2_HIP(hipGetLastError());
     }
@@ -231,23 +220,8 @@ int gf2_ec_enumerate_list(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t roun
                           int64_t first_rank, int64_t count, uint64_t select, int64_t capacity, uint64_t* records_out, int64_t* found_out) {
     const char* who = "gf2_ec_enumerate_list";
     if (!ctx || !circuit || !found_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (rounds < 1 || rounds > GF2_EC_MAX_ROUNDS) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= rounds <= %d, got %lld", who, GF2_EC_MAX_ROUNDS, (long long)rounds);
-    if (circuit->ldr > GF2_CIRCUIT_MAX_LDR)
-        GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per effect, got %lld", who, GF2_CIRCUIT_MAX_LDR, (long long)circuit->ldr);
-    if (circuit->ldr < rounds + 2)
-        GF2_FAIL(GF2_E_ARG, "%s: %lld rounds need ldr = 1 + rounds + F words with F >= 1 flag words, the circuit has %lld", who,
-                 (long long)rounds, (long long)circuit->ldr);
     GadgetListArgs a = {};
-    a.rounds = (int)rounds;
-    a.mask[0] = (1ull << r2) - 1;
-    a.mask[1] = (1ull << r1) - 1;
-    a.kwx = a.kwz = 1;
-    const u64 keys = a.mask[0] | a.mask[1] << 32;
-    bool beyond = (circuit->any[0] & ~(keys | 1ull << 31 | 1ull << 63)) != 0;
-    for (int64_t t = 1; t <= rounds; ++t) beyond |= (circuit->any[t] & ~keys) != 0;
-    if (beyond) GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits, the two parity bits and the flag words", who);
+    GF2_TRY(ec_rule_args(who, circuit, rounds, r1, r2, &a));
     return gadget_list<RULE_EC>(who, ctx, circuit, a, keys1, flips1, entries1, keys2, flips2, entries2, w, first_rank, count, select, capacity,
                                 records_out, found_out);
 }
@@ -258,29 +232,8 @@ int gf2_ft_enumerate_list(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nste
                           int64_t* found_out) {
     const char* who = "gf2_ft_enumerate_list";
     if (!ctx || !circuit || !found_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (circuit->ldr < 8 || circuit->ldr > GF2_FT_MAX_LDR)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 8 <= ldr <= %d words per effect, got %lld", who, GF2_FT_MAX_LDR, (long long)circuit->ldr);
-    if (nsteps < 1 || circuit->ldr < nsteps + 1)
-        GF2_FAIL(GF2_E_ARG, "%s: needs nsteps >= 1 and ldr = nsteps + F words with F >= 1 flag words, got nsteps = %lld, the circuit has %lld", who,
-                 (long long)nsteps, (long long)circuit->ldr);
-    if (measure_mask >> nsteps) GF2_FAIL(GF2_E_ARG, "%s: measure_mask has bits at or above nsteps = %lld", who, (long long)nsteps);
-    const int trials = __builtin_popcountll(measure_mask);
-    if (trials % 2 == 0) GF2_FAIL(GF2_E_ARG, "%s: a majority vote needs an odd number of trials, measure_mask has %d", who, trials);
     GadgetListArgs a = {};
-    a.nsteps = (int)nsteps;
-    a.trials = trials;
-    a.first_measure = __builtin_ctzll(measure_mask);
-    a.measure_mask = (unsigned int)measure_mask;
-    a.mask[0] = (1ull << r2) - 1;
-    a.mask[1] = (1ull << r1) - 1;
-    a.kwx = a.kwz = 1;
-    bool beyond = false;
-    for (int64_t s = 0; s < nsteps; ++s)
-        beyond |= (circuit->any[s] & ~((measure_mask >> s) & 1ull ? a.mask[0] | 1ull << 31 : a.mask[0] | a.mask[1] << 32)) != 0;
-    if (beyond)
-        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key bits and bit 31)", who);
+    GF2_TRY(ft_rule_args(who, circuit, nsteps, measure_mask, r1, r2, &a));
     return gadget_list<RULE_FT>(who, ctx, circuit, a, keys1, flips1, entries1, keys2, flips2, entries2, w, first_rank, count, select, capacity,
                                 records_out, found_out);
 }

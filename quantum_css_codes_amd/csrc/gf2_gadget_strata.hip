@@ -31,8 +31,6 @@ static_assert(GADGET_STRATA_LAUNCH_SAMPLES / GADGET_STRATA_MAX_BLOCKS * GADGET_S
               "a workgroup's 32-bit bins (and so every lane's tallies) must hold a whole launch");
 static_assert(GF2_FT_MAX_LDR - 1 <= GADGET_STRATA_MAX_ADD && GF2_EC_MAX_ROUNDS <= GADGET_STRATA_MAX_ADD, "a sum field's value per sample");
 
-enum { STRATA_RULE_EC = 0, STRATA_RULE_FT = 1 };
-
 struct GadgetStrataArgs {
     const u64* eff;
     int locations, weight;
@@ -79,7 +77,7 @@ __device__ __forceinline__ void gadget_stratum_faults(const GadgetStrataArgs& a,
 
 template <int LDR, int RULE, bool STAGED = false>
 __global__ __launch_bounds__(CIRC_THREADS) void gadget_strata_kernel(GadgetStrataArgs a) {
-    constexpr int F = RULE == STRATA_RULE_EC ? GF2_EC_FIELDS : GF2_FT_FIELDS;
+    constexpr int F = RULE == RULE_EC ? GF2_EC_FIELDS : GF2_FT_FIELDS;
     extern __shared__ u64 gadget_strata_lds[];
     u64* eff_lds = gadget_strata_lds;
     unsigned int* bins = (unsigned int*)(eff_lds + (STAGED ? 2 * a.locations * LDR : 0));   // F
@@ -98,10 +96,10 @@ __global__ __launch_bounds__(CIRC_THREADS) void gadget_strata_kernel(GadgetStrat
 #pragma unroll
         for (int w = 0; w < LDR; ++w) out[w] = 0;
         gadget_stratum_faults<LDR>(a, eff, ks, out);
-        const u64 flags = RULE == STRATA_RULE_EC ? ec_flag_or<LDR>(a, out) : ft_flag_or<LDR>(a, out);
+        const u64 flags = RULE == RULE_EC ? ec_flag_or<LDR>(a, out) : ft_flag_or<LDR>(a, out);
         if (flags) continue;                                                       // a verification fired: the attempt is repeated
         local[0] += 1;
-        if constexpr (RULE == STRATA_RULE_EC) {
+        if constexpr (RULE == RULE_EC) {
             bool flip[2], miss[2];
             unsigned int unmatched[2] = {0, 0};
             ec_chain<LDR>(a, out, flip, miss, unmatched);
@@ -130,17 +128,6 @@ __global__ __launch_bounds__(CIRC_THREADS) void gadget_strata_kernel(GadgetStrat
     if (threadIdx.x < F && bins[threadIdx.x]) atomicAdd(&a.counts[threadIdx.x], (u64)bins[threadIdx.x]);
 }
 
-template <int LDR, int RULE>
-static void gadget_strata_launch_ldr(gf2_ctx* ctx, const GadgetStrataArgs& a, bool staged, unsigned blocks, size_t lds) {
-    if constexpr (RULE == STRATA_RULE_EC) {
-        if (staged) {
-            hipLaunchKernelGGL((gadget_strata_kernel<LDR, RULE, true>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((gadget_strata_kernel<LDR, RULE, false>), dim3(blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
-}
-
 // The strata of a call whose circuit and layout are checked: the strata arguments checked as gf2_mc_circuit_decode_strata checks
 // them, tables made once, every stratum cut into launches of at most GADGET_STRATA_LAUNCH_SAMPLES samples, the counts back once.
 template <int RULE>
@@ -148,7 +135,7 @@ static int gadget_strata(const char* who, gf2_ctx* ctx, const gf2_circuit* circu
                          const uint8_t* flips1, int64_t entries1, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed,
                          int64_t first_sample, int64_t nstrata, const int32_t* weights, const int64_t* counts, double k_x, double k_y,
                          double k_z, uint64_t* counts_out) {
-    constexpr int F = RULE == STRATA_RULE_EC ? GF2_EC_FIELDS : GF2_FT_FIELDS;
+    constexpr int F = RULE == RULE_EC ? GF2_EC_FIELDS : GF2_FT_FIELDS;
     GF2_TRY(circuit_check_tables(who, keys1, flips1, entries1, keys2, flips2, entries2));
     if (nstrata < 0 || nstrata > GF2_STRATA_MAX || (nstrata && (!weights || !counts)))
         GF2_FAIL(GF2_E_ARG, "%s: needs 0 <= nstrata <= %d and their weights and counts", who, GF2_STRATA_MAX);
@@ -170,9 +157,8 @@ static int gadget_strata(const char* who, gf2_ctx* ctx, const gf2_circuit* circu
     a.eff = circuit->eff_dev;
     a.locations = (int)circuit->locations;
     a.seed = seed;
-    const size_t eff_bytes = (size_t)2 * circuit->locations * circuit->ldr * 8;
-    const bool staged = RULE == STRATA_RULE_EC && eff_bytes <= CIRC_EFF_LDS_BYTES;      // (the measurement's tables never fit)
-    const size_t lds = (staged ? eff_bytes : 0) + (size_t)F * 4;
+    size_t lds;
+    const bool staged = circuit_staged(circuit, RULE == RULE_EC, (size_t)F * 4, &lds);   // (the measurement's tables never fit)
     for (int64_t s = 0; s < nstrata; ++s) {
         a.weight = (int)weights[s];
         a.counts = tables.counts_dev + F * s;
@@ -183,20 +169,16 @@ static int gadget_strata(const char* who, gf2_ctx* ctx, const gf2_circuit* circu
             if (blocks > GADGET_STRATA_MAX_BLOCKS) blocks = GADGET_STRATA_MAX_BLOCKS;
             if (blocks < 1) blocks = 1;
             GF2_TRY(gf2_prof_begin(ctx, GF2_K_SAMPLER));
-#define GADGET_STRATA_CASE(L) \
-    case L: gadget_strata_launch_ldr<L, RULE>(ctx, a, staged, (unsigned)blocks, lds); break;
-            if constexpr (RULE == STRATA_RULE_EC) {
-                switch (circuit->ldr) {
-                    GADGET_STRATA_CASE(3) GADGET_STRATA_CASE(4) GADGET_STRATA_CASE(5) GADGET_STRATA_CASE(6) GADGET_STRATA_CASE(7)
-                    GADGET_STRATA_CASE(8)
+            gadget_for_ldr<RULE>(circuit->ldr, [&](auto ldr) {
+                constexpr int LDR = decltype(ldr)::value;
+                if constexpr (RULE == RULE_EC) {
+                    if (staged) {
+                        hipLaunchKernelGGL((gadget_strata_kernel<LDR, RULE, true>), dim3((unsigned)blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+                        return;
+                    }
                 }
-            } else {
-                switch (circuit->ldr) {
-                    GADGET_STRATA_CASE(8) GADGET_STRATA_CASE(9) GADGET_STRATA_CASE(10) GADGET_STRATA_CASE(11) GADGET_STRATA_CASE(12)
-                    GADGET_STRATA_CASE(13) GADGET_STRATA_CASE(14) GADGET_STRATA_CASE(15) GADGET_STRATA_CASE(16)
-                }
-            }
-#undef GADGET_STRATA_CASE
+                hipLaunchKernelGGL((gadget_strata_kernel<LDR, RULE, false>), dim3((unsigned)blocks), dim3(CIRC_THREADS), lds, ctx->stream, a);
+            });
             GF2_TRY(gf2_prof_end(ctx));
             GF2_HIP(hipGetLastError());
         }
@@ -212,25 +194,10 @@ int gf2_mc_ec_decode_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t ro
                             const int64_t* counts, double k_x, double k_y, double k_z, uint64_t* counts_out) {
     const char* who = "gf2_mc_ec_decode_strata";
     if (!ctx || !circuit || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (rounds < 1 || rounds > GF2_EC_MAX_ROUNDS) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= rounds <= %d, got %lld", who, GF2_EC_MAX_ROUNDS, (long long)rounds);
-    if (circuit->ldr > GF2_CIRCUIT_MAX_LDR)
-        GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per sample, got %lld", who, GF2_CIRCUIT_MAX_LDR, (long long)circuit->ldr);
-    if (circuit->ldr < rounds + 2)
-        GF2_FAIL(GF2_E_ARG, "%s: %lld rounds need ldr = 1 + rounds + F words with F >= 1 flag words, the circuit has %lld", who,
-                 (long long)rounds, (long long)circuit->ldr);
     GadgetStrataArgs a = {};
-    a.rounds = (int)rounds;
-    a.mask[0] = (1ull << r2) - 1;
-    a.mask[1] = (1ull << r1) - 1;
-    a.kwx = a.kwz = 1;
-    const u64 keys = a.mask[0] | a.mask[1] << 32;
-    bool beyond = (circuit->any[0] & ~(keys | 1ull << 31 | 1ull << 63)) != 0;
-    for (int64_t t = 1; t <= rounds; ++t) beyond |= (circuit->any[t] & ~keys) != 0;
-    if (beyond) GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits, the two parity bits and the flag words", who);
-    return gadget_strata<STRATA_RULE_EC>(who, ctx, circuit, a, keys1, flips1, entries1, keys2, flips2, entries2, seed, first_sample, nstrata,
-                                         weights, counts, k_x, k_y, k_z, counts_out);
+    GF2_TRY(ec_rule_args(who, circuit, rounds, r1, r2, &a));
+    return gadget_strata<RULE_EC>(who, ctx, circuit, a, keys1, flips1, entries1, keys2, flips2, entries2, seed, first_sample, nstrata,
+                                  weights, counts, k_x, k_y, k_z, counts_out);
 }
 
 int gf2_mc_ft_decode_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, uint64_t measure_mask, int64_t r1,
@@ -239,31 +206,10 @@ int gf2_mc_ft_decode_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t ns
                             const int32_t* weights, const int64_t* counts, double k_x, double k_y, double k_z, uint64_t* counts_out) {
     const char* who = "gf2_mc_ft_decode_strata";
     if (!ctx || !circuit || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (circuit->ldr < 8 || circuit->ldr > GF2_FT_MAX_LDR)
-        GF2_FAIL(GF2_E_ARG, "%s: needs 8 <= ldr <= %d words per sample, got %lld", who, GF2_FT_MAX_LDR, (long long)circuit->ldr);
-    if (nsteps < 1 || circuit->ldr < nsteps + 1)
-        GF2_FAIL(GF2_E_ARG, "%s: needs nsteps >= 1 and ldr = nsteps + F words with F >= 1 flag words, got nsteps = %lld, the circuit has %lld", who,
-                 (long long)nsteps, (long long)circuit->ldr);
-    if (measure_mask >> nsteps) GF2_FAIL(GF2_E_ARG, "%s: measure_mask has bits at or above nsteps = %lld", who, (long long)nsteps);
-    const int trials = __builtin_popcountll(measure_mask);
-    if (trials % 2 == 0) GF2_FAIL(GF2_E_ARG, "%s: a majority vote needs an odd number of trials, measure_mask has %d", who, trials);
     GadgetStrataArgs a = {};
-    a.nsteps = (int)nsteps;
-    a.trials = trials;
-    a.first_measure = __builtin_ctzll(measure_mask);
-    a.measure_mask = (unsigned int)measure_mask;
-    a.mask[0] = (1ull << r2) - 1;
-    a.mask[1] = (1ull << r1) - 1;
-    a.kwx = a.kwz = 1;
-    bool beyond = false;
-    for (int64_t s = 0; s < nsteps; ++s)
-        beyond |= (circuit->any[s] & ~((measure_mask >> s) & 1ull ? a.mask[0] | 1ull << 31 : a.mask[0] | a.mask[1] << 32)) != 0;
-    if (beyond)
-        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key bits and bit 31)", who);
-    return gadget_strata<STRATA_RULE_FT>(who, ctx, circuit, a, keys1, flips1, entries1, keys2, flips2, entries2, seed, first_sample, nstrata,
-                                         weights, counts, k_x, k_y, k_z, counts_out);
+    GF2_TRY(ft_rule_args(who, circuit, nsteps, measure_mask, r1, r2, &a));
+    return gadget_strata<RULE_FT>(who, ctx, circuit, a, keys1, flips1, entries1, keys2, flips2, entries2, seed, first_sample, nstrata,
+                                  weights, counts, k_x, k_y, k_z, counts_out);
 }
 
 }  // extern "C"

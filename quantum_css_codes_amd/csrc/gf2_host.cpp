@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "gf2hip.h"
+#include "gf2_gadget_rule.h"
 
 static thread_local char g_error[512] = "";
 
@@ -585,27 +586,16 @@ int list_check_args(const char* who, uint64_t select, uint64_t class_bits, int64
     return GF2_OK;
 }
 
-// The argument rules gf2_ec_tally_host and gf2_ec_enumerate_host share ...
+// The layout rule of the cycle's host statements (gf2_gadget_rule.h: the device entry points' own) ...
 int ec_check_layout(const char* who, int64_t ldr, int64_t rounds, int64_t r1, int64_t r2) {
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (rounds < 1 || rounds > GF2_EC_MAX_ROUNDS) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= rounds <= %d, got %lld", who, GF2_EC_MAX_ROUNDS, (long long)rounds);
-    if (ldr > GF2_CIRCUIT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per sample, got %lld", who, GF2_CIRCUIT_MAX_LDR, (long long)ldr);
-    if (ldr < rounds + 2)
-        GF2_FAIL(GF2_E_ARG, "%s: %lld rounds need ldr = 1 + rounds + F words with F >= 1 flag words, got %lld", who, (long long)rounds, (long long)ldr);
-    return GF2_OK;
+    GadgetRule rule;
+    return ec_rule_layout(who, ldr, rounds, r1, r2, &rule);
 }
 
-// ... and those of gf2_ft_tally_host and gf2_ft_enumerate_host.
+// ... and of the measurement's, which take tables of any number of words up to GF2_FT_MAX_LDR.
 int ft_check_layout(const char* who, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1, int64_t r2) {
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    if (ldr > GF2_FT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs ldr <= %d words per sample, got %lld", who, GF2_FT_MAX_LDR, (long long)ldr);
-    if (nsteps < 1 || ldr < nsteps + 1)
-        GF2_FAIL(GF2_E_ARG, "%s: needs nsteps >= 1 and ldr = nsteps + F words with F >= 1 flag words, got nsteps = %lld and ldr = %lld", who,
-                 (long long)nsteps, (long long)ldr);
-    if (measure_mask >> nsteps) GF2_FAIL(GF2_E_ARG, "%s: measure_mask has bits at or above nsteps = %lld", who, (long long)nsteps);
-    const int trials = __builtin_popcountll(measure_mask);
-    if (trials % 2 == 0) GF2_FAIL(GF2_E_ARG, "%s: a majority vote needs an odd number of trials, measure_mask has %d", who, trials);
-    return GF2_OK;
+    GadgetRule rule;
+    return ft_rule_layout(who, ldr, 0, nsteps, measure_mask, r1, r2, &rule);
 }
 
 int check_table_args(const char* who, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, const uint64_t* keys2,
@@ -629,29 +619,23 @@ int make_host_tables(const char* who, HostTable* tab, const uint64_t* keys1, con
 
 // No effect of the cycle's table may set a bit outside the layout (the layout already checked) ...
 int ec_check_effects(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, int64_t r2) {
-    const uint64_t keys = ((1ull << r2) - 1) | ((1ull << r1) - 1) << 32;
+    GadgetRule rule;
+    if (int rc = gadget_rule_keys(who, r1, r2, &rule)) return rc;
     uint64_t any[GF2_CIRCUIT_MAX_LDR] = {0};
     for (int64_t i = 0; i < 2 * locations; ++i)
         for (int64_t q = 0; q < ldr; ++q) any[q] |= eff[i * ldr + q];
-    bool beyond = (any[0] & ~(keys | 1ull << 31 | 1ull << 63)) != 0;
-    for (int64_t t = 1; t <= rounds; ++t) beyond |= (any[t] & ~keys) != 0;
-    if (beyond) GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the keys' r_2 / r_1 bits, the two parity bits and the flag words", who);
-    return GF2_OK;
+    return ec_rule_effects(who, any, rounds, rule);
 }
 
 // ... nor one of the measurement's.
 int ft_check_effects(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
                      int64_t r2) {
-    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    GadgetRule rule;
+    if (int rc = gadget_rule_keys(who, r1, r2, &rule)) return rc;
     uint64_t any[GF2_FT_MAX_LDR] = {0};
     for (int64_t i = 0; i < 2 * locations; ++i)
         for (int64_t q = 0; q < ldr; ++q) any[q] |= eff[i * ldr + q];
-    bool beyond = false;
-    for (int64_t s = 0; s < nsteps; ++s)
-        beyond |= (any[s] & ~((measure_mask >> s) & 1ull ? mask[0] | 1ull << 31 : mask[0] | mask[1] << 32)) != 0;
-    if (beyond)
-        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key bits and bit 31)", who);
-    return GF2_OK;
+    return ft_rule_effects(who, any, nsteps, measure_mask, rule);
 }
 
 // The argument rules gf2_ec_enumerate_host and gf2_ec_enumerate_list_host share (eff not null) ...
@@ -1119,8 +1103,9 @@ int gf2_stream_plan(const char* who, const uint64_t* type_eff, const int64_t* ty
 }
 
 int gf2_stream_check_bits(const char* who, const StreamPlan& plan, int64_t r1, int64_t r2) {
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
-    const uint64_t key_x = (1ull << r2) - 1, keys = key_x | ((1ull << r1) - 1) << 32;
+    GadgetRule rule;
+    if (int rc = gadget_rule_keys(who, r1, r2, &rule)) return rc;
+    const uint64_t key_x = rule.mask[0], keys = key_x | rule.mask[1] << 32;
     if (plan.any_local[GF2_STREAM_NONE] || (plan.any_local[GF2_STREAM_EC] & ~keys) || (plan.any_local[GF2_STREAM_MEASURE] & ~(key_x | 1ull << 31)) ||
         (plan.any_tail & ~(keys | 1ull << 31 | 1ull << 63)))
         GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (a NONE block no local bit, an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key "
@@ -1251,7 +1236,8 @@ int gf2_stream_tally_host(const uint64_t* words, int64_t count, int64_t ldw, con
                           const uint8_t* flips2, int64_t entries2, uint64_t* counts_out, uint8_t* class_out) {
     const char* who = "gf2_stream_tally_host";
     if (!counts_out || !block_kind) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (r1 < 1 || r2 < 1 || r1 > 31 || r2 > 31) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= r_1, r_2 <= 31 (the keys share a word), got %lld and %lld", who, (long long)r1, (long long)r2);
+    GadgetRule rule;
+    if (int rc = gadget_rule_keys(who, r1, r2, &rule)) return rc;
     if (nblocks < 1 || nblocks > GF2_CIRCUIT_MAX_LOCATIONS + 1)
         GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= nblocks <= %d blocks, got %lld", who, GF2_CIRCUIT_MAX_LOCATIONS + 1, (long long)nblocks);
     std::vector<int> kinds;
@@ -1281,9 +1267,8 @@ int gf2_stream_tally_host(const uint64_t* words, int64_t count, int64_t ldw, con
     if (count == 0) return GF2_OK;
     HostTable tab[2];
     if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
-    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
     for (int64_t i = 0; i < count; ++i) {
-        const uint8_t cls = stream_tally_sample(words + i * ldw, kinds, flag_words, trials, mask, tab, counts_out);
+        const uint8_t cls = stream_tally_sample(words + i * ldw, kinds, flag_words, trials, rule.mask, tab, counts_out);
         if (class_out) class_out[i] = cls;
     }
     return GF2_OK;
