@@ -1507,6 +1507,135 @@ def test_transform_stabilisers_runs_of_cnots_with_one_control(n):
     assert refused                                                          # the last trial must have exercised the refusal
 
 
+def conjugate_both(mat, gates):
+    """css_code.transform_stabilisers and the restatement of css_code.py:737-781 on copies of mat: (got, want, refused); both must
+    refuse, or neither."""
+    want, got = mat.copy(), mat.copy()
+    try:
+        cpu_ref.transform_stabilisers(want, gates)
+        refused = False
+    except NotImplementedError:
+        refused = True
+    if refused:
+        with pytest.raises(NotImplementedError, match="only handles CSS codes"):
+            css_code.transform_stabilisers(got, gates)
+    else:
+        css_code.transform_stabilisers(got, gates)
+    return got, want, refused
+
+
+def css_rows(rng, k, n):
+    """k rows, all X or all Z."""
+    mat = np.zeros((k, 2 * n), dtype=int)
+    mat[: k // 2, n:] = rng.integers(0, 2, (k // 2, n))
+    mat[k // 2:, :n] = rng.integers(0, 2, (k - k // 2, n))
+    return mat
+
+
+@pytest.mark.parametrize("k, n", [(130, 4100), (70, 10240)])
+def test_transform_stabilisers_beyond_64_kib_of_lds(k, n):
+    # conjugate_kernel keeps 512 bytes of LDS per word of 2n bits: 129 words (n = 4100) are the first size beyond the 64 KiB a kernel
+    # has without asking, 320 words (n = 10240) are the limit, 160 KiB; three and two workgroups.  Gate lists as in the test above,
+    # the runs capped at 300 targets (the restatement costs gates x rows): targets in the control's own word, a target named twice,
+    # CNOT(c, c), H gates between runs, and targets on the last qubits, whose Z columns lie in the matrix's last word
+    rng = np.random.default_rng(1000 * k + n)
+    words = -(-2 * n // 64)
+    assert words * 512 > 65536 and words <= 320 and k > 64
+    gates = []
+    for run in range(10):
+        c = int(rng.integers(0, n))
+        targets = [int(t) for t in rng.permutation(n)[: int(rng.integers(1, 301))]]
+        if run % 2 == 0:
+            targets += [n - 1, n - 3, n - 64]                               # the top word of each half
+        own = [q for q in ((c & ~63) + j for j in (0, 5, 63)) if q < n]     # inside the control's own word: not folded
+        gates += [(1, c, t) for t in targets[:100] + own + targets[100:]]
+        if run % 3 == 0:
+            gates.append((1, c, targets[0]))                                # named twice
+        if run % 4 == 1:
+            gates.append((1, c, c))
+        if run % 2 == 0:
+            gates.append((0, int(rng.integers(0, n)), 0))
+        gates.append((1, int(rng.integers(0, n)), int(rng.integers(0, n))))
+    # one run whose every target lies outside the control's word, a target named twice inside it: the host cancels it in the run's mask
+    gates += [(1, 1, t) for t in (70, 200, n - 2, 70, 64 * ((n - 1) >> 6), 200, 201)]
+    gates.append((0, n - 1, 0))                                             # H on the last qubit: the last bit of both halves
+    gates = np.array(gates, dtype=np.int32)
+    assert ((gates[:, 0] == 1) & (gates[:, 2] >> 6 == (n - 1) >> 6)).any()
+    got, want, refused = conjugate_both(css_rows(rng, k, n), gates)
+    assert np.array_equal(got & 1, want & 1) and not refused, (k, n)
+    # ... and rows that carry both X and Z: the first H is refused, after the first run
+    mixed = rng.integers(0, 2, (k, 2 * n))
+    got, want, refused = conjugate_both(mixed, gates)
+    assert np.array_equal(got & 1, want & 1) and refused and not np.array_equal(want, mixed), (k, n)
+
+
+def test_transform_stabilisers_refuses_more_than_20480_columns():
+    n = 10241
+    mat = css_rows(np.random.default_rng(3), 4, n)
+    before = mat.copy()
+    with pytest.raises(_native.GF2Error, match="exceed") as refused:
+        css_code.transform_stabilisers(mat, np.array([(1, 0, n - 1), (0, 5, 0)], dtype=np.int32))
+    assert refused.value.code == _native.GF2_E_ARG and "gf2_conjugate_gates" in refused.value.message
+    assert np.array_equal(mat, before)
+
+
+def test_transform_stabilisers_two_workgroups_refuse_different_gates():
+    # three workgroups of 64 rows; the first has a Y on qubit 5, the third a Y on qubit 9, and each of the two H gates is refused by
+    # one of them only.  The walk must stop at the earlier gate, whichever workgroup meets it, with the matrix the reference leaves.
+    k, n = 200, 70
+    rng = np.random.default_rng(200)
+    mat = css_rows(rng, k, n)
+    mat[10, [5, n + 5]] = 1
+    mat[150, [9, n + 9]] = 1
+    others = [q for q in range(n) if q not in (5, 9)]                       # no CNOT touches the two qubits: their columns stay
+    ctx = _native.default_context()
+    for first_h, second_h in ((9, 5), (5, 9)):
+        gates = [(1, 3, t) for t in range(64, 70)]                          # a folded run: entries and gates number differently
+        while len(gates) < 101:
+            if len(gates) in (40, 90):
+                gates.append((0, first_h if len(gates) == 40 else second_h, 0))
+            else:
+                c, t = (int(q) for q in rng.choice(others, 2, replace=False))
+                gates.append((1, c, t))
+        gates = np.array(gates, dtype=np.int32)
+        assert gates[40].tolist() == [0, first_h, 0] and gates[90].tolist() == [0, second_h, 0] and np.count_nonzero(gates[:, 0] == 0) == 2
+        packed = _native.pack_rows(mat)
+        rc, stop = ctx.conjugate_gates(packed, k, n, gates)
+        assert (rc, stop) == (_native.GF2_E_NOTCSS, 40), (first_h, rc, stop)
+        prefix = mat.copy()
+        cpu_ref.transform_stabilisers(prefix, gates[:40])
+        assert np.array_equal(_native.unpack_rows(packed, 2 * n), prefix)   # the accepted prefix, replayed on the original
+        got, want, refused = conjugate_both(mat, gates)
+        assert np.array_equal(got & 1, want & 1) and refused, first_h
+
+
+@pytest.mark.parametrize("length", [63, 64, 65, 127, 128, 129])
+def test_transform_stabilisers_gate_fetch_edges(length):
+    # the kernel fetches 64 entries of the folded list at a time, the next 64 in flight: lists the host cannot fold (H gates, and
+    # CNOTs whose target lies in the control's own 64-column word), so that the device sees exactly `length` entries.  The CNOTs
+    # stay on qubits 0 .. 59 and 66 .. 69, the H gates on 60 .. 65, so that no row ever has both X and Z on a qubit: nothing is
+    # refused, and the last entry is an H that changes the matrix.
+    k = n = 70
+    rng = np.random.default_rng(length)
+    gates = []
+    while len(gates) < length - 1:
+        if len(gates) % 7 == 3:
+            gates.append((0, int(rng.integers(60, 66)), 0))
+        else:
+            lo, hi = ((0, 60), (66, 70))[len(gates) % 5 == 0]
+            c, t = (int(q) for q in rng.choice(np.arange(lo, hi), 2, replace=False))
+            gates.append((1, c, t))
+    gates.append((0, 64, 0))
+    gates = np.array(gates, dtype=np.int32)
+    assert len(gates) == length and all(kind == 0 or a >> 6 == b >> 6 for kind, a, b in gates.tolist())
+    mat = css_rows(rng, k, n)
+    got, want, refused = conjugate_both(mat, gates)
+    assert np.array_equal(got & 1, want & 1) and not refused
+    short = mat.copy()
+    cpu_ref.transform_stabilisers(short, gates[:-1])
+    assert not np.array_equal(short, want)                                  # dropping the last entry would show
+
+
 def test_steane_encoders_known_answers(steane_h):
     # test/test_css_code.py:61-106
     code = css_code.CSSCode(steane_h, steane_h)
