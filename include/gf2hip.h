@@ -13,6 +13,18 @@
  *     a thread-local human-readable message for the last failure on the calling thread.
  *   - Packed layout: row-major uint64_t words, column j in word j>>6 at bit j&63, `ld` words per
  *     row (ld >= ceil(n/64)).  Pad bits (columns >= n) must be zero on input and are zero on output.
+ *   - Device buffers (tests/test_gpu_state.py holds the library to each of these):
+ *       outputs need no initialisation: every word an entry point promises is stored, whatever it is (an all-zero syndrome
+ *       too), and nothing is written outside the buffer;
+ *       pitch padding (words of a row past the ones promised, when a pitch is larger than needed) is either left as it was
+ *       or zeroed, and exactly left as it was where an entry point says so (the outcome stores); it is never read;
+ *       histograms (hist_dev) are ACCUMULATED into: the caller zeroes the bins before the first call, and calls add up;
+ *       alignment: every device pointer must be 8-byte aligned (4-byte for status_dev); "any 8-byte-aligned address" at an
+ *       argument below means that nothing more is asked -- a kernel that has a 16-byte path picks it by looking at the
+ *       pointer and the pitch -- and "16-byte aligned" that the entry point refuses anything else with GF2_E_ARG (the
+ *       tiled layout and the blocked eliminations are read and written as 16-byte pieces).  gf2_dev_alloc, hipMalloc and
+ *       torch allocations are aligned to 256 bytes or more.  DESIGN.md "State between calls" lists the wide accesses.
+ *       No result depends on what the context's workspaces, or any device buffer of the library, held before a call.
  *   - "host" pointers are caller-owned host memory; the library never keeps them past return.
  *     "dev" pointers are device memory from gf2_dev_alloc (or any hipMalloc'ed / torch-allocated
  *     buffer on the context's device).
@@ -83,6 +95,13 @@ int gf2_ctx_get_flags(gf2_ctx* ctx, uint32_t* flags_out);
 /* (Further option numbers, used by the A/B scripts: quantum_css_codes_amd/csrc/gf2_tuning.h.) */
 int gf2_ctx_set_option(gf2_ctx* ctx, int option, int64_t value);
 
+/* ---- testing ----
+ * Sets every byte of the context's workspaces (four slots that only grow and are never cleared between calls) to `byte`
+ * (0..255), after waiting for all of the context's streams, and waits for the fills.  slot_bytes_out (four int64, may be null)
+ * receives the slots' sizes.  No result of this library depends on what the workspaces hold between calls; the test suite
+ * shows it by calling this between two identical calls.  GF2_E_ARG for a null context or a byte outside 0..255. */
+int gf2_ctx_fill_workspace(gf2_ctx* ctx, int byte, int64_t* slot_bytes_out /* 4, may be null */);
+
 /* Device memory and stream-ordered copies on the context's stream (copies are synchronous). */
 int gf2_dev_alloc(gf2_ctx* ctx, size_t bytes, void** dev_out);
 int gf2_dev_free(gf2_ctx* ctx, void* dev);
@@ -134,8 +153,13 @@ int gf2_rref_batch(gf2_ctx* ctx, uint64_t* a, int64_t batch, int64_t m, int64_t 
                    int64_t* pivots_out, int64_t* rank_out);
 
 /* Device-resident forms (asynchronous on the context's stream).  pivots_dev: batch x min(m,n) int64
- * (may be null); rank_dev: batch int64.  gf2_normalize_dev: swaps_dev capacity 2*r int64, nswaps_dev one
- * int64, status_dev one int (0 = ok, 1 = rows are not independent). */
+ * (may be null); the first rank entries of a row are written, the others are left as they were or zeroed; rank_dev: batch
+ * int64.  gf2_normalize_dev: swaps_dev capacity 2*r int64 (the first 2 * *nswaps_dev are written), nswaps_dev one
+ * int64, status_dev one int (0 = ok, 1 = rows are not independent).
+ * Alignment.  a_dev: any 8-byte-aligned address for matrices of at most 256 rows with ld <= 16 and ceil(m/64) * ld <= 32 (one
+ * wavefront per matrix; contiguous rows at a 16-byte-aligned address are moved as 16-byte pieces), 16-byte aligned otherwise
+ * (the blocked routes).  h_dev: 16-byte aligned.  pivots_dev, rank_dev, swaps_dev, nswaps_dev: any 8-byte-aligned address;
+ * status_dev: any 4-byte-aligned address. */
 int gf2_rref_batch_dev(gf2_ctx* ctx, uint64_t* a_dev, int64_t batch, int64_t m, int64_t n, int64_t ld,
                        int64_t* pivots_dev, int64_t* rank_dev);
 int gf2_normalize_dev(gf2_ctx* ctx, uint64_t* h_dev, int64_t r, int64_t n, int64_t ld, int64_t offset,
@@ -221,7 +245,8 @@ int gf2_check_destroy(gf2_ctx* ctx, gf2_check* check);
 /* Tiled layout helpers: words per sample (even, >= ceil(n/64)) and words of a buffer for `batch` samples. */
 int64_t gf2_tiled_ld(int64_t n);
 int64_t gf2_tiled_words(int64_t n, int64_t batch);
-/* Sample-major (batch x lde) -> tiled, both on the device; asynchronous. */
+/* Sample-major (batch x lde) -> tiled, both on the device; asynchronous.  Every word of the gf2_tiled_words(n, batch) is written
+ * (pad samples and the pad word are zero).  e_dev: any 8-byte-aligned address; tiled_dev: 16-byte aligned. */
 int gf2_retile_dev(gf2_ctx* ctx, const uint64_t* e_dev, int64_t batch, int64_t lde, int64_t n, uint64_t* tiled_dev);
 
 /* Host buffers, synchronous. */
@@ -235,7 +260,10 @@ int gf2_syndrome_batch(gf2_ctx* ctx, const uint64_t* h, int64_t r, int64_t n, in
  *               GF2_LAYOUT_TILED to avoid it.
  * Tiled:        e_dev as described at GF2_LAYOUT_TILED (lde ignored); s_dev is slab-major: ceil(r/64) rows
  *               of lds >= batch words.
- * Bit-sliced:   e_dev is n x lde with lde >= ceil(batch/64); s_dev is r x lds, lds >= ceil(batch/64). */
+ * Bit-sliced:   e_dev is n x lde with lde >= ceil(batch/64); s_dev is r x lds, lds >= ceil(batch/64).
+ * Words of a row of s_dev past the ones named are left as they were.  e_dev: 16-byte aligned in the tiled layout, else any
+ * 8-byte-aligned address; s_dev: any 8-byte-aligned address (n, r <= 64: one word per sample, or even bit-sliced pitches,
+ * at 16-byte-aligned addresses take 16-byte accesses). */
 int gf2_syndrome_dev(gf2_ctx* ctx, const gf2_check* check, const uint64_t* e_dev, int64_t batch, int64_t lde,
                      int layout, uint64_t* s_dev, int64_t lds);
 
@@ -248,14 +276,15 @@ int gf2_syndrome_dev(gf2_ctx* ctx, const gf2_check* check, const uint64_t* e_dev
  * records), with or without syndromes stored (since round 4 every gather workgroup stores its slab's 64-byte piece); checks
  * with n <= 512 and r <= 256 the lane-per-sample kernel; everything else one wavefront per sample gathering columns of the
  * transposed check from L2.  Words of a syndrome row past ceil(r/64) (lds larger than needed) are either left as they were
- * or zeroed. */
+ * or zeroed.  e_dev, s_dev, hist_dev: any 8-byte-aligned address (the slab pipeline runs its hand-scheduled gather kernel when
+ * e_dev -- and s_dev, if given -- are 16-byte aligned with even pitches, its compiler-scheduled one otherwise). */
 int gf2_syndrome_sparse_dev(gf2_ctx* ctx, const gf2_check* check, const uint64_t* e_dev, int64_t batch, int64_t lde,
                             uint64_t* s_dev, int64_t lds, uint64_t* hist_dev, int64_t nbins);
 
 /* Histogram of packed syndromes (device), accumulated into hist_dev (uint64 bins).  layout
  * GF2_LAYOUT_SAMPLE_MAJOR: s_dev is batch x lds; GF2_LAYOUT_TILED: slab-major as written by gf2_syndrome_dev for
  * tiled errors (lds >= batch).  mode GF2_HIST_FULL needs r <= 24 and nbins == 2^r; GF2_HIST_WEIGHT needs
- * nbins == r+1. */
+ * nbins == r+1.  s_dev, hist_dev: any 8-byte-aligned address. */
 int gf2_histogram_dev(gf2_ctx* ctx, const uint64_t* s_dev, int64_t batch, int64_t lds, int layout, int64_t r,
                       int mode, uint64_t* hist_dev, int64_t nbins);
 
@@ -265,7 +294,8 @@ int gf2_histogram_dev(gf2_ctx* ctx, const uint64_t* s_dev, int64_t batch, int64_
  * parity_check_c2, Z errors by parity_check_c1 (css_code.py:457-470). */
 
 /* Writes packed errors for samples first_sample .. first_sample+count-1.  layout GF2_LAYOUT_SAMPLE_MAJOR:
- * count x lde; GF2_LAYOUT_TILED: gf2_tiled_words(n, count) words (lde ignored; pad samples are zero). */
+ * count x lde; GF2_LAYOUT_TILED: gf2_tiled_words(n, count) words (lde ignored; pad samples are zero).  Sample-major: words of a
+ * row past ceil(n/64) are zeroed or left as they were; ex_dev, ez_dev: any 8-byte-aligned address.  Tiled: 16-byte aligned. */
 int gf2_sample_errors_dev(gf2_ctx* ctx, int64_t n, uint64_t seed, int64_t first_sample, int64_t count,
                           double p_x, double p_y, double p_z,
                           uint64_t* ex_dev, uint64_t* ez_dev, int64_t lde, int layout);
@@ -362,7 +392,7 @@ int gf2_circuit_create(gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int
 int gf2_circuit_destroy(gf2_ctx* ctx, gf2_circuit* circuit);
 
 /* Outcome words of samples first_sample .. first_sample + count - 1: out_dev is count x ldo (ldo >= ldr), sample-major; words
- * past ldr are left as they were.  Asynchronous on the context's stream. */
+ * past ldr are left as they were.  Asynchronous on the context's stream.  out_dev: any 8-byte-aligned address. */
 int gf2_circuit_outcomes_dev(gf2_ctx* ctx, const gf2_circuit* circuit, uint64_t seed, int64_t first_sample, int64_t count,
                              double p_x, double p_y, double p_z, uint64_t* out_dev, int64_t ldo);
 
@@ -495,7 +525,8 @@ int gf2_ft_tally_host(const uint64_t* words, int64_t count, int64_t ldw, int64_t
  * gf2_mc_ft_decode only: every other entry point refuses it with GF2_E_ARG. */
 int gf2_ft_circuit_create(gf2_ctx* ctx, const uint64_t* eff, int64_t locations, int64_t ldr, gf2_circuit** circuit_out);
 
-/* gf2_circuit_outcomes_dev for 1 <= ldr <= GF2_FT_MAX_LDR (the rewritten program run once per sample, test_fidelity.py's loop). */
+/* gf2_circuit_outcomes_dev for 1 <= ldr <= GF2_FT_MAX_LDR (the rewritten program run once per sample, test_fidelity.py's loop):
+ * words past ldr are left as they were; out_dev: any 8-byte-aligned address. */
 int gf2_ft_outcomes_dev(gf2_ctx* ctx, const gf2_circuit* circuit, uint64_t seed, int64_t first_sample, int64_t count, double p_x,
                         double p_y, double p_z, uint64_t* out_dev, int64_t ldo);
 
@@ -722,7 +753,7 @@ int gf2_stream_create(gf2_ctx* ctx, const uint64_t* type_eff, const int64_t* typ
 int gf2_stream_destroy(gf2_ctx* ctx, gf2_stream* stream);
 
 /* The stream-layout words of samples first_sample .. first_sample + count - 1, rejected ones included: ldo >= nsteps + F words per
- * sample in device memory. */
+ * sample in device memory; words past nsteps + F are left as they were.  out_dev: any 8-byte-aligned address. */
 int gf2_stream_outcomes_dev(gf2_ctx* ctx, const gf2_stream* stream, uint64_t seed, int64_t first_sample, int64_t count, double p_x,
                             double p_y, double p_z, uint64_t* out_dev, int64_t ldo);
 

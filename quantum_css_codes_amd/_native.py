@@ -68,6 +68,7 @@ SIGNATURES = {
     "gf2_ctx_set_flags": [_p, ctypes.c_uint32],
     "gf2_ctx_get_flags": [_p, ctypes.POINTER(ctypes.c_uint32)],
     "gf2_ctx_set_option": [_p, ctypes.c_int, _c_i64],
+    "gf2_ctx_fill_workspace": [_p, ctypes.c_int, _p],
     "gf2_dev_alloc": [_p, ctypes.c_size_t, _pp],
     "gf2_dev_free": [_p, _p],
     "gf2_dev_zero": [_p, _p, ctypes.c_size_t],
@@ -780,6 +781,12 @@ class Context(object):
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)
+
+    def fill_workspace(self, byte):
+        """Testing: every byte of the four workspace slots set to `byte`; returns the slots' sizes in bytes."""
+        sizes = np.zeros(4, dtype=np.int64)
+        check(lib().gf2_ctx_fill_workspace(self.handle, int(byte), _ptr(sizes)))
+        return [int(v) for v in sizes]
 
     # -- routing ----------------------------------------------------------------------------------------
     def get_flags(self):

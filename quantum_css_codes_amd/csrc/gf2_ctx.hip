@@ -196,6 +196,23 @@ int gf2_ctx_sync(gf2_ctx* ctx) {
     return GF2_OK;
 }
 
+// Testing: every workspace slot set to one byte, so that a test can show that no result depends on what an earlier call left
+// there.  Waits for all four streams first and for the fills afterwards; launches no kernel.
+int gf2_ctx_fill_workspace(gf2_ctx* ctx, int byte, int64_t* slot_bytes_out) {
+    if (!ctx) GF2_FAIL(GF2_E_ARG, "gf2_ctx_fill_workspace: null context");
+    if (byte < 0 || byte > 255) GF2_FAIL(GF2_E_ARG, "gf2_ctx_fill_workspace: byte %d outside 0..255", byte);
+    GF2_TRY(gf2_ctx_activate(ctx));
+    GF2_HIP(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 2; ++k) GF2_HIP(hipStreamSynchronize(ctx->side[k]));
+    GF2_HIP(hipStreamSynchronize(ctx->hi));
+    for (int k = 0; k < 4; ++k) {
+        if (ctx->ws[k] && ctx->ws_bytes[k]) GF2_HIP(hipMemsetAsync(ctx->ws[k], byte, ctx->ws_bytes[k], ctx->stream));
+        if (slot_bytes_out) slot_bytes_out[k] = (int64_t)ctx->ws_bytes[k];
+    }
+    GF2_HIP(hipStreamSynchronize(ctx->stream));
+    return GF2_OK;
+}
+
 int gf2_dev_alloc(gf2_ctx* ctx, size_t bytes, void** dev_out) {
     if (!ctx || !dev_out) GF2_FAIL(GF2_E_ARG, "gf2_dev_alloc: null argument");
     GF2_TRY(gf2_ctx_activate(ctx));

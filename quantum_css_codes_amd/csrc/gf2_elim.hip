@@ -3286,6 +3286,9 @@ static int launch_rref_blocked(gf2_ctx* ctx, u64* a_dev, int64_t batch, int64_t 
 
 int gf2_rref_batch_dev(gf2_ctx* ctx, uint64_t* a_dev, int64_t batch, int64_t m, int64_t n, int64_t ld,
                        int64_t* pivots_dev, int64_t* rank_dev) {
+    // (the blocked routes move rows as 16-byte pieces; the small-matrix kernels take any 8-byte-aligned address)
+    if ((reinterpret_cast<uintptr_t>(a_dev) & 15) && !(m <= 256 && ld <= 16 && gf2_cdiv(m, 64) * ld <= 32))
+        GF2_FAIL(GF2_E_ARG, "gf2_rref_batch_dev: matrices of more than 256 rows or 16 words per row must be 16-byte aligned");
     if (!ctx) GF2_FAIL(GF2_E_ARG, "gf2_rref_batch_dev: null context");
     if (batch < 0 || m < 0 || n < 0 || ld < gf2_words(n)) GF2_FAIL(GF2_E_ARG, "gf2_rref_batch_dev: bad shape");
     if (!rank_dev) GF2_FAIL(GF2_E_ARG, "gf2_rref_batch_dev: null rank buffer");
@@ -3315,8 +3318,11 @@ int gf2_rref_batch_dev(gf2_ctx* ctx, uint64_t* a_dev, int64_t batch, int64_t m, 
         }
 #undef GF2_SMALL
     }
-    if (m < 0x7fffffffLL && batch <= 65535 && gf2_cdiv(m, 128) <= 65535 && !gf2_flag(ctx, GF2_F_RREF_SEQUENTIAL))
+    if (m < 0x7fffffffLL && batch <= 65535 && gf2_cdiv(m, 128) <= 65535 && !gf2_flag(ctx, GF2_F_RREF_SEQUENTIAL)) {
+        if (reinterpret_cast<uintptr_t>(a_dev) & 15)                   // (a small matrix sent here by GF2_F_RREF_NO_SMALL)
+            GF2_FAIL(GF2_E_ARG, "gf2_rref_batch_dev: the blocked routes need 16-byte aligned matrices");
         return launch_rref_blocked(ctx, (u64*)a_dev, batch, m, n, ld, pivots_dev, cap, rank_dev);
+    }
     return launch_eliminate(ctx, ELIM_RREF, (u64*)a_dev, batch, m, n, ld, 0, pivots_dev, cap, rank_dev, nullptr, nullptr,
                             nullptr);
 }
@@ -3357,6 +3363,7 @@ int gf2_rref(gf2_ctx* ctx, uint64_t* a, int64_t m, int64_t n, int64_t ld, int64_
 
 int gf2_normalize_dev(gf2_ctx* ctx, uint64_t* h_dev, int64_t r, int64_t n, int64_t ld, int64_t offset,
                       int64_t* swaps_dev, int64_t* nswaps_dev, int* status_dev) {
+    if (reinterpret_cast<uintptr_t>(h_dev) & 15) GF2_FAIL(GF2_E_ARG, "gf2_normalize_dev: the matrix must be 16-byte aligned");
     if (!ctx) GF2_FAIL(GF2_E_ARG, "gf2_normalize_dev: null context");
     if (r < 0 || n < 0 || offset < 0 || ld < gf2_words(n)) GF2_FAIL(GF2_E_ARG, "gf2_normalize_dev: bad shape");
     if (n < offset + r) GF2_FAIL(GF2_E_COLUMNS, "not enough columns");

@@ -380,6 +380,8 @@ extern "C" {
 
 int gf2_sample_errors_dev(gf2_ctx* ctx, int64_t n, uint64_t seed, int64_t first_sample, int64_t count, double p_x,
                           double p_y, double p_z, uint64_t* ex_dev, uint64_t* ez_dev, int64_t lde, int layout) {
+    if (layout == GF2_LAYOUT_TILED && ((reinterpret_cast<uintptr_t>(ex_dev) | reinterpret_cast<uintptr_t>(ez_dev)) & 15))
+        GF2_FAIL(GF2_E_ARG, "gf2_sample_errors_dev: tiled buffers must be 16-byte aligned");
     if (!ctx) GF2_FAIL(GF2_E_ARG, "gf2_sample_errors_dev: null context");
     if (layout != GF2_LAYOUT_SAMPLE_MAJOR && layout != GF2_LAYOUT_TILED)
         GF2_FAIL(GF2_E_ARG, "gf2_sample_errors_dev: layout must be sample-major or tiled");

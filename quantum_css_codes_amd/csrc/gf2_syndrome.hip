@@ -563,6 +563,8 @@ int gf2_check_destroy(gf2_ctx* ctx, gf2_check* check) {
 }
 
 int gf2_retile_dev(gf2_ctx* ctx, const uint64_t* e_dev, int64_t batch, int64_t lde, int64_t n, uint64_t* tiled_dev) {
+    // (the tiled layout is written and read as 16-byte pieces; checked first of all, so that the refusal needs no device)
+    if (reinterpret_cast<uintptr_t>(tiled_dev) & 15) GF2_FAIL(GF2_E_ARG, "gf2_retile_dev: the tiled buffer must be 16-byte aligned");
     if (!ctx) GF2_FAIL(GF2_E_ARG, "gf2_retile_dev: null context");
     if (batch < 0 || n < 0 || lde < gf2_words(n) || lde < 1) GF2_FAIL(GF2_E_ARG, "gf2_retile_dev: bad shape");
     if (batch == 0) return GF2_OK;
@@ -609,6 +611,8 @@ static int launch_tiled(gf2_ctx* ctx, const gf2_check* ck, const uint64_t* e_til
 
 int gf2_syndrome_dev(gf2_ctx* ctx, const gf2_check* ck, const uint64_t* e_dev, int64_t batch, int64_t lde,
                      int layout, uint64_t* s_dev, int64_t lds) {
+    if (layout == GF2_LAYOUT_TILED && (reinterpret_cast<uintptr_t>(e_dev) & 15))
+        GF2_FAIL(GF2_E_ARG, "gf2_syndrome_dev: tiled errors must be 16-byte aligned");
     if (!ctx || !ck) GF2_FAIL(GF2_E_ARG, "gf2_syndrome_dev: null argument");
     if (batch < 0) GF2_FAIL(GF2_E_ARG, "gf2_syndrome_dev: negative batch");
     if (batch == 0 || ck->r == 0) return GF2_OK;
