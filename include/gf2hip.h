@@ -693,6 +693,46 @@ int gf2_mc_ft_decode_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t ns
                             const uint8_t* flips2, int64_t entries2, uint64_t seed, int64_t first_sample, int64_t nstrata,
                             const int32_t* weights, const int64_t* counts, double k_x, double k_y, double k_z, uint64_t* counts_out);
 
+/* ---- sampled strata of the two post-selected gadgets under gate-level faults ---------------------------
+ * [build-defined, DESIGN.md section 5e "Sampled strata under gate-level faults"]  The sites, kind masks and outcome rule of "exact
+ * strata ... under gate-level faults" above and the generator of "weight-stratified Monte-Carlo", combined.  A stratum is a pair
+ * (a, b): exactly a faulty one-operand gates and b faulty CNOTs, 0 <= a <= n_1, 0 <= b <= n_2, a + b <= GF2_GATE_STRATUM_MAX_WEIGHT.
+ * Sample i of stratum (a, b) is a pure function of (seed, i, a, b): ks = sample_key(seed, i), d = segment_draw(ks, 64 + 17 b + a)
+ * (the slot carries the stratum and starts above every location stratum's), and for pick k = 0 .. a + b - 1 with
+ * v = mix64(d + G (k + 1)), hi = v >> 32, lo = v & 0xFFFFFFFF:
+ *   k < a:   j = n_1 - a + k, t = (hi (j + 1)) >> 32; the site is t unless an earlier pick is t, then j (Floyd's rule);
+ *            kappa = 1 + ((lo * 3) >> 32);
+ *   k >= a:  m = k - a, j = n_2 - b + m, t = (hi (j + 1)) >> 32; the CNOT index is t unless an earlier CNOT pick is t, then j; the
+ *            site is n_1 + that index; kappa = 1 + ((lo * 15) >> 32).
+ * The outcome words are the XOR over the picks and the set bits t of each kappa of eff[site_loc[site] + (t >> 1)][t & 1]; c is the
+ * number of CNOT picks with a two-operand kind; the sample is judged by the gadget's tally rule, post-selection included, and
+ * tallied into row c.  counts[c][field] / N estimates the exact strata's counts[a + b][b][c][field] / (C(n_1, a) C(n_2, b) 3^a 15^b).
+ *
+ * The definition on the host, serial, no GPU needed: the outcome words (count x ldw, ldw >= ldr, the words past ldr left as they
+ * were, 1 <= ldr <= GF2_FT_MAX_LDR) and one byte c per sample of samples first_sample .. first_sample + count - 1.
+ * gf2_ec_tally_host / gf2_ft_tally_host applied to the words, grouped by c, complete the statement.  GF2_E_ARG for a stratum outside
+ * the limits above, a site table that is no partition of [0, L), a negative count or first_sample. */
+#define GF2_GATE_STRATUM_MAX_WEIGHT 16
+int gf2_gate_stratum_outcomes_host(const uint64_t* eff, int64_t locations, int64_t ldr, const int32_t* site_loc, int64_t n1, int64_t n2,
+                                   int64_t a, int64_t b, uint64_t seed, int64_t first_sample, int64_t count, uint64_t* words_out,
+                                   int64_t ldw, uint8_t* two_operand_out);
+
+/* The tallies on the device: stratum s is (a[s], b[s]) with samples first_sample .. first_sample + counts[s] - 1; counts_out is
+ * nstrata x (GF2_GATE_STRATUM_MAX_WEIGHT + 1) x F words [stratum][c][field], F = GF2_EC_FIELDS or GF2_FT_FIELDS, the rows c > b zero.
+ * Circuit, layout and tables as gf2_mc_ec_decode_strata / gf2_mc_ft_decode_strata check them, the site table as
+ * gf2_ec_gate_enumerate checks it, nstrata <= GF2_STRATA_MAX, every (a, b) within the limits above, non-negative counts and
+ * first_sample.  The hash tables and the device copy of site_loc are made once per call, a stratum is cut into launches of at most
+ * 2^36 samples, the counts come back once. */
+int gf2_mc_ec_decode_gate_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                                 const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                                 int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, uint64_t seed, int64_t first_sample,
+                                 int64_t nstrata, const int32_t* a, const int32_t* b, const int64_t* counts, uint64_t* counts_out);
+int gf2_mc_ft_decode_gate_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                                 const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                                 const uint8_t* flips2, int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, uint64_t seed,
+                                 int64_t first_sample, int64_t nstrata, const int32_t* a, const int32_t* b, const int64_t* counts,
+                                 uint64_t* counts_out);
+
 /* ---- streamed gadgets: error-correction cycles and programs of any length, block by block ---------------
  * [build-defined, DESIGN.md "Streamed gadgets"]  Both ancilla blocks are RESET at the start of every preparation, so only the data
  * block survives from one block of a gadget -- the first preparation, an EC round, a MEASURE trial -- to the next.  A fault inside a

@@ -29,6 +29,7 @@ CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 ENUMERATE_MAX_WEIGHT = 8
 GATE_ENUMERATE_MAX_WEIGHT = 4                       # GF2_GATE_ENUMERATE_MAX_WEIGHT
+GATE_STRATUM_MAX_WEIGHT = 16                        # GF2_GATE_STRATUM_MAX_WEIGHT
 FAULT_RECORD_WORDS, FAULT_LIST_MAX_CAPACITY = 2, 1 << 28       # GF2_FAULT_RECORD_WORDS, GF2_FAULT_LIST_MAX_CAPACITY
 K_SYNDROME, K_HIST, K_SAMPLER, K_ELIM = 0, 1, 2, 3
 # routing flags of a context and its tunables: the few a caller needs are in include/gf2hip.h (F_MC_DENSE, F_RREF_SEQUENTIAL,
@@ -167,6 +168,11 @@ SIGNATURES = {
                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
     "gf2_mc_ft_decode_strata": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, _p, _p,
                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, _p],
+    "gf2_gate_stratum_outcomes_host": [_p, _c_i64, _c_i64, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _c_i64, _p, _c_i64, _p],
+    "gf2_mc_ec_decode_gate_strata": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_u64, _c_i64,
+                                     _c_i64, _p, _p, _p, _p],
+    "gf2_mc_ft_decode_gate_strata": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_u64,
+                                     _c_i64, _c_i64, _p, _p, _p, _p],
     "gf2_stream_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _c_i64, _p, _c_i64],
     "gf2_stream_tally_host": [_p, _c_i64, _c_i64, _p, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _p],
     "gf2_stream_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _pp],
@@ -583,6 +589,32 @@ def ft_gate_enumerate_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, key
     """gf2_ft_gate_enumerate_host (host code, no GPU): the (b + 1, 7) counts of the logical measurement's tally rule, likewise."""
     return _gate_enumerate_host(lib().gf2_ft_gate_enumerate_host, FT_FIELDS_COUNT, eff, (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF),
                                 (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), w, b, first_rank, count)
+
+
+def gate_stratum_outcomes_host(eff, site_loc, n1, n2, a, b, count, seed=0, first=0, ldw=None):
+    """gf2_gate_stratum_outcomes_host (host code, no GPU): (words, c) of samples [first, first + count) of the stratum of a faulty
+    one-operand gates and b faulty CNOTs among the sites of an effect table eff, (L, 2, ldr): the (count, ldw) outcome words (ldw
+    defaults to ldr; the words past ldr zero here) and the (count,) uint8 number of two-operand kinds per sample."""
+    eff = np.ascontiguousarray(eff, dtype="<u8")
+    if eff.ndim != 3 or eff.shape[1] != 2:
+        raise ValueError("eff must be (locations, 2, ldr)")
+    site_loc = _gate_sites(site_loc, n1, n2)
+    count = int(count)
+    ldw = eff.shape[2] if ldw is None else int(ldw)
+    out = np.zeros((max(1, count), max(1, ldw)), dtype="<u8")
+    two = np.zeros(max(1, count), dtype=np.uint8)
+    check(lib().gf2_gate_stratum_outcomes_host(_ptr(eff), eff.shape[0], eff.shape[2], _ptr(site_loc), int(n1), int(n2), int(a), int(b),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, _ptr(out), ldw, _ptr(two)))
+    return out[:max(0, count)], two[:max(0, count)]
+
+
+def _gate_strata_arrays(strata, counts, fields):
+    strata = np.ascontiguousarray(strata, dtype=np.int32).reshape(-1, 2)
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(strata) != len(counts):
+        raise ValueError("one sample count per stratum")
+    return (np.ascontiguousarray(strata[:, 0]), np.ascontiguousarray(strata[:, 1]), counts,
+            np.zeros((len(counts), GATE_STRATUM_MAX_WEIGHT + 1, fields), dtype=np.uint64))
 
 
 def _fault_list_call(fn, head, select, capacity, limit=None):
@@ -1157,6 +1189,28 @@ class Context(object):
         out = np.zeros((max(0, min(int(b), GATE_ENUMERATE_MAX_WEIGHT)) + 1, FT_FIELDS_COUNT), dtype=np.uint64)
         check(lib().gf2_ft_gate_enumerate(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2),
                                           *t2, _ptr(site_loc), int(n1), int(n2), int(w), int(b), int(first_rank), int(count), _ptr(out)))
+        return out
+
+    def mc_ec_decode_gate_strata(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, seed, first, strata, counts):
+        """gf2_mc_ec_decode_gate_strata: mc_ec_decode's tables, gate_sites' site table; strata (nstrata, 2) rows (a, b) and counts per
+        stratum.  Returns the (nstrata, 17, 8) counts [stratum][c][field]."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        site_loc = _gate_sites(site_loc, n1, n2)
+        wa, wb, counts, out = _gate_strata_arrays(strata, counts, EC_FIELDS_COUNT)
+        check(lib().gf2_mc_ec_decode_gate_strata(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, _ptr(site_loc), int(n1),
+                                                 int(n2), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), len(counts), _ptr(wa), _ptr(wb),
+                                                 _ptr(counts), _ptr(out)))
+        return out
+
+    def mc_ft_decode_gate_strata(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, seed, first,
+                                 strata, counts):
+        """gf2_mc_ft_decode_gate_strata: mc_ft_decode's tables, likewise.  Returns the (nstrata, 17, 7) counts."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        site_loc = _gate_sites(site_loc, n1, n2)
+        wa, wb, counts, out = _gate_strata_arrays(strata, counts, FT_FIELDS_COUNT)
+        check(lib().gf2_mc_ft_decode_gate_strata(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1,
+                                                 int(r2), *t2, _ptr(site_loc), int(n1), int(n2), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first),
+                                                 len(counts), _ptr(wa), _ptr(wb), _ptr(counts), _ptr(out)))
         return out
 
     def ec_enumerate_list(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):

@@ -880,14 +880,11 @@ int gf2_ft_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t l
 }  // extern "C"
 
 // ---- exact strata under gate-level faults (include/gf2hip.h "gate-level faults") ------------------------
-// The argument rules of a rank range of sites, shared by the host statements below and the device entry points
-// (gf2_gate_enumerate.hip).
-int gf2_gate_check_range(const char* who, int64_t locations, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b,
-                         int64_t first_rank, int64_t count) {
+// The argument rules of the site table alone (the sampled strata of gf2_gate_strata.hip and their host statement check it through
+// this too) ...
+int gf2_gate_check_sites(const char* who, int64_t locations, const int32_t* site_loc, int64_t n1, int64_t n2) {
     if (locations < 1 || locations > GF2_CIRCUIT_MAX_LOCATIONS)
         GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= L <= %d (2^20) locations, got %lld", who, GF2_CIRCUIT_MAX_LOCATIONS, (long long)locations);
-    if (w < 0 || w > GF2_GATE_ENUMERATE_MAX_WEIGHT) GF2_FAIL(GF2_E_ARG, "%s: weight %lld outside [0, %d]", who, (long long)w, GF2_GATE_ENUMERATE_MAX_WEIGHT);
-    if (b < 0 || b > w) GF2_FAIL(GF2_E_ARG, "%s: %lld CNOT picks outside [0, w = %lld]", who, (long long)b, (long long)w);
     if (!site_loc || n1 < 0 || n2 < 0 || n1 + 2 * n2 != locations)
         GF2_FAIL(GF2_E_ARG, "%s: the site table is no partition of [0, L): n_1 + 2 n_2 = %lld + 2 * %lld, L = %lld", who, (long long)n1, (long long)n2,
                  (long long)locations);
@@ -902,6 +899,17 @@ int gf2_gate_check_range(const char* who, int64_t locations, const int32_t* site
     } catch (const std::bad_alloc&) {
         GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
     }
+    return GF2_OK;
+}
+
+// ... and of a rank range of sites, shared by the host statements below and the device entry points (gf2_gate_enumerate.hip).
+int gf2_gate_check_range(const char* who, int64_t locations, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b,
+                         int64_t first_rank, int64_t count) {
+    if (locations < 1 || locations > GF2_CIRCUIT_MAX_LOCATIONS)                // (gf2_gate_check_sites' test, here to keep the order of the messages)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= L <= %d (2^20) locations, got %lld", who, GF2_CIRCUIT_MAX_LOCATIONS, (long long)locations);
+    if (w < 0 || w > GF2_GATE_ENUMERATE_MAX_WEIGHT) GF2_FAIL(GF2_E_ARG, "%s: weight %lld outside [0, %d]", who, (long long)w, GF2_GATE_ENUMERATE_MAX_WEIGHT);
+    if (b < 0 || b > w) GF2_FAIL(GF2_E_ARG, "%s: %lld CNOT picks outside [0, w = %lld]", who, (long long)b, (long long)w);
+    if (int rc = gf2_gate_check_sites(who, locations, site_loc, n1, n2)) return rc;
     const int64_t a = w - b;
     const unsigned __int128 total = (unsigned __int128)binom_sat(n1, (int)a) * binom_sat(n2, (int)b);
     if (total >> 63) GF2_FAIL(GF2_E_ARG, "%s: C(%lld, %lld) C(%lld, %lld) subsets do not fit 63 bits", who, (long long)n1, (long long)a, (long long)n2, (long long)b);
@@ -1014,6 +1022,68 @@ int gf2_ft_gate_enumerate_host(const uint64_t* eff, int64_t locations, int64_t l
     gate_walk(eff, ldr, site_loc, n1, n2, w, b, first_rank, count, [&](const int32_t*, const int*, int64_t c, const uint64_t* out) {
         (void)ft_tally_sample(out, ldr, nsteps, measure_mask, trials, mask, tab, counts_out + c * GF2_FT_FIELDS);
     });
+    return GF2_OK;
+}
+
+}  // extern "C"
+
+// ---- sampled strata under gate-level faults (include/gf2hip.h "sampled strata ... under gate-level faults") --
+// The limits of one stratum (a, b), shared by the host statement below and the device entry points (gf2_gate_strata.hip); `at`
+// names the stratum in the message ("" when the call has one).
+int gf2_gate_check_stratum(const char* who, const char* at, int64_t n1, int64_t n2, int64_t a, int64_t b) {
+    if (a < 0 || b < 0 || a + b > GF2_GATE_STRATUM_MAX_WEIGHT)
+        GF2_FAIL(GF2_E_ARG, "%s: %sneeds a, b >= 0 and a + b <= %d faulty gates, got a = %lld and b = %lld", who, at,
+                 GF2_GATE_STRATUM_MAX_WEIGHT, (long long)a, (long long)b);
+    if (a > n1 || b > n2)
+        GF2_FAIL(GF2_E_ARG, "%s: %sneeds a <= n_1 = %lld and b <= n_2 = %lld, got a = %lld and b = %lld", who, at, (long long)n1,
+                 (long long)n2, (long long)a, (long long)b);
+    return GF2_OK;
+}
+
+extern "C" {
+
+// The outcome words and two-operand counts of a gadget's stratified samples under gate-level faults, the host statement of what
+// gate_strata_kernel draws: the generator of gf2_stratum_outcomes_host over sites, one array of picks in the unified site numbering
+// for Floyd's comparison (the two ranges are disjoint).  gf2_ec_tally_host / gf2_ft_tally_host judge the words; no tally rule is
+// repeated here.
+int gf2_gate_stratum_outcomes_host(const uint64_t* eff, int64_t locations, int64_t ldr, const int32_t* site_loc, int64_t n1, int64_t n2,
+                                   int64_t a, int64_t b, uint64_t seed, int64_t first_sample, int64_t count, uint64_t* words_out,
+                                   int64_t ldw, uint8_t* two_operand_out) {
+    const char* who = "gf2_gate_stratum_outcomes_host";
+    if (!eff) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (ldr < 1 || ldr > GF2_FT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= ldr <= %d words per effect, got %lld", who, GF2_FT_MAX_LDR, (long long)ldr);
+    if (int rc = gf2_gate_check_sites(who, locations, site_loc, n1, n2)) return rc;
+    if (int rc = gf2_gate_check_stratum(who, "", n1, n2, a, b)) return rc;
+    if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "%s: negative range (needs count >= 0 and first_sample >= 0)", who);
+    if (ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the table's %lld words", who, (long long)ldr);
+    if (count > 0 && (!words_out || !two_operand_out)) GF2_FAIL(GF2_E_ARG, "%s: null buffer", who);
+    const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
+    for (int64_t i = 0; i < count; ++i) {
+        uint64_t* const out = words_out + i * ldw;
+        for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
+        const uint64_t ks = host_mix64(seed + golden * ((uint64_t)(first_sample + i) + 1));
+        const uint64_t d = host_mix64(ks + stream * ((uint64_t)(64 + 17 * b + a) + 1));   // the segment slot carries the stratum
+        uint64_t picks[GF2_GATE_STRATUM_MAX_WEIGHT];
+        unsigned c = 0;
+        for (int64_t k = 0; k < a + b; ++k) {
+            const uint64_t v = host_mix64(d + golden * (uint64_t)(k + 1));
+            const uint64_t hi = v >> 32, lo = v & 0xFFFFFFFFull;
+            const bool one = k < a;
+            const uint64_t base = one ? 0 : (uint64_t)n1;
+            const uint64_t j = one ? (uint64_t)(n1 - a + k) : (uint64_t)(n2 - b + (k - a));
+            const uint64_t t = base + ((hi * (j + 1)) >> 32);                    // Floyd: a candidate in [0, j] of its class
+            bool taken = false;
+            for (int64_t q = 0; q < k; ++q) taken |= picks[q] == t;
+            picks[k] = taken ? base + j : t;
+            const uint64_t kappa = 1 + ((lo * (one ? 3u : 15u)) >> 32);
+            const uint64_t* e = eff + (size_t)(2 * site_loc[picks[k]]) * ldr;     // effect t of the site: (2 l + t) ldr
+            for (int bit = 0; bit < 4; ++bit)
+                if ((kappa >> bit) & 1)
+                    for (int64_t q = 0; q < ldr; ++q) out[q] ^= e[bit * ldr + q];
+            c += (kappa & 3) != 0 && (kappa >> 2) != 0;
+        }
+        two_operand_out[i] = (uint8_t)c;
+    }
     return GF2_OK;
 }
 

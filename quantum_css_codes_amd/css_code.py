@@ -418,6 +418,14 @@ class CSSCode(QECC):
         from . import ec_noise
         return ec_noise.circuit_for(self, rounds, idle_data).enumerate_gate_strata(weights, **options)
 
+    def error_correct_gate_strata(self, strata, samples, rounds=1, idle_data=False, **options):
+        """Sampled strata of the cycle under gate-level faults: strata[s] = (a, b), samples[s] stratified samples of exactly a faulty
+        one-operand gates and b faulty CNOTs each (ec_noise.ECCircuit.gate_strata; DESIGN.md section 5e "Sampled strata under
+        gate-level faults"): a montecarlo.SampledGateStrata.  error_correct_gate_strata_exact(...).merged(it) combines them with the
+        exact strata into a rate with a standard error and rigorous bounds."""
+        from . import ec_noise
+        return ec_noise.circuit_for(self, rounds, idle_data).gate_strata(strata, samples, **options)
+
     def error_correct_gate_single_faults(self, rounds=1):
         """[build-defined]  The census of every single gate fault of the cycle, no GPU needed: ECCircuit.gate_single_faults."""
         from . import ec_noise
@@ -464,6 +472,13 @@ class CSSCode(QECC):
         series(('depolarising', 1), 'wrong') gives the Taylor coefficients of the probability that the measured bit is wrong."""
         from . import ft_noise
         return ft_noise.program_for(self, ops).enumerate_gate_strata(weights, **options)
+
+    def logical_program_gate_strata(self, ops, strata, samples, **options):
+        """Sampled strata (a, b) of the rewritten program `ops; MEASURE` under gate-level faults, samples[s] stratified samples each
+        (ft_noise.FTProgram.gate_strata; DESIGN.md section 5e "Sampled strata under gate-level faults"): a
+        montecarlo.SampledGateStrata, to be merged with logical_program_gate_strata_exact's."""
+        from . import ft_noise
+        return ft_noise.program_for(self, ops).gate_strata(strata, samples, **options)
 
     def logical_program_gate_single_faults(self, ops):
         """[build-defined]  The census of every single gate fault of the rewritten program, no GPU needed:

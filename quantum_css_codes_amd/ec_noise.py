@@ -347,6 +347,23 @@ class ECCircuit(object):
         (default circuit_noise.ENUMERATE_BUDGET) configurations in all is a ValueError.  Returns a montecarlo.GateStrata."""
         return gate_strata(self, EC_FIELDS, weights, max_configurations, host, "cycle")
 
+    def gate_strata(self, strata, samples, seed=0, first_sample=0, host=False):
+        """Sampled strata of the cycle under gate-level faults (DESIGN.md section 5e "Sampled strata under gate-level faults"):
+        stratum s = (a, b) draws samples [first_sample, first_sample + samples[s]) of exactly a faulty one-operand gates and b faulty
+        CNOTs, a + b <= 16, kinds uniform over the 3 and the 15, and judges them by logical_error_rates' tally rule, post-selection
+        included, tallied by the number c of two-operand kinds (gf2_mc_ec_decode_gate_strata).  `samples` and `first_sample` are one
+        number for all strata or one per stratum.  host=True draws with gf2_gate_stratum_outcomes_host and tallies with
+        gf2_ec_tally_host: no GPU.  Returns a montecarlo.SampledGateStrata."""
+        from . import montecarlo
+        tables, sites = self._tables(), self.gate_sites()[:3]
+        if host:
+            run = montecarlo.host_gate_strata_run(self.effects, sites, lambda words: _native.ec_tally_host(words, self.rounds, *tables),
+                                                  len(EC_FIELDS), seed)
+        else:
+            ctx, circ = _native.default_context(), self.device()
+            run = lambda first, strata, ns: ctx.mc_ec_decode_gate_strata(circ, self.rounds, *tables, *sites, int(seed), int(first), strata, ns)
+        return montecarlo.gate_strata_local(sites[1], sites[2], EC_FIELDS, strata, samples, first_sample, run)
+
     def gate_single_faults(self):
         """The census of every single gate fault, no GPU: (classes, flipping) -- classes (G, 15) uint8, the class byte (CLASS_* bits)
         of kind mask kappa (column kappa - 1; a one-operand gate uses columns 0 .. 2, the others stay 0) at every gate of the list;

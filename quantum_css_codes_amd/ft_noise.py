@@ -272,6 +272,24 @@ class FTProgram(object):
         included, whole strata, every CNOT count b.  Arguments as ECCircuit.enumerate_gate_strata's.  Returns a montecarlo.GateStrata."""
         return ec_noise.gate_strata(self, FT_FIELDS, weights, max_configurations, host, "program")
 
+    def gate_strata(self, strata, samples, seed=0, first_sample=0, host=False):
+        """Sampled strata of the measurement under gate-level faults (DESIGN.md section 5e "Sampled strata under gate-level faults"):
+        stratum s = (a, b) draws samples of exactly a faulty one-operand gates and b faulty CNOTs of the rewritten program, a + b <= 16,
+        judged by measurement_error_rates' tally rule, post-selection included, tallied by the number c of two-operand kinds
+        (gf2_mc_ft_decode_gate_strata).  Arguments as ECCircuit.gate_strata's; host=True goes through gf2_gate_stratum_outcomes_host
+        and gf2_ft_tally_host and needs no GPU.  Returns a montecarlo.SampledGateStrata."""
+        from . import montecarlo
+        tables, sites = self._tables(), self.gate_sites()[:3]
+        if host:
+            run = montecarlo.host_gate_strata_run(self.effects, sites,
+                                                  lambda words: _native.ft_tally_host(words, self.nsteps, self.measure_mask, *tables),
+                                                  len(FT_FIELDS), seed)
+        else:
+            ctx, circ = _native.default_context(), self.device()
+            run = lambda first, strata, ns: ctx.mc_ft_decode_gate_strata(circ, self.nsteps, self.measure_mask, *tables, *sites, int(seed),
+                                                                         int(first), strata, ns)
+        return montecarlo.gate_strata_local(sites[1], sites[2], FT_FIELDS, strata, samples, first_sample, run)
+
     def gate_single_faults(self):
         """The census of every single gate fault, no GPU: (classes, wrong) -- classes (G, 15) uint8, the class byte (CLASS_* bits) of
         kind mask kappa (column kappa - 1; a one-operand gate uses columns 0 .. 2) at every gate of the list; wrong, the accepted

@@ -762,6 +762,10 @@ class GateStrata(object):
                 return k, c
         return None
 
+    def merged(self, sampled):
+        """These exact strata with sampled ones (a SampledGateStrata or a list of them) as a MergedGateStrata."""
+        return MergedGateStrata(self, [sampled] if isinstance(sampled, SampledGateStrata) else list(sampled))
+
 
 # ---- malignant fault sets of a post-selected gadget (DESIGN.md "Malignant fault sets of the cycle", "... of the measurement") --------
 
@@ -1083,6 +1087,260 @@ def gadget_strata_sharded(gadget, weights, samples, kinds=(1, 1, 1), seed=0, fir
     part = fn(gadget, weights, [mine for _, mine in shards], kinds=kinds, seed=seed, first_sample=[start for start, _ in shards])
     total, = all_reduce_histograms([part.counts.reshape(-1)], group=group)
     return SampledPostSelectedStrata(part.nb, weights, samples, total, part.fields, kinds)
+
+
+# ---- sampled strata under gate-level faults (DESIGN.md section 5e "Sampled strata under gate-level faults") ------------------------
+
+GATE_STRATA_ROWS = _native.GATE_STRATUM_MAX_WEIGHT + 1
+
+
+class SampledGateStrata(object):
+    """Tallies of a stratified run of a post-selected gadget under gate-level faults (ec_noise.ECCircuit.gate_strata /
+    ft_noise.FTProgram.gate_strata) with `n1` one-operand gates and `n2` CNOTs: `strata` (nstrata rows (a, b), distinct), `samples`
+    (N per stratum), `counts` (nstrata x 17 x F, [stratum][c][field] with c the number of two-operand kinds, field 0 'accepted',
+    every other field among accepted samples, the rows c > b zero).  counts[s][c] / N estimates the exact strata's
+    counts[a + b][b][c] / (C(n1, a) C(n2, b) 3^a 15^b).  joint, acceptance and rate are MergedGateStrata's over these strata alone;
+    GateStrata.merged adds exact strata."""
+
+    SUM_FIELDS = PostSelectedStrata.SUM_FIELDS
+
+    def __init__(self, n1, n2, strata, samples, counts, fields):
+        self.n1, self.n2 = int(n1), int(n2)
+        self.fields = tuple(fields)
+        if not self.fields or self.fields[0] != 'accepted':
+            raise ValueError("the first field of a post-selected tally is 'accepted'")
+        self.strata = np.asarray(strata, dtype=np.int64).reshape(-1, 2).copy()
+        self.samples = np.asarray(samples, dtype=np.int64).reshape(-1).copy()
+        self.counts = np.asarray(counts, dtype=np.uint64).reshape(len(self.strata), GATE_STRATA_ROWS, len(self.fields)).copy()
+        if self.samples.shape != (len(self.strata),):
+            raise ValueError("one sample count per stratum")
+        if len(set(map(tuple, self.strata.tolist()))) != len(self.strata):
+            raise ValueError("the strata (a, b) must be distinct")
+        for a, b in self.strata.tolist():
+            if not (0 <= a <= self.n1 and 0 <= b <= self.n2 and a + b <= _native.GATE_STRATUM_MAX_WEIGHT):
+                raise ValueError("a stratum (a, b) needs 0 <= a <= n1 = %d, 0 <= b <= n2 = %d and a + b <= %d, got (%d, %d)"
+                                 % (self.n1, self.n2, _native.GATE_STRATUM_MAX_WEIGHT, a, b))
+        if self.samples.size and self.samples.min() < 0:
+            raise ValueError("negative sample count")
+
+    def _column(self, field):
+        if field not in self.fields:
+            raise ValueError("no field %r (the fields are %s)" % (field, ', '.join(self.fields)))
+        return self.fields.index(field)
+
+    def fractions(self, field='accepted'):
+        """counts / samples per stratum and class, (nstrata, 17): the fraction of ALL samples of the stratum that have c two-operand
+        kinds, are accepted and carry `field` (0 where a stratum has no samples)."""
+        col = self.counts[:, :, self._column(field)].astype(np.float64)
+        n = self.samples[:, None]
+        return np.divide(col, n, out=np.zeros_like(col), where=n > 0)
+
+    def _alone(self):
+        return MergedGateStrata(None, [self])
+
+    def joint(self, odds, field='accepted'):
+        return self._alone().joint(odds, field)
+
+    def acceptance(self, odds):
+        return self._alone().acceptance(odds)
+
+    def rate(self, odds, field='wrong'):
+        return self._alone().rate(odds, field)
+
+    def as_dicts(self):
+        return [dict(zip(self.fields, (int(v) for v in rows.sum(axis=0))), a=int(a), b=int(b), samples=int(n))
+                for (a, b), n, rows in zip(self.strata.tolist(), self.samples, self.counts)]
+
+
+class MergedGateStrata(object):
+    """Exact and sampled strata of one post-selected gadget under gate-level faults together.  `exact` is a GateStrata or None,
+    `sampled` a list of SampledGateStrata over the same (n1, n2) and fields; no stratum may be sampled twice.  An exact weight w
+    replaces every sampled (a, b) with a + b = w (no variance) and covers its whole anti-diagonal.
+
+    At the odds (x, y1, y2) a sampled stratum (a, b) carries, per class c, the weight
+    omega = Z x^a y1^(b - c) y2^c C(n1, a) C(n2, b) 3^a 15^b with Z = (1 + 3 x)^-n1 (1 + 6 y1 + 9 y2)^-n2, and with phi the sampled
+    fraction count / N:  N = sum omega phi[field],  D = sum omega phi[accepted],  T = 1 - sum over the covered (a, b) of
+    P(A = a) P(B = b), A ~ Bin(n1, 3 x / (1 + 3 x)), B ~ Bin(n2, (6 y1 + 9 y2) / (1 + 6 y1 + 9 y2)).  A sampled stratum with nothing
+    accepted contributes nothing and counts as covered."""
+
+    def __init__(self, exact, sampled):
+        self.exact, self.sampled = exact, list(sampled)
+        if exact is None and not self.sampled:
+            raise ValueError("no strata at all")
+        first = exact if exact is not None else self.sampled[0]
+        self.n1, self.n2, self.fields = first.n1, first.n2, first.fields
+        self.exact_weights = sorted(exact.weights) if exact is not None else []
+        seen = set()
+        for part in self.sampled:
+            if (part.n1, part.n2) != (self.n1, self.n2):
+                raise ValueError("sampled strata over (n1, n2) = (%d, %d), the others over (%d, %d)" % (part.n1, part.n2, self.n1, self.n2))
+            if part.fields != self.fields:
+                raise ValueError("sampled strata with fields %r, the others with %r" % (part.fields, self.fields))
+            live = set(tuple(s) for s, n in zip(part.strata.tolist(), part.samples.tolist()) if n > 0)
+            if live & seen:
+                raise ValueError("a stratum (a, b) is sampled twice: %r" % (sorted(live & seen),))
+            seen |= live
+        self.strata = sorted(s for s in seen if s[0] + s[1] not in self.exact_weights)   # the sampled strata that are used
+
+    def _column(self, field):
+        if field not in self.fields:
+            raise ValueError("no field %r (the fields are %s)" % (field, ', '.join(self.fields)))
+        return self.fields.index(field)
+
+    @staticmethod
+    def _odds(odds):
+        x, y1, y2 = (float(v) for v in odds)
+        if min(x, y1, y2) < 0.0:
+            raise ValueError("odds are not negative")
+        return x, y1, y2
+
+    def _omega(self, odds, a, b):
+        """omega_{a, b, c} for c = 0 .. b (log space; 0 where an odd with a positive exponent is 0)."""
+        x, y1, y2 = odds
+        log_z = -self.n1 * math.log1p(3.0 * x) - self.n2 * math.log1p(6.0 * y1 + 9.0 * y2)
+        log_n = (math.lgamma(self.n1 + 1) - math.lgamma(a + 1) - math.lgamma(self.n1 - a + 1) + math.lgamma(self.n2 + 1)
+                 - math.lgamma(b + 1) - math.lgamma(self.n2 - b + 1) + a * math.log(3.0) + b * math.log(15.0))
+        out = np.zeros(b + 1)
+        for c in range(b + 1):
+            powers = ((a, x), (b - c, y1), (c, y2))
+            if any(e and not v for e, v in powers):
+                continue
+            out[c] = math.exp(log_z + log_n + sum(e * math.log(v) for e, v in powers if e))
+        return out
+
+    def _sampled_parts(self, field):
+        """(a, b) -> (field counts[c], accepted counts[c], N) of every sampled stratum that is used, c = 0 .. b."""
+        col = self._column(field)
+        out = {}
+        for part in self.sampled:
+            for (a, b), n, rows in zip(part.strata.tolist(), part.samples.tolist(), part.counts):
+                if n > 0 and (a, b) in self.strata:
+                    out[(a, b)] = (rows[:b + 1, col].astype(np.float64), rows[:b + 1, 0].astype(np.float64), n)
+        return out
+
+    def _sums(self, odds, field):
+        """(N, D): the exact weights' joint probabilities plus sum omega phi over the sampled strata that are used."""
+        n_tot = [self.exact.joint(odds, field)] if self.exact is not None else []
+        d_tot = [self.exact.joint(odds, 'accepted')] if self.exact is not None else []
+        for (a, b), (f, acc, n) in self._sampled_parts(field).items():
+            omega = self._omega(odds, a, b)
+            n_tot.append(float(np.dot(omega, f)) / n)
+            d_tot.append(float(np.dot(omega, acc)) / n)
+        return math.fsum(n_tot), math.fsum(d_tot)
+
+    def joint(self, odds, field='accepted'):
+        """P(accepted and field) at the odds (x, y1, y2) over the covered strata."""
+        odds = self._odds(odds)
+        self._column(field)
+        return self._sums(odds, field)[0]
+
+    def _missing_mass(self, odds):
+        """T: the probability that (A, B) is not a covered stratum.  Whole weights through GateStrata._missing_mass' sum of two
+        binomials; a weight with sampled cells directly, cell by cell, so that nothing is subtracted."""
+        x, y1, y2 = odds
+        q_1, q_2 = 3.0 * x / (1.0 + 3.0 * x), (6.0 * y1 + 9.0 * y2) / (1.0 + 6.0 * y1 + 9.0 * y2)
+        p_a, p_b = binomial_weights(self.n1, q_1), binomial_weights(self.n2, q_2)
+        total = np.convolve(p_a, p_b)
+        have = np.zeros(len(total), dtype=bool)
+        have[self.exact_weights] = True
+        cells = {}
+        for a, b in self.strata:
+            cells.setdefault(a + b, set()).add(a)
+        terms = []
+        for w, sampled_a in cells.items():
+            have[w] = True
+            terms.extend(float(p_a[a] * p_b[w - a]) for a in range(max(0, w - self.n2), min(self.n1, w) + 1) if a not in sampled_a)
+        terms.extend(total[~have].tolist())
+        return math.fsum(terms)
+
+    def acceptance(self, odds):
+        """(D, D + T): the probability that an attempt is accepted lies between them (up to the sampling error of D)."""
+        odds = self._odds(odds)
+        d = self._sums(odds, 'accepted')[1]
+        return d, d + self._missing_mass(odds)
+
+    def rate(self, odds, field='wrong'):
+        """The conditional rate P(field | accepted) of an indicator field as PostSelectedRate(estimate, stderr, lower, upper):
+        estimate R = N / D, lower = N / (D + T), upper = (N + T) / (D + T), and stderr by the delta method: a sample of stratum
+        (a, b) with class c contributes u = omega_{a,b,c} (1[field] - R 1[accepted]), and
+        stderr = (1 / D) sqrt(sum over the sampled strata of (E[u^2] - E[u]^2) / N_{a,b}), the expectations over the stratum's own
+        samples.  With y1 = y2 and one sampled stratum this is sqrt(R (1 - R) / (N a)), a the accepted fraction."""
+        if field in PostSelectedStrata.SUM_FIELDS:
+            raise ValueError("rate() is defined for indicator fields; %r is a sum" % (field,))
+        odds = self._odds(odds)
+        self._column(field)
+        n_tot, d = self._sums(odds, field)
+        t = self._missing_mass(odds)
+        if not d > 0:
+            raise ValueError("no accepted sample or configuration among the covered strata at the odds %r" % (odds,))
+        r = n_tot / d
+        var = []
+        for (a, b), (f, acc, n) in self._sampled_parts(field).items():
+            omega = self._omega(odds, a, b)
+            mean = float(np.dot(omega, f - r * acc)) / n
+            square = float(np.dot(omega**2, f * (1.0 - r)**2 + (acc - f) * r**2)) / n
+            var.append((square - mean**2) / n)
+        return PostSelectedRate(r, math.sqrt(max(math.fsum(var), 0.0)) / d, n_tot / (d + t), (n_tot + t) / (d + t))
+
+
+def _gate_strata_request(n1, n2, strata, samples, first_sample):
+    strata = [(int(a), int(b)) for a, b in np.asarray(strata, dtype=np.int64).reshape(-1, 2).tolist()]
+    samples = np.broadcast_to(np.asarray(samples, dtype=np.int64), (len(strata),)).copy()
+    firsts = np.broadcast_to(np.asarray(first_sample, dtype=np.int64), (len(strata),)).copy()
+    top = _native.GATE_STRATUM_MAX_WEIGHT
+    for a, b in strata:
+        if a < 0 or b < 0 or a + b > top:
+            raise ValueError("a stratum (a, b) needs a, b >= 0 and a + b <= %d faulty gates, got (%d, %d)" % (top, a, b))
+        if a > n1 or b > n2:
+            raise ValueError("a stratum (a, b) needs a <= n1 = %d and b <= n2 = %d, got (%d, %d)" % (n1, n2, a, b))
+    if samples.size and samples.min() < 0:
+        raise ValueError("negative sample count")
+    if firsts.size and firsts.min() < 0:
+        raise ValueError("negative first sample")
+    return strata, samples, firsts
+
+
+def host_gate_strata_run(effects, sites, tally, nfields, seed, chunk=1 << 18):
+    """The `run` of gate_strata_local on the host: gf2_gate_stratum_outcomes_host's words and classes, `chunk` samples at a time, the
+    words grouped by their class c and handed to `tally` (words -> the gadget's counts; _native.ec_tally_host / ft_tally_host)."""
+    def run(first, strata, samples):
+        out = np.zeros((len(strata), GATE_STRATA_ROWS, nfields), dtype=np.uint64)
+        for s, ((a, b), count) in enumerate(zip(strata, np.asarray(samples).tolist())):
+            for done in range(0, int(count), chunk):
+                words, two = _native.gate_stratum_outcomes_host(effects, *sites, a, b, min(chunk, int(count) - done), seed, int(first) + done)
+                for c in np.unique(two).tolist():
+                    out[s, c] += tally(words[two == c])
+        return out
+    return run
+
+
+def gate_strata_local(n1, n2, fields, strata, samples, first_sample, run):
+    """What ECCircuit.gate_strata and FTProgram.gate_strata share: the request checked and grouped as strata_local groups it (one
+    native call per distinct first sample), `run(first, strata, samples)` returning the (nstrata, 17, F) counts of a call."""
+    strata, samples, firsts = _gate_strata_request(n1, n2, strata, samples, first_sample)
+    counts = np.zeros((len(strata), GATE_STRATA_ROWS, len(fields)), dtype=np.uint64)
+    for first, rows in _strata_calls(firsts):
+        counts[rows] = run(int(first), [strata[s] for s in rows], samples[rows])
+    return SampledGateStrata(n1, n2, strata, samples, counts, fields)
+
+
+def gate_strata_sharded(gadget, strata, samples, seed=0, first_sample=0, group=None, local_fn=None):
+    """Sampled strata under gate-level faults of an ec_noise.ECCircuit or an ft_noise.FTProgram over the ranks of a process group:
+    every stratum's sample range is cut by shard_range, this rank runs its part, and one all-reduce sums the nstrata x 17 x F counts.
+    `local_fn(gadget, strata, samples, seed=, first_sample=)` replaces gadget.gate_strata (the CPU tests pass the host statement).
+    Returns a SampledGateStrata with the whole sample counts."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+    else:
+        rank, world = 0, 1
+    _, n1, n2, _ = gadget.gate_sites()
+    strata, samples, firsts = _gate_strata_request(n1, n2, strata, samples, first_sample)
+    shards = [shard_range(first, count, rank, world) for first, count in zip(firsts.tolist(), samples.tolist())]
+    fn = local_fn or (lambda g, strata, ns, seed, first_sample: g.gate_strata(strata, ns, seed=seed, first_sample=first_sample))
+    part = fn(gadget, strata, [mine for _, mine in shards], seed=seed, first_sample=[start for start, _ in shards])
+    total, = all_reduce_histograms([part.counts.reshape(-1)], group=group)
+    return SampledGateStrata(n1, n2, strata, samples, total, part.fields)
 
 
 def enumerate_sharded(circuit, weights, group=None, local_fn=None):
