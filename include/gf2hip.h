@@ -733,6 +733,48 @@ int gf2_mc_ft_decode_gate_strata(gf2_ctx* ctx, const gf2_circuit* circuit, int64
                                  int64_t first_sample, int64_t nstrata, const int32_t* a, const int32_t* b, const int64_t* counts,
                                  uint64_t* counts_out);
 
+/* ---- direct Monte-Carlo of the two post-selected gadgets under gate-level faults ---------------------------
+ * [build-defined, DESIGN.md section 5e "Direct Monte-Carlo under gate-level faults"]  Every gate fails on its own: a one-operand
+ * gate with probability p_1 and one of its 3 kinds, a CNOT as one event with probability p_2 and one of its 15.  The sites, kind
+ * masks and outcome rule are those of "exact strata ... under gate-level faults" above, the draw is the sampler's ("Monte-Carlo"
+ * above) run once per class of sites, the kind rule that of the sampled gate strata.  Sample i is a pure function of
+ * (seed, i, p_1, p_2, n_1, n_2): ks = sample_key(seed, i), and for each of the two classes
+ *   one-operand sites:  m = n_1, radix 3,  site base 0,   T = quantise(p_1), slot base GF2_GATE_MC_SLOT_ONE;
+ *   CNOT sites:         m = n_2, radix 15, site base n_1, T = quantise(p_2), slot base GF2_GATE_MC_SLOT_CNOT
+ * cut into segments s = 0, 1, ... of 512 sites (nb = 512, or m - 512 s in the last; a class with m = 0 has none):
+ *   d = segment_draw(ks, slot base + s);  K = #{k < nb : (d >> 32) >= cdf[k]}, cdf = the inverse binomial CDF table of (T, nb);
+ *   for k < K: v = mix64(d + G (k + 1)), j = nb - K + k, t = ((v >> 32) (j + 1)) >> 32; the position is t unless an earlier pick
+ *   of this segment took t, then j (Floyd's rule); kappa = 1 + (((v & 0xFFFFFFFF) radix) >> 32); site = site base + 512 s + position.
+ * L <= 2^20 gives at most 2048 segments per class, so the two classes, the location sampler (slots below 2048) and every stratum
+ * (slots below 353) are disjoint streams of one seed.  The outcome words are the XOR over the picks and the set bits t of each kappa
+ * of eff[site_loc[site] + (t >> 1)][t & 1]; the sample is judged by the gadget's tally rule, post-selection included.  As for the
+ * sampler, an event rarer than 2^-32 per segment never occurs, and the kinds are uniform up to 2^-28 relative.
+ *
+ * The definition on the host, serial, no GPU needed: the outcome words (count x ldw, ldw >= ldr, the words past ldr left as they
+ * were, 1 <= ldr <= GF2_FT_MAX_LDR) of samples first_sample .. first_sample + count - 1 and, unless faults_out is null, int32
+ * [count][3] = (a, b, c): faulty one-operand gates, faulty CNOTs, CNOT picks with a two-operand kind.  gf2_ec_tally_host /
+ * gf2_ft_tally_host applied to the words complete the statement.  GF2_E_ARG for p_1 or p_2 outside [0, 1] (NaN included), a site
+ * table that is no partition of [0, L), a negative count or first_sample, ldw < ldr, ldr outside [1, GF2_FT_MAX_LDR]. */
+#define GF2_GATE_MC_SLOT_ONE  4096              /* first segment slot of the one-operand sites                     */
+#define GF2_GATE_MC_SLOT_CNOT 8192              /* ... and of the CNOT sites                                       */
+int gf2_gate_outcomes_host(const uint64_t* eff, int64_t locations, int64_t ldr, const int32_t* site_loc, int64_t n1, int64_t n2,
+                           uint64_t seed, int64_t first_sample, int64_t count, double p1, double p2, uint64_t* words_out, int64_t ldw,
+                           int32_t* faults_out);
+
+/* The tallies on the device: counts_out[GF2_EC_FIELDS] / counts_out[GF2_FT_FIELDS] of samples first_sample .. first_sample +
+ * count - 1, as gf2_mc_ec_decode / gf2_mc_ft_decode give them.  Circuit, layout, tables and site table as
+ * gf2_mc_ec_decode_gate_strata / gf2_mc_ft_decode_gate_strata check them, rates and range as the host statement does.  The four
+ * inverse-CDF tables, the hash tables and the device copy of site_loc are made per call and freed with it: the calls keep no state
+ * in the context.  A call is cut into launches of at most 2^36 samples. */
+int gf2_mc_ec_decode_gate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                          const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                          int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, uint64_t seed, int64_t first_sample,
+                          int64_t count, double p1, double p2, uint64_t* counts_out);
+int gf2_mc_ft_decode_gate(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                          const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                          const uint8_t* flips2, int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, uint64_t seed,
+                          int64_t first_sample, int64_t count, double p1, double p2, uint64_t* counts_out);
+
 /* ---- streamed gadgets: error-correction cycles and programs of any length, block by block ---------------
  * [build-defined, DESIGN.md "Streamed gadgets"]  Both ancilla blocks are RESET at the start of every preparation, so only the data
  * block survives from one block of a gadget -- the first preparation, an EC round, a MEASURE trial -- to the next.  A fault inside a

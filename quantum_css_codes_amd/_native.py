@@ -173,6 +173,12 @@ SIGNATURES = {
                                      _c_i64, _p, _p, _p, _p],
     "gf2_mc_ft_decode_gate_strata": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_u64,
                                      _c_i64, _c_i64, _p, _p, _p, _p],
+    "gf2_gate_outcomes_host": [_p, _c_i64, _c_i64, _p, _c_i64, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, _p, _c_i64,
+                               _p],
+    "gf2_mc_ec_decode_gate": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_u64, _c_i64, _c_i64,
+                              ctypes.c_double, ctypes.c_double, _p],
+    "gf2_mc_ft_decode_gate": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_u64, _c_i64,
+                              _c_i64, ctypes.c_double, ctypes.c_double, _p],
     "gf2_stream_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _c_i64, _p, _c_i64],
     "gf2_stream_tally_host": [_p, _c_i64, _c_i64, _p, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _p],
     "gf2_stream_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _pp],
@@ -606,6 +612,25 @@ def gate_stratum_outcomes_host(eff, site_loc, n1, n2, a, b, count, seed=0, first
     check(lib().gf2_gate_stratum_outcomes_host(_ptr(eff), eff.shape[0], eff.shape[2], _ptr(site_loc), int(n1), int(n2), int(a), int(b),
                                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, _ptr(out), ldw, _ptr(two)))
     return out[:max(0, count)], two[:max(0, count)]
+
+
+def gate_outcomes_host(eff, site_loc, n1, n2, count, p1, p2, seed=0, first=0, ldw=None, faults=True):
+    """gf2_gate_outcomes_host (host code, no GPU): (words, faults) of samples [first, first + count) of the direct Monte-Carlo under
+    gate-level faults -- every one-operand site of an effect table eff, (L, 2, ldr), fails with probability p1, every CNOT site with
+    p2: the (count, ldw) outcome words (ldw defaults to ldr; the words past ldr zero here) and the (count, 3) int32 numbers (a, b, c)
+    of faulty one-operand gates, faulty CNOTs and two-operand kinds per sample (None with faults=False)."""
+    eff = np.ascontiguousarray(eff, dtype="<u8")
+    if eff.ndim != 3 or eff.shape[1] != 2:
+        raise ValueError("eff must be (locations, 2, ldr)")
+    site_loc = _gate_sites(site_loc, n1, n2)
+    count = int(count)
+    ldw = eff.shape[2] if ldw is None else int(ldw)
+    out = np.zeros((max(1, count), max(1, ldw)), dtype="<u8")
+    abc = np.zeros((max(1, count), 3), dtype=np.int32) if faults else None
+    check(lib().gf2_gate_outcomes_host(_ptr(eff), eff.shape[0], eff.shape[2], _ptr(site_loc), int(n1), int(n2),
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p1), float(p2), _ptr(out), ldw,
+                                       _ptr(abc) if faults else None))
+    return out[:max(0, count)], (abc[:max(0, count)] if faults else None)
 
 
 def _gate_strata_arrays(strata, counts, fields):
@@ -1212,6 +1237,27 @@ class Context(object):
                                                  int(r2), *t2, _ptr(site_loc), int(n1), int(n2), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first),
                                                  len(counts), _ptr(wa), _ptr(wb), _ptr(counts), _ptr(out)))
         return out
+
+    def mc_ec_decode_gate(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, seed, first, count, p1, p2):
+        """gf2_mc_ec_decode_gate: mc_ec_decode's eight counts over samples [first, first + count) when every gate fails on its own,
+        a one-operand site of gate_sites' table with probability p1, a CNOT site with p2."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        site_loc = _gate_sites(site_loc, n1, n2)
+        counts = np.zeros(EC_FIELDS_COUNT, dtype=np.uint64)
+        check(lib().gf2_mc_ec_decode_gate(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, _ptr(site_loc), int(n1), int(n2),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(count), float(p1), float(p2), _ptr(counts)))
+        return counts
+
+    def mc_ft_decode_gate(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, seed, first, count,
+                          p1, p2):
+        """gf2_mc_ft_decode_gate: mc_ft_decode's seven counts, likewise."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        site_loc = _gate_sites(site_loc, n1, n2)
+        counts = np.zeros(FT_FIELDS_COUNT, dtype=np.uint64)
+        check(lib().gf2_mc_ft_decode_gate(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1,
+                                          int(r2), *t2, _ptr(site_loc), int(n1), int(n2), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first),
+                                          int(count), float(p1), float(p2), _ptr(counts)))
+        return counts
 
     def ec_enumerate_list(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):
         """gf2_ec_enumerate_list: ec_enumerate_list_host's (found, records) from the device, byte for byte."""

@@ -1089,6 +1089,122 @@ int gf2_gate_stratum_outcomes_host(const uint64_t* eff, int64_t locations, int64
 
 }  // extern "C"
 
+// ---- direct Monte-Carlo under gate-level faults (include/gf2hip.h "direct Monte-Carlo ... under gate-level faults") --
+// The argument rules of the two rates and of the sample range, shared by the host statement below and the device entry points
+// (gf2_gate_mc.hip).
+int gf2_gate_check_mc(const char* who, double p1, double p2, int64_t first_sample, int64_t count) {
+    if (!(p1 >= 0.0) || !(p1 <= 1.0) || !(p2 >= 0.0) || !(p2 <= 1.0))
+        GF2_FAIL(GF2_E_ARG, "%s: needs 0 <= p_1, p_2 <= 1, got p_1 = %g and p_2 = %g", who, p1, p2);
+    if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "%s: negative range (needs count >= 0 and first_sample >= 0)", who);
+    return GF2_OK;
+}
+
+// binomial_cdf_direct and binomial_cdf_table of gf2_sampler.h (that header is device code) in the same IEEE operations, in this order.
+static void host_binomial_cdf_direct(uint64_t t_any, int nb, uint64_t* cdf, int cap) {
+    for (int k = 0; k < cap; ++k) cdf[k] = 4294967296ull;
+    if (nb <= 0) return;
+    if (t_any >= 4294967296ull) {
+        for (int k = 0; k < nb; ++k) cdf[k] = 0;
+        return;
+    }
+    const double q = (double)t_any / 4294967296.0, om = 1.0 - q;
+    double pmf = 1.0;
+    for (int i = 0; i < nb; ++i) pmf *= om;
+    double cum = 0.0;
+    for (int k = 0; k < nb; ++k) {
+        cum += pmf;
+        double c = __builtin_floor(cum * 4294967296.0 + 0.5);
+        if (c > 4294967296.0) c = 4294967296.0;
+        cdf[k] = (uint64_t)c;
+        pmf = pmf * (double)(nb - k) / (double)(k + 1) * q / om;
+    }
+}
+
+static void host_binomial_cdf_table(uint64_t t_any, int nb, uint64_t* cdf) {     // cdf[513]: a segment's 512 sites and one
+    const int cap = 513;
+    if (t_any <= 2147483648ull || t_any >= 4294967296ull) {
+        host_binomial_cdf_direct(t_any, nb, cdf, cap);
+        return;
+    }
+    uint64_t other[513];
+    host_binomial_cdf_direct(4294967296ull - t_any, nb, other, cap);
+    for (int k = 0; k < cap; ++k) cdf[k] = 4294967296ull;
+    for (int k = 0; k < nb; ++k) cdf[k] = 4294967296ull - other[nb - k - 1];
+}
+
+extern "C" {
+
+// The outcome words and fault counts of a gadget's samples when every gate fails on its own, the host statement of what
+// gate_mc_kernel draws: the segment sampler of gf2_sampler.h run over the one-operand sites and then over the CNOT sites, each class
+// with its own slots, rate and radix of kinds, a pick's effects XOR-ed as gf2_gate_stratum_outcomes_host does.  gf2_ec_tally_host /
+// gf2_ft_tally_host judge the words; no tally rule is repeated here.
+int gf2_gate_outcomes_host(const uint64_t* eff, int64_t locations, int64_t ldr, const int32_t* site_loc, int64_t n1, int64_t n2,
+                           uint64_t seed, int64_t first_sample, int64_t count, double p1, double p2, uint64_t* words_out, int64_t ldw,
+                           int32_t* faults_out) {
+    const char* who = "gf2_gate_outcomes_host";
+    if (!eff) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (ldr < 1 || ldr > GF2_FT_MAX_LDR) GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= ldr <= %d words per effect, got %lld", who, GF2_FT_MAX_LDR, (long long)ldr);
+    if (int rc = gf2_gate_check_sites(who, locations, site_loc, n1, n2)) return rc;
+    if (int rc = gf2_gate_check_mc(who, p1, p2, first_sample, count)) return rc;
+    if (ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the table's %lld words", who, (long long)ldr);
+    if (count > 0 && !words_out) GF2_FAIL(GF2_E_ARG, "%s: null buffer", who);
+    const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
+    const int SEG = 512;
+    const int64_t m[2] = {n1, n2}, site_base[2] = {0, n1};
+    const uint64_t radix[2] = {3, 15}, slot_base[2] = {GF2_GATE_MC_SLOT_ONE, GF2_GATE_MC_SLOT_CNOT};
+    const uint64_t T[2] = {host_quantise(p1), host_quantise(p2)};
+    std::vector<uint64_t> cdf;                                                   // [class][whole, last][SEG + 1]
+    try {
+        cdf.resize(4 * (SEG + 1));
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    for (int cl = 0; cl < 2; ++cl) {
+        host_binomial_cdf_table(T[cl], SEG, &cdf[(2 * cl) * (SEG + 1)]);
+        host_binomial_cdf_table(T[cl], m[cl] > 0 ? (int)(m[cl] - ((m[cl] - 1) / SEG) * SEG) : 0, &cdf[(2 * cl + 1) * (SEG + 1)]);
+    }
+    for (int64_t i = 0; i < count; ++i) {
+        uint64_t* const out = words_out + i * ldw;
+        for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
+        const uint64_t ks = host_mix64(seed + golden * ((uint64_t)(first_sample + i) + 1));
+        int32_t faults[3] = {0, 0, 0};
+        for (int cl = 0; cl < 2; ++cl) {
+            const int64_t nseg = (m[cl] + SEG - 1) / SEG;                        // (none for an empty class)
+            for (int64_t s = 0; s < nseg; ++s) {
+                const bool last = s == nseg - 1;
+                const int nb = last ? (int)(m[cl] - SEG * s) : SEG;
+                const uint64_t* table = &cdf[(2 * cl + (last ? 1 : 0)) * (SEG + 1)];
+                const uint64_t d = host_mix64(ks + stream * (slot_base[cl] + (uint64_t)s + 1));
+                const uint64_t u = d >> 32;
+                int K = 0;
+                while (K < nb && u >= table[K]) K += 1;
+                uint64_t taken[SEG / 64] = {0, 0, 0, 0, 0, 0, 0, 0};
+                for (int k = 0; k < K; ++k) {
+                    const uint64_t v = host_mix64(d + golden * (uint64_t)(k + 1));
+                    const uint64_t hi = v >> 32, lo = v & 0xFFFFFFFFull;
+                    const uint64_t j = (uint64_t)(nb - K + k);
+                    const uint64_t t = (hi * (j + 1)) >> 32;                      // Floyd: a candidate in [0, j]
+                    const uint64_t pos = ((taken[t >> 6] >> (t & 63)) & 1ull) ? j : t;
+                    taken[pos >> 6] |= 1ull << (pos & 63);
+                    const uint64_t kappa = 1 + ((lo * radix[cl]) >> 32);
+                    const int64_t site = site_base[cl] + SEG * s + (int64_t)pos;
+                    const uint64_t* e = eff + (size_t)(2 * site_loc[site]) * ldr;  // effect t of the site: (2 l + t) ldr
+                    for (int bit = 0; bit < 4; ++bit)
+                        if ((kappa >> bit) & 1)
+                            for (int64_t q = 0; q < ldr; ++q) out[q] ^= e[bit * ldr + q];
+                    faults[cl] += 1;
+                    if (cl == 1) faults[2] += (kappa & 3) != 0 && (kappa >> 2) != 0;
+                }
+            }
+        }
+        if (faults_out)
+            for (int q = 0; q < 3; ++q) faults_out[3 * i + q] = faults[q];
+    }
+    return GF2_OK;
+}
+
+}  // extern "C"
+
 // ---- streamed gadgets (include/gf2hip.h "streamed gadgets") -------------------------------------------
 #include "gf2_stream_plan.h"
 

@@ -426,6 +426,13 @@ class CSSCode(QECC):
         from . import ec_noise
         return ec_noise.circuit_for(self, rounds, idle_data).gate_strata(strata, samples, **options)
 
+    def error_correct_gate_error_rates(self, num_samples, p1, p2, rounds=1, idle_data=False, **options):
+        """The direct Monte-Carlo of the cycle under gate-level faults: every one-operand gate fails with probability p1, every CNOT
+        as one event with probability p2, no truncation in the number of faulty gates (ec_noise.ECCircuit.gate_error_rates; DESIGN.md
+        section 5e "Direct Monte-Carlo under gate-level faults"): a dict of ec_noise.EC_FIELDS plus 'samples'."""
+        from . import ec_noise
+        return ec_noise.circuit_for(self, rounds, idle_data).gate_error_rates(num_samples, p1, p2, **options)
+
     def error_correct_gate_single_faults(self, rounds=1):
         """[build-defined]  The census of every single gate fault of the cycle, no GPU needed: ECCircuit.gate_single_faults."""
         from . import ec_noise
@@ -479,6 +486,13 @@ class CSSCode(QECC):
         montecarlo.SampledGateStrata, to be merged with logical_program_gate_strata_exact's."""
         from . import ft_noise
         return ft_noise.program_for(self, ops).gate_strata(strata, samples, **options)
+
+    def logical_program_gate_error_rates(self, ops, num_samples, p1, p2, **options):
+        """The direct Monte-Carlo of the rewritten program `ops; MEASURE` under gate-level faults, every gate failing on its own
+        (ft_noise.FTProgram.gate_error_rates; DESIGN.md section 5e "Direct Monte-Carlo under gate-level faults"): a dict of
+        ft_noise.FT_FIELDS plus 'samples'; wrong / accepted estimates the probability that the measured bit is wrong."""
+        from . import ft_noise
+        return ft_noise.program_for(self, ops).gate_error_rates(num_samples, p1, p2, **options)
 
     def logical_program_gate_single_faults(self, ops):
         """[build-defined]  The census of every single gate fault of the rewritten program, no GPU needed:

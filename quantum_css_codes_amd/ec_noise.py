@@ -364,6 +364,24 @@ class ECCircuit(object):
             run = lambda first, strata, ns: ctx.mc_ec_decode_gate_strata(circ, self.rounds, *tables, *sites, int(seed), int(first), strata, ns)
         return montecarlo.gate_strata_local(sites[1], sites[2], EC_FIELDS, strata, samples, first_sample, run)
 
+    def gate_error_rates(self, num_samples, p1, p2, seed=0, first_sample=0, host=False):
+        """The direct Monte-Carlo of the cycle under gate-level faults (DESIGN.md section 5e "Direct Monte-Carlo under gate-level
+        faults"): in samples [first_sample, first_sample + num_samples) every one-operand gate fails with probability p1 and one of
+        its 3 kinds, every CNOT as one event with probability p2 and one of its 15, and logical_error_rates' tally rule judges them,
+        post-selection included (gf2_mc_ec_decode_gate).  host=True draws with gf2_gate_outcomes_host and tallies with
+        gf2_ec_tally_host: no GPU.  Returns a dict of EC_FIELDS plus 'samples'; the counts of sample ranges add."""
+        tables, sites = self._tables(), self.gate_sites()[:3]
+        if host:
+            from . import montecarlo
+            counts = montecarlo.host_gate_counts(self.effects, sites, lambda words: _native.ec_tally_host(words, self.rounds, *tables),
+                                                 len(EC_FIELDS), num_samples, p1, p2, seed, first_sample)
+        else:
+            counts = _native.default_context().mc_ec_decode_gate(self.device(), self.rounds, *tables, *sites, int(seed), int(first_sample),
+                                                                 int(num_samples), float(p1), float(p2))
+        out = {name: int(v) for name, v in zip(EC_FIELDS, counts)}
+        out['samples'] = int(num_samples)
+        return out
+
     def gate_single_faults(self):
         """The census of every single gate fault, no GPU: (classes, flipping) -- classes (G, 15) uint8, the class byte (CLASS_* bits)
         of kind mask kappa (column kappa - 1; a one-operand gate uses columns 0 .. 2, the others stay 0) at every gate of the list;

@@ -290,6 +290,23 @@ class FTProgram(object):
                                                                          int(first), strata, ns)
         return montecarlo.gate_strata_local(sites[1], sites[2], FT_FIELDS, strata, samples, first_sample, run)
 
+    def gate_error_rates(self, num_samples, p1, p2, seed=0, first_sample=0, host=False):
+        """The direct Monte-Carlo of the measurement under gate-level faults (DESIGN.md section 5e "Direct Monte-Carlo under
+        gate-level faults"): every one-operand gate of the rewritten program fails with probability p1, every CNOT as one event with
+        probability p2, judged by measurement_error_rates' tally rule, post-selection included (gf2_mc_ft_decode_gate).  Arguments as
+        ECCircuit.gate_error_rates'; host=True goes through gf2_gate_outcomes_host and gf2_ft_tally_host and needs no GPU.  Returns a
+        dict of FT_FIELDS plus 'samples'."""
+        tables, sites = self._tables(), self.gate_sites()[:3]
+        if host:
+            from . import montecarlo
+            counts = montecarlo.host_gate_counts(self.effects, sites,
+                                                 lambda words: _native.ft_tally_host(words, self.nsteps, self.measure_mask, *tables),
+                                                 len(FT_FIELDS), num_samples, p1, p2, seed, first_sample)
+        else:
+            counts = _native.default_context().mc_ft_decode_gate(self.device(), self.nsteps, self.measure_mask, *tables, *sites, int(seed),
+                                                                 int(first_sample), int(num_samples), float(p1), float(p2))
+        return self._dict(counts, num_samples)
+
     def gate_single_faults(self):
         """The census of every single gate fault, no GPU: (classes, wrong) -- classes (G, 15) uint8, the class byte (CLASS_* bits) of
         kind mask kappa (column kappa - 1; a one-operand gate uses columns 0 .. 2) at every gate of the list; wrong, the accepted

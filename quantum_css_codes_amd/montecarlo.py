@@ -1343,6 +1343,42 @@ def gate_strata_sharded(gadget, strata, samples, seed=0, first_sample=0, group=N
     return SampledGateStrata(n1, n2, strata, samples, total, part.fields)
 
 
+def host_gate_counts(effects, sites, tally, nfields, num_samples, p1, p2, seed, first_sample, chunk=1 << 18):
+    """The counts of the direct Monte-Carlo under gate-level faults on the host (DESIGN.md section 5e "Direct Monte-Carlo under
+    gate-level faults"): gf2_gate_outcomes_host's words of samples [first_sample, first_sample + num_samples), `chunk` at a time,
+    handed to `tally` (words -> the gadget's counts; _native.ec_tally_host / ft_tally_host) and summed."""
+    if int(num_samples) < 0:
+        raise ValueError("negative sample count")
+    out = np.zeros(nfields, dtype=np.uint64)
+    if int(num_samples) == 0:                                           # (the native call still checks the other arguments)
+        _native.gate_outcomes_host(effects, *sites, 0, p1, p2, seed, int(first_sample), faults=False)
+    for done in range(0, int(num_samples), chunk):
+        words, _ = _native.gate_outcomes_host(effects, *sites, min(chunk, int(num_samples) - done), p1, p2, seed, int(first_sample) + done,
+                                              faults=False)
+        out += tally(words)
+    return out
+
+
+def gate_error_rates_sharded(gadget, num_samples, p1, p2, seed=0, first_sample=0, group=None, local_fn=None):
+    """The direct Monte-Carlo under gate-level faults of an ec_noise.ECCircuit or an ft_noise.FTProgram over the ranks of a process
+    group: the sample range is cut by shard_range, this rank runs its part, and one all-reduce sums the counts (counts of sample
+    ranges add).  `local_fn(gadget, num_samples, p1, p2, seed=, first_sample=)` replaces gadget.gate_error_rates (the CPU tests pass
+    the host statement).  Returns gate_error_rates' dict with the whole sample count."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+    else:
+        rank, world = 0, 1
+    start, mine = shard_range(first_sample, num_samples, rank, world)
+    fn = local_fn or (lambda g, n, p1, p2, seed, first_sample: g.gate_error_rates(n, p1, p2, seed=seed, first_sample=first_sample))
+    part = fn(gadget, mine, p1, p2, seed=seed, first_sample=start)
+    names = [name for name in part if name != 'samples']
+    total, = all_reduce_histograms([np.array([part[name] for name in names], dtype=np.uint64)], group=group)
+    out = {name: int(v) for name, v in zip(names, total)}
+    out['samples'] = int(num_samples)
+    return out
+
+
 def enumerate_sharded(circuit, weights, group=None, local_fn=None):
     """The whole strata `weights` of a FaultCircuit over the ranks of a process group: every weight's rank range [0, C(L, w)) is cut
     by shard_range, this rank enumerates its part, and one all-reduce sums the counts.  `local_fn(circuit, weights, first_rank,
