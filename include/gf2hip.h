@@ -845,6 +845,62 @@ int gf2_mc_stream_decode(gf2_ctx* ctx, const gf2_stream* stream, int64_t r1, con
                          int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed, int64_t first_sample,
                          int64_t count, double p_x, double p_y, double p_z, uint64_t* counts_out);
 
+/* ---- repeat-until-success: every preparation of a streamed gadget retried on its own ------------------------
+ * [build-defined, DESIGN.md section 5d "Repeat-until-success"]  The streamed route gives every preparation one attempt and rejects a
+ * sample when any verification fires.  Here a block type is cut into REGIONS, consecutive (first location, count, retried) that
+ * partition its locations in order; a retried region (a preparation with its verifications) is redrawn until its own flag rows are
+ * zero.  Locations fail independently and a flag row depends on one region only, so the accepted samples have the distribution
+ * post-selection gives, at a cost linear in the number of blocks.  type_regions holds the types' regions one after the other, three
+ * int64 each; type_nregions[t] is their number for type t.  Besides the sequence rules of gf2_stream_words_host, GF2_E_ARG naming
+ * the rule: regions that do not partition a type's locations in order, a region that is not retried whose locations set a flag
+ * bit, two regions of a type whose flag masks (OR of the flag words of a region's locations) intersect, max_attempts outside
+ * [1, GF2_RETRY_MAX_ATTEMPTS], more than GF2_RETRY_MAX_SIZES distinct segment sizes (one inverse-CDF table each).
+ *
+ * Sample i is a pure function of (seed, i, p_x, p_y, p_z, the sequence, its regions, max_attempts).  ks = sample_key(seed, i).
+ * Region g -- the g-th region of the whole sequence, counted through the blocks in order -- and attempt a = 0, 1, ... have the keys
+ *   kr = segment_draw(ks, 2^32 + g),  ka = mix64(kr + G (a + 1)).
+ * The region's locations are cut into segments s = 0, 1, ... of 512 from its first location (nb = 512, or what is left in its last
+ * segment): d = segment_draw(ka, s), K = #{k < nb : (d >> 32) >= cdf[k]} with the inverse binomial CDF table of (T_any, nb), and the
+ * picks, Floyd's rule and the kinds are the location sampler's (error_draw).  The slots 2^32 + g lie above those of every other
+ * stream of a seed.  A region that is not retried uses a = 0.  A retried one takes the first a < max_attempts whose flags are
+ * zero, and only that attempt's local and tail words enter the block; the key of (g, a) never depends on how many attempts earlier
+ * regions took.  With none the sample is EXHAUSTED: the walk stops, the step words from that block on stay 0 and the flag words
+ * hold the last attempt's flags at that block's flag rows.  Blocks, steps and tally as "streamed gadgets" above.
+ * Layout of a sample, nsteps + F + 1 words: [step 0 .. nsteps - 1] [F flag words, zero for an accepted sample] [attempts: the
+ * sample's attempts over all its retried regions]. */
+#define GF2_RETRY_FIELDS 14                     /* the GF2_STREAM_FIELDS (accepted: not exhausted), exhausted, attempts */
+#define GF2_RETRY_MAX_ATTEMPTS 65536
+#define GF2_RETRY_MAX_SIZES 16                  /* distinct segment sizes of a sequence's regions: the kernel's inverse-CDF tables */
+typedef struct gf2_retry gf2_retry;
+
+/* The words on the host, serial, no GPU needed: words_out is count x ldw (ldw >= nsteps + F + 1), the words past those left as
+ * they were.  attempts_out (may be null): uint32 [count][retried regions of the sequence], the attempts of every preparation in
+ * order, 0 for one never reached.  gf2_stream_tally_host on the first nsteps + F words completes the statement: an exhausted sample
+ * has a non-zero flag word and is rejected there.  GF2_E_ARG also for a negative count or first_sample and for bad rates. */
+int gf2_retry_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                         const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                         const int64_t* type_nregions, uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z,
+                         int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out);
+
+/* A sequence and its regions on the device.  Argument rules as gf2_retry_words_host's (max_attempts belongs to the calls).
+ * Destroyed by gf2_retry_destroy. */
+int gf2_retry_create(gf2_ctx* ctx, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                     const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                     const int64_t* type_nregions, gf2_retry** retry_out);
+int gf2_retry_destroy(gf2_ctx* ctx, gf2_retry* retry);
+
+/* The words of samples first_sample .. first_sample + count - 1 in device memory, ldo >= nsteps + F + 1 words per sample; words past
+ * those are left as they were.  out_dev: any 8-byte-aligned address. */
+int gf2_retry_outcomes_dev(gf2_ctx* ctx, const gf2_retry* retry, uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y,
+                           double p_z, int64_t max_attempts, uint64_t* out_dev, int64_t ldo);
+
+/* The tally of those samples on the device, no word stored.  counts_out[GF2_RETRY_FIELDS] on the host: the twelve streamed fields
+ * with accepted = not exhausted, then exhausted, then the attempts of all samples of the call.  Counts of sample ranges add.  The
+ * inverse-CDF tables are made per call and freed with it: the calls keep no state beyond the handle. */
+int gf2_mc_retry_decode(gf2_ctx* ctx, const gf2_retry* retry, int64_t r1, const uint64_t* keys1, const uint8_t* flips1, int64_t entries1,
+                        int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed, int64_t first_sample,
+                        int64_t count, double p_x, double p_y, double p_z, int64_t max_attempts, uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

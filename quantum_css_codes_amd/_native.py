@@ -25,6 +25,7 @@ EC_FIELDS_COUNT, EC_MAX_ROUNDS = 8, 6
 FT_FIELDS_COUNT, FT_MAX_LDR = 7, 16
 STREAM_FIELDS_COUNT, STREAM_MAX_TYPES, STREAM_MAX_OVERLAP = 12, 64, 8
 STREAM_NONE, STREAM_EC, STREAM_MEASURE, STREAM_FINAL = 0, 1, 2, 3
+RETRY_FIELDS_COUNT, RETRY_MAX_ATTEMPTS, RETRY_MAX_SIZES = 14, 65536, 16
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 ENUMERATE_MAX_WEIGHT = 8
@@ -186,6 +187,13 @@ SIGNATURES = {
     "gf2_stream_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p, _c_i64],
     "gf2_mc_stream_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
                              ctypes.c_double, _p],
+    "gf2_retry_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                             _c_i64, _p, _c_i64, _p],
+    "gf2_retry_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _pp],
+    "gf2_retry_destroy": [_p, _p],
+    "gf2_retry_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_i64, _p, _c_i64],
+    "gf2_mc_retry_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
+                            ctypes.c_double, _c_i64, _p],
     "gf2_comm_unique_id": [_p, ctypes.c_size_t],
     "gf2_comm_create": [_p, _p, ctypes.c_int, ctypes.c_int, _pp],
     "gf2_comm_create_all": [_pp, ctypes.c_int, _pp],
@@ -469,6 +477,29 @@ def stream_tally_host(words, block_kind, flag_words, r1, keys1, flips1, r2, keys
     check(lib().gf2_stream_tally_host(_ptr(words) if len(words) else None, len(words), words.shape[1], _ptr(kinds), len(kinds), int(flag_words),
                                       int(r1), *t1, int(r2), *t2, _ptr(counts), _ptr(cls) if classes else None))
     return (counts, cls[:len(words)]) if classes else counts
+
+
+def _retry_regions(type_regions, type_nregions, ntypes):
+    """The regions of a sequence's block types as the gf2_retry_* entry points take them, and their pointer arguments."""
+    regions = np.ascontiguousarray(type_regions, dtype=np.int64).reshape(-1, 3)
+    counts = np.ascontiguousarray(type_nregions, dtype=np.int64).reshape(-1)
+    if len(counts) != ntypes or int(counts.clip(0).sum()) != len(regions):
+        raise ValueError("one region count per type, type_regions as long as their sum")
+    return (regions, counts), (_ptr(regions) if len(regions) else None, _ptr(counts))
+
+
+def retry_words_host(type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, seed, first, count, p_x, p_y, p_z,
+                     max_attempts, ldw, preparations):
+    """gf2_retry_words_host (host code, no GPU): the (count, ldw) words [steps] [flag words] [attempts] of samples [first, first +
+    count) of the repeat-until-success sampler and the (count, preparations) uint32 attempts of every retried region."""
+    keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+    keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+    count = int(count)
+    out = np.zeros((max(1, count), max(1, int(ldw))), dtype="<u8")
+    attempts = np.zeros((max(1, count), max(1, int(preparations))), dtype=np.uint32)
+    check(lib().gf2_retry_words_host(*seq, *regions, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p_x), float(p_y), float(p_z),
+                                     int(max_attempts), _ptr(out), int(ldw), _ptr(attempts)))
+    return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
 
 
 def stratum_errors(nb, w, count, kinds=(1, 1, 1), seed=0, first=0):
@@ -819,6 +850,30 @@ class Stream(object):
             pass
 
 
+class Retry(object):
+    """A block sequence and its regions on the device (gf2_retry_create)."""
+
+    def __init__(self, ctx, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions):
+        self.ctx = ctx
+        keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+        keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+        out = ctypes.c_void_p()
+        check(lib().gf2_retry_create(ctx.handle, *seq, *regions, ctypes.byref(out)))
+        self.handle = out.value
+
+    def free(self):
+        if self.handle:
+            check(lib().gf2_retry_destroy(self.ctx.handle, self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            if self.handle and self.ctx.handle:
+                lib().gf2_retry_destroy(self.ctx.handle, self.handle)
+        except Exception:
+            pass
+
+
 class Context(object):
     """One HIP stream on one MI355X (gf2_ctx)."""
 
@@ -1138,6 +1193,21 @@ class Context(object):
         counts = np.zeros(STREAM_FIELDS_COUNT, dtype=np.uint64)
         check(lib().gf2_mc_stream_decode(self.handle, stream.handle, int(r1), *t1, int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF, first, count,
                                          p_x, p_y, p_z, _ptr(counts)))
+        return counts
+
+    def retry_create(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions):
+        return Retry(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions)
+
+    def retry_outcomes_dev(self, retry, seed, first, count, p_x, p_y, p_z, max_attempts, out_buf, ldo):
+        check(lib().gf2_retry_outcomes_dev(self.handle, retry.handle, seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, int(max_attempts),
+                                           out_buf.ptr, ldo))
+
+    def mc_retry_decode(self, retry, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z, max_attempts):
+        """gf2_mc_retry_decode: the fourteen counts of the repeat-until-success tally over samples [first, first + count)."""
+        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+        counts = np.zeros(RETRY_FIELDS_COUNT, dtype=np.uint64)
+        check(lib().gf2_mc_retry_decode(self.handle, retry.handle, int(r1), *t1, int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF, first, count,
+                                        p_x, p_y, p_z, int(max_attempts), _ptr(counts)))
         return counts
 
     def mc_circuit_decode_strata(self, circ, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x, k_y, k_z):

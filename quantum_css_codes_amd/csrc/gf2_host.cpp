@@ -1461,3 +1461,204 @@ int gf2_stream_tally_host(const uint64_t* words, int64_t count, int64_t ldw, con
 }
 
 }  // extern "C"
+
+// ---- repeat-until-success (include/gf2hip.h "repeat-until-success") -----------------------------------
+#include "gf2_retry_plan.h"
+
+int gf2_retry_plan(const char* who, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                   const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                   const int64_t* type_nregions, int64_t max_attempts, StreamPlan* plan, RetryPlan* retry) {
+    if (int rc = gf2_stream_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, plan)) return rc;
+    if (!type_regions || !type_nregions || !retry) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    int64_t total = 0;
+    for (int64_t t = 0; t < ntypes; ++t) {
+        if (type_nregions[t] < 1 || type_nregions[t] > type_locations[t])
+            GF2_FAIL(GF2_E_ARG, "%s: the regions of block type %lld do not partition its %lld locations in order: it has %lld regions", who,
+                     (long long)t, (long long)type_locations[t], (long long)type_nregions[t]);
+        total += type_nregions[t];
+    }
+    std::vector<uint64_t> masks;
+    try {
+        retry->type_first.assign((size_t)ntypes + 1, 0);
+        retry->first.assign((size_t)total, 0);
+        retry->count.assign((size_t)total, 0);
+        retry->retried.assign((size_t)total, 0);
+        retry->last_size.assign((size_t)total, 0);
+        retry->sizes.clear();
+        masks.assign((size_t)total, 0);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    std::vector<int32_t> sizes;                                                  // a set of at most GF2_RETRY_MAX_SIZES + 1 values
+    auto note_size = [&](int32_t nb) {
+        if (std::find(sizes.begin(), sizes.end(), nb) == sizes.end() && sizes.size() <= (size_t)GF2_RETRY_MAX_SIZES) sizes.push_back(nb);
+    };
+    int64_t at = 0;
+    try {
+        sizes.reserve(GF2_RETRY_MAX_SIZES + 1);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    for (int64_t t = 0; t < ntypes; ++t) {
+        retry->type_first[(size_t)t] = at;
+        int64_t next = 0;
+        for (int64_t r = 0; r < type_nregions[t]; ++r, ++at) {
+            const int64_t first = type_regions[3 * at], count = type_regions[3 * at + 1], retried = type_regions[3 * at + 2];
+            if (first != next || count < 1 || count > type_locations[t] - first || (retried != 0 && retried != 1))
+                GF2_FAIL(GF2_E_ARG, "%s: the regions of block type %lld do not partition its %lld locations in order: region %lld is "
+                         "(first %lld, count %lld, retried %lld) where location %lld is next", who, (long long)t, (long long)type_locations[t],
+                         (long long)r, (long long)first, (long long)count, (long long)retried, (long long)next);
+            next = first + count;
+            uint64_t mask = 0;
+            const uint64_t* e = type_eff + (size_t)(plan->type_offset[(size_t)t] + first) * 6;
+            for (int64_t l = 0; l < count; ++l) mask |= e[6 * l + 2] | e[6 * l + 5];
+            if (!retried && mask)
+                GF2_FAIL(GF2_E_ARG, "%s: region %lld of block type %lld (locations %lld .. %lld) is not retried but its locations set a flag bit", who,
+                         (long long)r, (long long)t, (long long)first, (long long)next - 1);
+            for (int64_t q = retry->type_first[(size_t)t]; q < at; ++q)
+                if (masks[(size_t)q] & mask)
+                    GF2_FAIL(GF2_E_ARG, "%s: the flag masks of regions %lld and %lld of block type %lld intersect: a flag row must depend on one "
+                             "region only", who, (long long)(q - retry->type_first[(size_t)t]), (long long)r, (long long)t);
+            masks[(size_t)at] = mask;
+            retry->first[(size_t)at] = (int32_t)first;
+            retry->count[(size_t)at] = (int32_t)count;
+            retry->retried[(size_t)at] = (int32_t)retried;
+            if (count > 512) note_size(512);
+            note_size((int32_t)(count - (count - 1) / 512 * 512));
+        }
+        if (next != type_locations[t])
+            GF2_FAIL(GF2_E_ARG, "%s: the regions of block type %lld do not partition its %lld locations in order: they end at location %lld", who,
+                     (long long)t, (long long)type_locations[t], (long long)next);
+    }
+    retry->type_first[(size_t)ntypes] = at;
+    if (max_attempts < 1 || max_attempts > GF2_RETRY_MAX_ATTEMPTS)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= max_attempts <= %d, got %lld", who, GF2_RETRY_MAX_ATTEMPTS, (long long)max_attempts);
+    if (sizes.size() > (size_t)GF2_RETRY_MAX_SIZES)
+        GF2_FAIL(GF2_E_ARG, "%s: the regions have more than GF2_RETRY_MAX_SIZES = %d distinct segment sizes, one inverse-CDF table each", who,
+                 GF2_RETRY_MAX_SIZES);
+    std::sort(sizes.begin(), sizes.end());
+    retry->sizes = sizes;
+    retry->full_size = !sizes.empty() && sizes.back() == 512 ? (int32_t)sizes.size() - 1 : -1;
+    for (int64_t q = 0; q < total; ++q) {
+        const int32_t nb = retry->count[(size_t)q] - (retry->count[(size_t)q] - 1) / 512 * 512;
+        retry->last_size[(size_t)q] = (int32_t)(std::find(sizes.begin(), sizes.end(), nb) - sizes.begin());
+    }
+    retry->regions = retry->preparations = 0;
+    for (int64_t b = 0; b < nblocks; ++b) {
+        if (block_kind[b] == GF2_STREAM_FINAL) continue;
+        const int64_t t = block_type[b];
+        retry->regions += type_nregions[t];
+        for (int64_t q = retry->type_first[(size_t)t]; q < retry->type_first[(size_t)t + 1]; ++q) retry->preparations += retry->retried[(size_t)q];
+    }
+    return GF2_OK;
+}
+
+int gf2_retry_check_range(const char* who, double p_x, double p_y, double p_z, int64_t first_sample, int64_t count) {
+    if (count < 0 || first_sample < 0) GF2_FAIL(GF2_E_ARG, "%s: negative range", who);
+    if (!(p_x >= 0.0) || !(p_y >= 0.0) || !(p_z >= 0.0) || p_x + p_y + p_z > 1.0 + 1e-12)
+        GF2_FAIL(GF2_E_ARG, "probabilities must be non-negative and sum to at most 1");
+    return GF2_OK;
+}
+
+extern "C" {
+
+// The definition of gf2_retry_outcomes_dev's words (DESIGN.md section 5d "Repeat-until-success"), serial: the blocks in order, the
+// regions of a block in order, a retried region redrawn under the key of (region, attempt) until its flags are zero.  The draw of a
+// segment is gf2_gate_outcomes_host's with the location sampler's kinds; the block rule is gf2_stream_words_host's.
+int gf2_retry_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                         const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                         const int64_t* type_nregions, uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z,
+                         int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out) {
+    const char* who = "gf2_retry_words_host";
+    StreamPlan plan;
+    RetryPlan retry;
+    if (int rc = gf2_retry_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
+                                max_attempts, &plan, &retry))
+        return rc;
+    if (int rc = gf2_retry_check_range(who, p_x, p_y, p_z, first_sample, count)) return rc;
+    const int64_t ldr = plan.nsteps + plan.flag_words + 1;
+    if (ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the sequence's nsteps + F + 1 = %lld words", who, (long long)ldr);
+    if (count == 0) return GF2_OK;
+    if (!words_out) GF2_FAIL(GF2_E_ARG, "%s: null buffer", who);
+    const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
+    const int SEG = 512;
+    const double p_t = p_x + p_y + p_z, p_xy = p_x + p_y;
+    const uint64_t t_any = host_quantise(p_t), t_1 = p_t > 0.0 ? host_quantise(p_x / p_t) : 0, t_2 = p_t > 0.0 ? host_quantise(p_xy / p_t) : 0;
+    std::vector<uint64_t> cdf;                                                   // [size][SEG + 1]
+    try {
+        cdf.resize(retry.sizes.size() * (SEG + 1));
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    for (size_t k = 0; k < retry.sizes.size(); ++k) host_binomial_cdf_table(t_any, retry.sizes[k], &cdf[k * (SEG + 1)]);
+    for (int64_t i = 0; i < count; ++i) {
+        uint64_t* const out = words_out + i * ldw;
+        for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
+        uint32_t* const tries = attempts_out ? attempts_out + i * retry.preparations : nullptr;
+        for (int64_t q = 0; tries && q < retry.preparations; ++q) tries[q] = 0;
+        const uint64_t ks = host_mix64(seed + golden * ((uint64_t)(first_sample + i) + 1));
+        uint64_t T = 0, attempts = 0;
+        int64_t g = 0, prep = 0;
+        bool exhausted = false;
+        for (int64_t b = 0; b < nblocks && !exhausted; ++b) {
+            uint64_t local = 0, tail = 0;
+            if (block_kind[b] != GF2_STREAM_FINAL) {
+                const int64_t t = block_type[b];
+                for (int64_t r = retry.type_first[(size_t)t]; r < retry.type_first[(size_t)t + 1] && !exhausted; ++r, ++g) {
+                    const int64_t rows = plan.type_offset[(size_t)t] + retry.first[(size_t)r], m = retry.count[(size_t)r];
+                    const int64_t nseg = (m + SEG - 1) / SEG, limit = retry.retried[(size_t)r] ? max_attempts : 1;
+                    const uint64_t kr = host_mix64(ks + stream * (GF2_RETRY_SLOT_BASE + (uint64_t)g + 1));
+                    uint64_t acc[3] = {0, 0, 0};
+                    int64_t a = 0;
+                    do {
+                        const uint64_t ka = host_mix64(kr + golden * ((uint64_t)a + 1));
+                        acc[0] = acc[1] = acc[2] = 0;
+                        for (int64_t s = 0; s < nseg; ++s) {
+                            const bool last = s == nseg - 1;
+                            const int nb = last ? (int)(m - SEG * s) : SEG;
+                            const uint64_t* table = &cdf[(size_t)(last ? retry.last_size[(size_t)r] : retry.full_size) * (SEG + 1)];
+                            const uint64_t d = host_mix64(ka + stream * ((uint64_t)s + 1));
+                            const uint64_t u = d >> 32;
+                            int K = 0;
+                            while (K < nb && u >= table[K]) K += 1;
+                            uint64_t taken[SEG / 64] = {0, 0, 0, 0, 0, 0, 0, 0};
+                            for (int k = 0; k < K; ++k) {
+                                const uint64_t v = host_mix64(d + golden * (uint64_t)(k + 1));
+                                const uint64_t j = (uint64_t)(nb - K + k);
+                                const uint64_t pick = ((v >> 32) * (j + 1)) >> 32;   // Floyd: a candidate in [0, j]
+                                const uint64_t pos = ((taken[pick >> 6] >> (pick & 63)) & 1ull) ? j : pick;
+                                taken[pos >> 6] |= 1ull << (pos & 63);
+                                const uint64_t c = v & 0xFFFFFFFFull;
+                                const int kind = (c < t_2 ? 1 : 0) | (c >= t_1 ? 2 : 0);
+                                const uint64_t* e = type_eff + (size_t)(rows + SEG * s + (int64_t)pos) * 6;
+                                for (int comp = 0; comp < 2; ++comp)
+                                    if (kind >> comp & 1)
+                                        for (int q = 0; q < 3; ++q) acc[q] ^= e[3 * comp + q];
+                            }
+                        }
+                        a += 1;
+                    } while (acc[2] != 0 && a < limit);
+                    if (retry.retried[(size_t)r]) {
+                        attempts += (uint64_t)a;
+                        if (tries) tries[prep] = (uint32_t)a;
+                        prep += 1;
+                    }
+                    if (acc[2] != 0) {                                           // no attempt passed: the walk stops here
+                        exhausted = true;
+                        const int64_t row = plan.flag[(size_t)b];
+                        out[plan.nsteps + (row >> 6)] |= acc[2] << (row & 63);
+                        if ((row & 63) && (acc[2] >> (64 - (row & 63)))) out[plan.nsteps + (row >> 6) + 1] |= acc[2] >> (64 - (row & 63));
+                    }
+                    local ^= acc[0], tail ^= acc[1];
+                }
+            }
+            if (exhausted) break;
+            if (plan.step[(size_t)b] >= 0) out[plan.step[(size_t)b]] = (T & gf2_stream_frame_mask(block_kind[b])) ^ local;
+            T ^= tail;
+        }
+        out[plan.nsteps + plan.flag_words] = attempts;
+    }
+    return GF2_OK;
+}
+
+}  // extern "C"

@@ -516,6 +516,23 @@ class CSSCode(QECC):
         gadget = stream_noise.stream_for(self, "program", ft_noise.check_ops(ops))
         return gadget.error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample)
 
+    def error_correct_retried_error_rates(self, num_samples, p_x, p_y, p_z, rounds, seed=0, first_sample=0, idle_data=False, max_attempts=256):
+        """[build-defined]  error_correct_streamed_error_rates with every preparation retried on its own until its verifications
+        pass (stream_noise.StreamedGadget.retry_error_rates), as the reference's while_do loops run them: essentially every sample is
+        accepted, whatever p and `rounds`.  The rates are those of the post-selected routes at every p; the samples are different
+        samples.  The dict also has 'exhausted' (samples with a preparation that failed max_attempts times), 'attempts' and
+        'preparations': attempts / (samples * preparations) is the mean number of attempts per preparation."""
+        from . import stream_noise
+        gadget = stream_noise.stream_for(self, "cycle", (int(rounds), bool(idle_data)))
+        return gadget.retry_error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample, max_attempts=max_attempts)
+
+    def logical_program_retried_error_rates(self, ops, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, max_attempts=256):
+        """[build-defined]  logical_program_streamed_error_rates with every preparation retried on its own, likewise.  The rates
+        are those of the post-selected routes at every p; the samples are different samples."""
+        from . import ft_noise, stream_noise
+        gadget = stream_noise.stream_for(self, "program", ft_noise.check_ops(ops))
+        return gadget.retry_error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample, max_attempts=max_attempts)
+
 
 # -- free functions -----------------------------------------------------------------------------------------
 

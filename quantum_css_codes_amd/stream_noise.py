@@ -26,6 +26,12 @@ resident routes', so sample i is the same sample on all of them.
 
 Acceptance falls like exp(-c p rounds): every preparation is post-selected, roughly 200 locations per Steane round reject the
 sample when they fail, so a run of `rounds` rounds keeps about exp(-200 p_kind rounds) of its samples.  Long runs are for p <~ 1e-4.
+
+Repeat-until-success (the retry_* methods; DESIGN.md section 5d "Repeat-until-success") lifts that limit: a block type is cut into
+BlockType.regions, every `prep ...` part of the builder a retried region, and a retried region is redrawn on its own until its
+verifications pass.  Locations fail independently and a flag row depends on one region only, so the accepted samples have exactly
+the distribution post-selection gives, essentially every sample is accepted, and the cost is linear in the number of blocks.  The
+samples are other samples than the post-selected routes draw: the rates agree, the counts of a seed do not.
 """
 import numpy as np
 
@@ -38,6 +44,7 @@ from .ec_noise import GATE_CNOT, GATE_IDLE, ROW_FINAL, ROW_ROUND
 NONE, EC, MEASURE, FINAL = _native.STREAM_NONE, _native.STREAM_EC, _native.STREAM_MEASURE, _native.STREAM_FINAL
 STREAM_FIELDS = ('accepted', 'logical_x', 'logical_z', 'logical_any', 'uncorrectable_x', 'uncorrectable_z', 'unmatched_x', 'unmatched_z',
                  'wrong', 'trial_wrong', 'first_trial_wrong', 'split_vote')
+RETRY_FIELDS = STREAM_FIELDS + ('exhausted', 'attempts')
 MAX_FLAG_ROWS = 64
 _BIT31, _BIT63 = np.uint64(1 << 31), np.uint64(1 << 63)
 FRAME_MASK = {NONE: np.uint64(0), EC: ~(_BIT31 | _BIT63), MEASURE: np.uint64(0xFFFFFFFF), FINAL: ~np.uint64(0)}   # what a step reads of T
@@ -48,7 +55,9 @@ _PROGRAM_FIELDS = (0, 8, 9, 10, 11, 6, 7)
 
 class BlockType(object):
     """One type of block: `name`, `kind` (NONE, EC or MEASURE), its gate list `gates` (g, 3) int32 on 3n qubits, `locations` (L_b, 2)
-    rows (gate, qubit), `num_flags` flag rows and `effects` (L_b, 2, 3) uint64: (local, tail, flags) of an X and of a Z fault."""
+    rows (gate, qubit), `num_flags` flag rows and `effects` (L_b, 2, 3) uint64: (local, tail, flags) of an X and of a Z fault;
+    `regions` (R, 3) int64 rows (first location, count, retried) that partition the locations in order -- every `prep ...` part of
+    the builder a retried region, the locations between and around them maximal regions that are not."""
 
     def __init__(self, code, name, kind, emit):
         build = ec_noise.GadgetBuilder(code)
@@ -68,10 +77,27 @@ class BlockType(object):
         self.gates = gates
         self.effects, self.locations = _native.circuit_effects_timed(gates, 3 * build.n, _native.pack_rows(rows_x), _native.pack_rows(rows_z),
                                                                      row_time, ldr=3)
+        gate_of = self.locations[:, 0]                              # non-descending: locations are in gate order
+        regions, at = [], 0
+        for first, stop, path in sorted(span for span in build.spans if span[2][-1].startswith("prep ")):
+            lo, hi = (int(v) for v in np.searchsorted(gate_of, [first, stop]))
+            if lo > at:
+                regions.append((at, lo - at, 0))
+            if hi > lo:
+                regions.append((lo, hi - lo, 1))
+            at = max(at, hi)
+        if at < len(gate_of):
+            regions.append((at, len(gate_of) - at, 0))
+        self.regions = np.array(regions, dtype=np.int64).reshape(-1, 3)
 
     @property
     def num_locations(self):
         return len(self.locations)
+
+    def region_masks(self):
+        """Per region, the OR of the flag words of its locations: the flag rows it sets."""
+        return np.array([np.bitwise_or.reduce(self.effects[first:first + count, :, 2].reshape(-1)) for first, count, _ in self.regions],
+                        dtype=np.uint64)
 
 
 def _emit_prepare(build):
@@ -122,7 +148,11 @@ class StreamedGadget(object):
         self.type_eff = np.ascontiguousarray(np.concatenate([t.effects for t in self.types]))
         self.type_locations = np.array([t.num_locations for t in self.types], dtype=np.int64)
         self.type_flags = np.array([t.num_flags for t in self.types], dtype=np.int64)
+        self.type_regions = np.ascontiguousarray(np.concatenate([t.regions for t in self.types]))
+        self.type_nregions = np.array([len(t.regions) for t in self.types], dtype=np.int64)
+        self.preparations = int(sum(int(self.types[t].regions[:, 2].sum()) for t in self.block_type if t >= 0))
         self._device = None
+        self._retry_device = None
 
     @classmethod
     def cycle(cls, code, rounds, idle_data=False):
@@ -267,6 +297,52 @@ class StreamedGadget(object):
         counts = got[0] if classes else got
         out = counts if fields else self._dict(counts, len(words))
         return (out, got[1]) if classes else out
+
+    # -- repeat-until-success ----------------------------------------------------------------------------------------------------
+    def _retry_sequence(self):
+        return self._sequence() + (self.type_regions, self.type_nregions)
+
+    def retry_device(self):
+        if self._retry_device is None:
+            self._retry_device = _native.default_context().retry_create(*self._retry_sequence())
+        return self._retry_device
+
+    def retry_outcomes(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, max_attempts=256):
+        """The words of samples [first_sample, first_sample + num_samples) of the repeat-until-success sampler, every preparation
+        retried until its verifications pass or max_attempts are used up: a (num_samples, ldw + 1) uint64 array [steps] [flag words,
+        zero unless the sample is exhausted] [attempts of the sample] (gf2_retry_outcomes_dev).  The rates are those of the
+        post-selected routes at every p; the samples are different samples."""
+        ctx = _native.default_context()
+        retry = self.retry_device()
+        count, ldo = int(num_samples), self.ldw + 1
+        buf = ctx.alloc(max(1, count) * ldo * 8)
+        ctx.retry_outcomes_dev(retry, int(seed), int(first_sample), count, float(p_x), float(p_y), float(p_z), int(max_attempts), buf, ldo)
+        out = buf.download((count, ldo), np.uint64)
+        buf.free()
+        return out
+
+    def retry_counts(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, max_attempts=256):
+        """The fourteen RETRY_FIELDS counts of samples [first_sample, first_sample + num_samples) on the device (gf2_mc_retry_decode):
+        the STREAM_FIELDS with accepted = not exhausted, the exhausted samples, the attempts of all samples.  The rates are those
+        of the post-selected routes at every p; the samples are different samples."""
+        return _native.default_context().mc_retry_decode(self.retry_device(), *self._tables(), int(seed), int(first_sample), int(num_samples),
+                                                         float(p_x), float(p_y), float(p_z), int(max_attempts))
+
+    def retry_error_rates(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, max_attempts=256):
+        """error_rates' dict from the repeat-until-success sampler, plus 'exhausted', 'attempts' and 'preparations' (the retried
+        regions per sample: attempts / (samples * preparations) is the mean number of attempts per preparation).  The rates are
+        those of the post-selected routes at every p; the samples are different samples.  The counts of sample ranges add."""
+        counts = self.retry_counts(num_samples, p_x, p_y, p_z, seed, first_sample, max_attempts)
+        out = self._dict(counts, num_samples)
+        out.update(exhausted=int(counts[12]), attempts=int(counts[13]), preparations=self.preparations)
+        return out
+
+    def retry_words_host(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, max_attempts=256):
+        """retry_outcomes' words on the host (gf2_retry_words_host, no GPU) and the (num_samples, preparations) uint32 attempts of
+        every preparation in order, 0 for one never reached.  tally_host on words[:, :ldw] completes the statement.  The rates are
+        those of the post-selected routes at every p; the samples are different samples."""
+        return _native.retry_words_host(*self._retry_sequence(), seed, first_sample, num_samples, p_x, p_y, p_z, max_attempts, self.ldw + 1,
+                                        self.preparations)
 
 
 def stream_for(code, what, key):
