@@ -4,6 +4,7 @@ ctypes binding of libgf2hip.so (include/gf2hip.h) and the packed-word helpers th
 There is no CPU fallback.  If the shared library is missing, or no gfx950 device is usable, the
 first compute call raises GF2Error -- the product never routes through oracle/ or NumPy arithmetic.
 """
+import collections
 import contextlib
 import ctypes
 import math
@@ -404,33 +405,74 @@ def circuit_effects_timed(gates, n, rows_x, rows_z, row_time, ldr=None):
     return eff[:total], locations[:total]
 
 
-def ec_tally_host(words, rounds, r1, keys1, flips1, r2, keys2, flips2, ldr=None, classes=False):
-    """gf2_ec_tally_host (host code, no GPU): the eight counts of the error-correction cycle's tally rule over outcome words
-    (count, ldw); ldr (default ldw) is the cycle's 1 + rounds + F.  classes=True also returns the class byte of every sample."""
+# ---- the tally rules of the gadgets ---------------------------------------------------------------------------------------------
+# A rule: the prefix of its entry points' and wrappers' names, its number of count fields, and `head`, which converts the arguments its
+# entry points take in front of the two syndrome tables.  Every family of entry points below is marshalled once, for all rules.
+Rule = collections.namedtuple("Rule", "name fields head")
+EC_RULE = Rule("ec", EC_FIELDS_COUNT, lambda rounds: (int(rounds),))
+FT_RULE = Rule("ft", FT_FIELDS_COUNT, lambda nsteps, measure_mask: (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF))
+CIRCUIT_RULE, STREAM_RULE, RETRY_RULE = (Rule(name, fields, lambda: ()) for name, fields in
+                                         (("circuit", 5), ("stream", STREAM_FIELDS_COUNT), ("retry", RETRY_FIELDS_COUNT)))
+
+
+def _enumerate_tables(keys1, flips1, keys2, flips2, null_flips=False):
+    """The two syndrome tables as the entry points take them: (the arrays, to keep alive; ((keys, flips, entries) of C1's, of C2's)).
+    An empty table is a null one; null_flips: flips may be None, a null pointer beside the keys (gf2_mc_circuit_decode takes it)."""
+    keep, tables = [], []
+    for keys, flips in ((keys1, flips1), (keys2, flips2)):
+        keys = np.ascontiguousarray(keys, dtype="<u8")
+        flips = None if flips is None and null_flips else np.ascontiguousarray(flips, dtype=np.uint8)
+        keep += [keys, flips]
+        tables.append((_ptr(keys) if len(keys) else None, _ptr(flips) if len(keys) and flips is not None else None, len(keys)))
+    return tuple(keep), tuple(tables)
+
+
+def _rule_arguments(rule, head, tables, null_flips=False):
+    """(arrays to keep alive, the arguments every entry point of a rule takes after its effect table or its handles): the rule's own,
+    then r and the (keys, flips, entries) of either table.  tables: (r1, keys1, flips1, r2, keys2, flips2)."""
+    r1, keys1, flips1, r2, keys2, flips2 = tables
+    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2, null_flips)
+    return keep, rule.head(*head) + (int(r1),) + t1 + (int(r2),) + t2
+
+
+def _effects(eff):
+    """An effect table (L, 2, ldr) as the host statements take it: (the array, to keep alive; (eff, locations, ldr))."""
+    eff = np.ascontiguousarray(eff, dtype="<u8")
+    if eff.ndim != 3 or eff.shape[1] != 2:
+        raise ValueError("eff must be (locations, 2, ldr)")
+    return eff, (_ptr(eff), eff.shape[0], eff.shape[2])
+
+
+def _tally_words(words):
     words = np.ascontiguousarray(words, dtype="<u8")
     if words.ndim != 2:
         raise ValueError("words must be (samples, ldw)")
-    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-    counts = np.zeros(EC_FIELDS_COUNT, dtype=np.uint64)
+    return words
+
+
+def _tally_host(fn, rule, words, middle, head, tables, classes):
+    """A gf2_*_tally_host entry point over `words` (_tally_words'); middle: its arguments between ldw and the rule's."""
+    keep, rest = _rule_arguments(rule, head, tables)
+    counts = np.zeros(rule.fields, dtype=np.uint64)
     cls = np.zeros(max(1, len(words)), dtype=np.uint8)
-    check(lib().gf2_ec_tally_host(_ptr(words) if len(words) else None, len(words), words.shape[1], words.shape[1] if ldr is None else int(ldr),
-                                  int(rounds), int(r1), *t1, int(r2), *t2, _ptr(counts), _ptr(cls) if classes else None))
+    check(fn(_ptr(words) if len(words) else None, len(words), words.shape[1], *middle, *rest, _ptr(counts), _ptr(cls) if classes else None))
     return (counts, cls[:len(words)]) if classes else counts
+
+
+def ec_tally_host(words, rounds, r1, keys1, flips1, r2, keys2, flips2, ldr=None, classes=False):
+    """gf2_ec_tally_host (host code, no GPU): the eight counts of the error-correction cycle's tally rule over outcome words
+    (count, ldw); ldr (default ldw) is the cycle's 1 + rounds + F.  classes=True also returns the class byte of every sample."""
+    words = _tally_words(words)
+    return _tally_host(lib().gf2_ec_tally_host, EC_RULE, words, (words.shape[1] if ldr is None else int(ldr),), (rounds,),
+                       (r1, keys1, flips1, r2, keys2, flips2), classes)
 
 
 def ft_tally_host(words, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, ldr=None, classes=False):
     """gf2_ft_tally_host (host code, no GPU): the seven counts of the logical measurement's tally rule over outcome words
     (count, ldw); ldr (default ldw) is the program's nsteps + F.  classes=True also returns the class byte of every sample."""
-    words = np.ascontiguousarray(words, dtype="<u8")
-    if words.ndim != 2:
-        raise ValueError("words must be (samples, ldw)")
-    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-    counts = np.zeros(FT_FIELDS_COUNT, dtype=np.uint64)
-    cls = np.zeros(max(1, len(words)), dtype=np.uint8)
-    check(lib().gf2_ft_tally_host(_ptr(words) if len(words) else None, len(words), words.shape[1], words.shape[1] if ldr is None else int(ldr),
-                                  int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2), *t2, _ptr(counts),
-                                  _ptr(cls) if classes else None))
-    return (counts, cls[:len(words)]) if classes else counts
+    words = _tally_words(words)
+    return _tally_host(lib().gf2_ft_tally_host, FT_RULE, words, (words.shape[1] if ldr is None else int(ldr),), (nsteps, measure_mask),
+                       (r1, keys1, flips1, r2, keys2, flips2), classes)
 
 
 def _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind):
@@ -467,16 +509,10 @@ def stream_words_host(type_eff, type_locations, type_flags, block_type, block_ki
 def stream_tally_host(words, block_kind, flag_words, r1, keys1, flips1, r2, keys2, flips2, classes=False):
     """gf2_stream_tally_host (host code, no GPU): the twelve counts of the streamed tally rule over stream-layout words (count, ldw).
     classes=True also returns the class byte of every sample."""
-    words = np.ascontiguousarray(words, dtype="<u8")
-    if words.ndim != 2:
-        raise ValueError("words must be (samples, ldw)")
+    words = _tally_words(words)
     kinds = np.ascontiguousarray(block_kind, dtype=np.int32).reshape(-1)
-    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-    counts = np.zeros(STREAM_FIELDS_COUNT, dtype=np.uint64)
-    cls = np.zeros(max(1, len(words)), dtype=np.uint8)
-    check(lib().gf2_stream_tally_host(_ptr(words) if len(words) else None, len(words), words.shape[1], _ptr(kinds), len(kinds), int(flag_words),
-                                      int(r1), *t1, int(r2), *t2, _ptr(counts), _ptr(cls) if classes else None))
-    return (counts, cls[:len(words)]) if classes else counts
+    return _tally_host(lib().gf2_stream_tally_host, STREAM_RULE, words, (_ptr(kinds), len(kinds), int(flag_words)), (),
+                       (r1, keys1, flips1, r2, keys2, flips2), classes)
 
 
 def _retry_regions(type_regions, type_nregions, ntypes):
@@ -518,24 +554,21 @@ def stratum_outcomes_host(eff, w, count, kinds=(1, 1, 1), seed=0, first=0, ldw=N
     """gf2_stratum_outcomes_host (host code, no GPU): the (count, ldw) outcome words of samples [first, first + count) of the stratum
     of weight w over the L locations of an effect table eff, (L, 2, ldr) as circuit_effects_timed returns it; ldw (default ldr) words
     per sample, those past ldr zero here."""
-    eff = np.ascontiguousarray(eff, dtype="<u8")
-    if eff.ndim != 3 or eff.shape[1] != 2:
-        raise ValueError("eff must be (locations, 2, ldr)")
+    eff, table = _effects(eff)
     count = int(count)
     ldw = eff.shape[2] if ldw is None else int(ldw)
     out = np.zeros((max(1, count), max(1, ldw)), dtype="<u8")
     k_x, k_y, k_z = (float(k) for k in kinds)
-    check(lib().gf2_stratum_outcomes_host(_ptr(eff), eff.shape[0], eff.shape[2], int(w), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count,
-                                          k_x, k_y, k_z, _ptr(out), ldw))
+    check(lib().gf2_stratum_outcomes_host(*table, int(w), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, k_x, k_y, k_z, _ptr(out), ldw))
     return out[:max(0, count)]
 
 
-def _strata_arrays(weights, counts):
+def _strata_arrays(weights, counts, fields=5):
     weights = np.ascontiguousarray(weights, dtype=np.int32).reshape(-1)
     counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
     if weights.shape != counts.shape:
         raise ValueError("one sample count per stratum")
-    return weights, counts, np.zeros((len(weights), 5), dtype=np.uint64)
+    return weights, counts, np.zeros((len(weights), fields), dtype=np.uint64)
 
 
 def subset_unrank(nb, w, rank):
@@ -548,50 +581,34 @@ def subset_unrank(nb, w, rank):
     return out[:max(0, int(w))]
 
 
-def _enumerate_tables(keys1, flips1, keys2, flips2):
-    k1, k2 = np.ascontiguousarray(keys1, dtype="<u8"), np.ascontiguousarray(keys2, dtype="<u8")
-    f1, f2 = np.ascontiguousarray(flips1, dtype=np.uint8), np.ascontiguousarray(flips2, dtype=np.uint8)
-    return (k1, f1, k2, f2), ((_ptr(k1) if len(k1) else None, _ptr(f1) if len(k1) else None, len(k1)),
-                              (_ptr(k2) if len(k2) else None, _ptr(f2) if len(k2) else None, len(k2)))
+def _enumerate(fn, rule, front, head, tables, w, first_rank, count):
+    """A gf2_*_enumerate(_host) entry point; front: (context, circuit) handles, or _effects' arguments for a host statement."""
+    keep, rest = _rule_arguments(rule, head, tables)
+    side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
+    out = np.zeros((side, side, rule.fields), dtype=np.uint64)
+    check(fn(*front, *rest, int(w), int(first_rank), int(count), _ptr(out)))
+    return out
 
 
 def circuit_enumerate_host(eff, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
     """gf2_circuit_enumerate_host (host code, no GPU): the (w + 1, w + 1, 5) uint64 counts [n_x][n_y][field] over the subsets of
     ranks [first_rank, first_rank + count), each with all 3^w kind assignments.  eff: (L, 2, ldr) as circuit_effects returns it."""
-    eff = np.ascontiguousarray(eff, dtype="<u8")
-    if eff.ndim != 3 or eff.shape[1] != 2:
-        raise ValueError("eff must be (locations, 2, ldr)")
-    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-    side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
-    out = np.zeros((side, side, 5), dtype=np.uint64)
-    check(lib().gf2_circuit_enumerate_host(_ptr(eff), eff.shape[0], eff.shape[2], r1, *t1, r2, *t2, int(w), int(first_rank), int(count),
-                                           _ptr(out)))
-    return out
-
-
-def _gadget_enumerate_host(fn, fields, eff, head, tables, w, first_rank, count):
-    eff = np.ascontiguousarray(eff, dtype="<u8")
-    if eff.ndim != 3 or eff.shape[1] != 2:
-        raise ValueError("eff must be (locations, 2, ldr)")
-    r1, keys1, flips1, r2, keys2, flips2 = tables
-    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-    side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
-    out = np.zeros((side, side, fields), dtype=np.uint64)
-    check(fn(_ptr(eff), eff.shape[0], eff.shape[2], *head, int(r1), *t1, int(r2), *t2, int(w), int(first_rank), int(count), _ptr(out)))
-    return out
+    eff, table = _effects(eff)
+    return _enumerate(lib().gf2_circuit_enumerate_host, CIRCUIT_RULE, table, (), (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count)
 
 
 def ec_enumerate_host(eff, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
     """gf2_ec_enumerate_host (host code, no GPU): the (w + 1, w + 1, 8) uint64 counts [n_x][n_y][field] of the error-correction
     cycle's tally rule over the subsets of ranks [first_rank, first_rank + count), each with all 3^w kind assignments."""
-    return _gadget_enumerate_host(lib().gf2_ec_enumerate_host, EC_FIELDS_COUNT, eff, (int(rounds),),
-                                  (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count)
+    eff, table = _effects(eff)
+    return _enumerate(lib().gf2_ec_enumerate_host, EC_RULE, table, (rounds,), (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count)
 
 
 def ft_enumerate_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
     """gf2_ft_enumerate_host (host code, no GPU): the (w + 1, w + 1, 7) counts of the logical measurement's tally rule, likewise."""
-    return _gadget_enumerate_host(lib().gf2_ft_enumerate_host, FT_FIELDS_COUNT, eff, (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF),
-                                  (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count)
+    eff, table = _effects(eff)
+    return _enumerate(lib().gf2_ft_enumerate_host, FT_RULE, table, (nsteps, measure_mask), (r1, keys1, flips1, r2, keys2, flips2), w,
+                      first_rank, count)
 
 
 def _gate_sites(site_loc, n1, n2):
@@ -601,47 +618,49 @@ def _gate_sites(site_loc, n1, n2):
     return sites
 
 
-def _gate_enumerate_host(fn, fields, eff, head, tables, sites, w, b, first_rank, count):
-    eff = np.ascontiguousarray(eff, dtype="<u8")
-    if eff.ndim != 3 or eff.shape[1] != 2:
-        raise ValueError("eff must be (locations, 2, ldr)")
-    r1, keys1, flips1, r2, keys2, flips2 = tables
-    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
+def _gate_arguments(rule, head, tables, sites):
+    """_rule_arguments followed by the site table (site_loc, n1, n2) of the gate-level fault model."""
+    keep, rest = _rule_arguments(rule, head, tables)
     site_loc, n1, n2 = sites
     site_loc = _gate_sites(site_loc, n1, n2)
-    out = np.zeros((max(0, min(int(b), GATE_ENUMERATE_MAX_WEIGHT)) + 1, fields), dtype=np.uint64)
-    check(fn(_ptr(eff), eff.shape[0], eff.shape[2], *head, int(r1), *t1, int(r2), *t2, _ptr(site_loc), int(n1), int(n2), int(w), int(b),
-             int(first_rank), int(count), _ptr(out)))
+    return (keep, site_loc), rest + (_ptr(site_loc), int(n1), int(n2))
+
+
+def _gate_enumerate(fn, rule, front, head, tables, sites, w, b, first_rank, count):
+    """A gf2_*_gate_enumerate(_host) entry point; front as _enumerate's."""
+    keep, rest = _gate_arguments(rule, head, tables, sites)
+    out = np.zeros((max(0, min(int(b), GATE_ENUMERATE_MAX_WEIGHT)) + 1, rule.fields), dtype=np.uint64)
+    check(fn(*front, *rest, int(w), int(b), int(first_rank), int(count), _ptr(out)))
     return out
 
 
 def ec_gate_enumerate_host(eff, rounds, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count):
     """gf2_ec_gate_enumerate_host (host code, no GPU): the (b + 1, 8) uint64 counts [c][field] of the error-correction cycle's tally
     rule over the site subsets of ranks [first_rank, first_rank + count) of (w, b), each with all 3^(w - b) 15^b kind assignments."""
-    return _gate_enumerate_host(lib().gf2_ec_gate_enumerate_host, EC_FIELDS_COUNT, eff, (int(rounds),), (r1, keys1, flips1, r2, keys2, flips2),
-                                (site_loc, n1, n2), w, b, first_rank, count)
+    eff, table = _effects(eff)
+    return _gate_enumerate(lib().gf2_ec_gate_enumerate_host, EC_RULE, table, (rounds,), (r1, keys1, flips1, r2, keys2, flips2),
+                           (site_loc, n1, n2), w, b, first_rank, count)
 
 
 def ft_gate_enumerate_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count):
     """gf2_ft_gate_enumerate_host (host code, no GPU): the (b + 1, 7) counts of the logical measurement's tally rule, likewise."""
-    return _gate_enumerate_host(lib().gf2_ft_gate_enumerate_host, FT_FIELDS_COUNT, eff, (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF),
-                                (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), w, b, first_rank, count)
+    eff, table = _effects(eff)
+    return _gate_enumerate(lib().gf2_ft_gate_enumerate_host, FT_RULE, table, (nsteps, measure_mask), (r1, keys1, flips1, r2, keys2, flips2),
+                           (site_loc, n1, n2), w, b, first_rank, count)
 
 
 def gate_stratum_outcomes_host(eff, site_loc, n1, n2, a, b, count, seed=0, first=0, ldw=None):
     """gf2_gate_stratum_outcomes_host (host code, no GPU): (words, c) of samples [first, first + count) of the stratum of a faulty
     one-operand gates and b faulty CNOTs among the sites of an effect table eff, (L, 2, ldr): the (count, ldw) outcome words (ldw
     defaults to ldr; the words past ldr zero here) and the (count,) uint8 number of two-operand kinds per sample."""
-    eff = np.ascontiguousarray(eff, dtype="<u8")
-    if eff.ndim != 3 or eff.shape[1] != 2:
-        raise ValueError("eff must be (locations, 2, ldr)")
+    eff, table = _effects(eff)
     site_loc = _gate_sites(site_loc, n1, n2)
     count = int(count)
     ldw = eff.shape[2] if ldw is None else int(ldw)
     out = np.zeros((max(1, count), max(1, ldw)), dtype="<u8")
     two = np.zeros(max(1, count), dtype=np.uint8)
-    check(lib().gf2_gate_stratum_outcomes_host(_ptr(eff), eff.shape[0], eff.shape[2], _ptr(site_loc), int(n1), int(n2), int(a), int(b),
-                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, _ptr(out), ldw, _ptr(two)))
+    check(lib().gf2_gate_stratum_outcomes_host(*table, _ptr(site_loc), int(n1), int(n2), int(a), int(b), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                               int(first), count, _ptr(out), ldw, _ptr(two)))
     return out[:max(0, count)], two[:max(0, count)]
 
 
@@ -650,17 +669,14 @@ def gate_outcomes_host(eff, site_loc, n1, n2, count, p1, p2, seed=0, first=0, ld
     gate-level faults -- every one-operand site of an effect table eff, (L, 2, ldr), fails with probability p1, every CNOT site with
     p2: the (count, ldw) outcome words (ldw defaults to ldr; the words past ldr zero here) and the (count, 3) int32 numbers (a, b, c)
     of faulty one-operand gates, faulty CNOTs and two-operand kinds per sample (None with faults=False)."""
-    eff = np.ascontiguousarray(eff, dtype="<u8")
-    if eff.ndim != 3 or eff.shape[1] != 2:
-        raise ValueError("eff must be (locations, 2, ldr)")
+    eff, table = _effects(eff)
     site_loc = _gate_sites(site_loc, n1, n2)
     count = int(count)
     ldw = eff.shape[2] if ldw is None else int(ldw)
     out = np.zeros((max(1, count), max(1, ldw)), dtype="<u8")
     abc = np.zeros((max(1, count), 3), dtype=np.int32) if faults else None
-    check(lib().gf2_gate_outcomes_host(_ptr(eff), eff.shape[0], eff.shape[2], _ptr(site_loc), int(n1), int(n2),
-                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p1), float(p2), _ptr(out), ldw,
-                                       _ptr(abc) if faults else None))
+    check(lib().gf2_gate_outcomes_host(*table, _ptr(site_loc), int(n1), int(n2), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count,
+                                       float(p1), float(p2), _ptr(out), ldw, _ptr(abc) if faults else None))
     return out[:max(0, count)], (abc[:max(0, count)] if faults else None)
 
 
@@ -673,39 +689,65 @@ def _gate_strata_arrays(strata, counts, fields):
             np.zeros((len(counts), GATE_STRATUM_MAX_WEIGHT + 1, fields), dtype=np.uint64))
 
 
-def _fault_list_call(fn, head, select, capacity, limit=None):
-    """One call of a gf2_*_enumerate_list* entry point: (found, records) -- records the (found, 2) uint64 words, or None when
-    `capacity` records (0: just count) do not hold them.  limit: the capacity above which the entry point refuses the call."""
+def _enumerate_list(fn, rule, front, head, tables, w, first_rank, count, select, capacity, limit=None):
+    """A gf2_*_enumerate_list(_host) entry point, front as _enumerate's: (found, records) -- records the (found, 2) uint64 words, or
+    None when `capacity` records (0: just count) do not hold them.  limit: the capacity above which the entry point refuses the call."""
+    keep, rest = _rule_arguments(rule, head, tables)
     capacity = int(capacity)
     records = np.zeros((max(1, capacity if limit is None else min(capacity, limit)), FAULT_RECORD_WORDS), dtype="<u8")
     found = _c_i64(0)
-    check(fn(*head, int(select) & 0xFFFFFFFFFFFFFFFF, capacity, _ptr(records) if capacity > 0 else None, ctypes.byref(found)))
+    check(fn(*front, *rest, int(w), int(first_rank), int(count), int(select) & 0xFFFFFFFFFFFFFFFF, capacity,
+             _ptr(records) if capacity > 0 else None, ctypes.byref(found)))
     found = int(found.value)
     return found, (records[:found].copy() if found <= capacity else None)
-
-
-def _gadget_list_host(fn, eff, head, tables, w, first_rank, count, select, capacity):
-    eff = np.ascontiguousarray(eff, dtype="<u8")
-    if eff.ndim != 3 or eff.shape[1] != 2:
-        raise ValueError("eff must be (locations, 2, ldr)")
-    r1, keys1, flips1, r2, keys2, flips2 = tables
-    keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-    return _fault_list_call(fn, (_ptr(eff), eff.shape[0], eff.shape[2]) + tuple(head) + (int(r1),) + t1 + (int(r2),) + t2 +
-                            (int(w), int(first_rank), int(count)), select, capacity)
 
 
 def ec_enumerate_list_host(eff, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):
     """gf2_ec_enumerate_list_host (host code, no GPU): (found, records) of the error-correction cycle over the subsets of ranks
     [first_rank, first_rank + count) -- found, the number of accepted configurations whose class byte has a bit of `select`;
     records, their (found, 2) uint64 words sorted by (rank, kinds code), or None when `capacity` records do not hold them."""
-    return _gadget_list_host(lib().gf2_ec_enumerate_list_host, eff, (int(rounds),), (r1, keys1, flips1, r2, keys2, flips2), w, first_rank,
-                             count, select, capacity)
+    eff, table = _effects(eff)
+    return _enumerate_list(lib().gf2_ec_enumerate_list_host, EC_RULE, table, (rounds,), (r1, keys1, flips1, r2, keys2, flips2), w, first_rank,
+                           count, select, capacity)
 
 
 def ft_enumerate_list_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):
     """gf2_ft_enumerate_list_host (host code, no GPU): (found, records) of the logical measurement, likewise."""
-    return _gadget_list_host(lib().gf2_ft_enumerate_list_host, eff, (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF),
-                             (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count, select, capacity)
+    eff, table = _effects(eff)
+    return _enumerate_list(lib().gf2_ft_enumerate_list_host, FT_RULE, table, (nsteps, measure_mask), (r1, keys1, flips1, r2, keys2, flips2),
+                           w, first_rank, count, select, capacity)
+
+
+def _decode(fn, rule, front, head, tables, seed, first, count, p_x, p_y, p_z, *more, null_flips=False):
+    """A gf2_mc_*_decode entry point: the rule's counts over samples [first, first + count); more: its arguments after p_z."""
+    keep, rest = _rule_arguments(rule, head, tables, null_flips)
+    counts = np.zeros(rule.fields, dtype=np.uint64)
+    check(fn(*front, *rest, seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, *more, _ptr(counts)))
+    return counts
+
+
+def _decode_strata(fn, rule, front, head, tables, seed, first, weights, counts, k_x, k_y, k_z):
+    """A gf2_mc_*_decode_strata entry point: the (nstrata, fields) counts."""
+    keep, rest = _rule_arguments(rule, head, tables)
+    weights, counts, out = _strata_arrays(weights, counts, rule.fields)
+    check(fn(*front, *rest, seed & 0xFFFFFFFFFFFFFFFF, first, len(weights), _ptr(weights), _ptr(counts), k_x, k_y, k_z, _ptr(out)))
+    return out
+
+
+def _decode_gate_strata(fn, rule, front, head, tables, sites, seed, first, strata, counts):
+    """A gf2_mc_*_decode_gate_strata entry point: the (nstrata, 17, fields) counts [stratum][c][field]."""
+    keep, rest = _gate_arguments(rule, head, tables, sites)
+    wa, wb, counts, out = _gate_strata_arrays(strata, counts, rule.fields)
+    check(fn(*front, *rest, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), len(counts), _ptr(wa), _ptr(wb), _ptr(counts), _ptr(out)))
+    return out
+
+
+def _decode_gate(fn, rule, front, head, tables, sites, seed, first, count, p1, p2):
+    """A gf2_mc_*_decode_gate entry point: the rule's counts over samples [first, first + count)."""
+    keep, rest = _gate_arguments(rule, head, tables, sites)
+    counts = np.zeros(rule.fields, dtype=np.uint64)
+    check(fn(*front, *rest, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(count), float(p1), float(p2), _ptr(counts)))
+    return counts
 
 
 # ---- context ----------------------------------------------------------------------------------------------
@@ -771,8 +813,26 @@ class DeviceView(DeviceBuffer):
         pass
 
 
-class Check(object):
+class _Handle(object):
+    """An object on the device, owned by a Context: `ctx`, `handle`, and the name of the entry point that destroys it."""
+    _destroy = None
+
+    def free(self):
+        if self.handle:
+            check(getattr(lib(), self._destroy)(self.ctx.handle, self.handle))
+            self.handle = None
+
+    def __del__(self):
+        try:
+            if self.handle and self.ctx.handle:
+                getattr(lib(), self._destroy)(self.ctx.handle, self.handle)
+        except Exception:
+            pass
+
+
+class Check(_Handle):
     """A parity-check matrix prepared on the device (gf2_check_create)."""
+    _destroy = "gf2_check_destroy"
 
     def __init__(self, ctx, packed, r, n):
         self.ctx = ctx
@@ -787,21 +847,11 @@ class Check(object):
     def slabs(self):
         return max(1, words_for(self.r))
 
-    def free(self):
-        if self.handle:
-            check(lib().gf2_check_destroy(self.ctx.handle, self.handle))
-            self.handle = None
-
-    def __del__(self):
-        try:
-            if self.handle and self.ctx.handle:
-                lib().gf2_check_destroy(self.ctx.handle, self.handle)
-        except Exception:
-            pass
 
 
-class Circuit(object):
+class Circuit(_Handle):
     """The effect table of a circuit's fault locations on the device (gf2_circuit_create).  eff: (L, 2, ldr) packed words."""
+    _destroy = "gf2_circuit_destroy"
 
     def __init__(self, ctx, eff, ft=False):
         self.ctx = ctx
@@ -814,21 +864,11 @@ class Circuit(object):
         check(create(ctx.handle, _ptr(eff), self.locations, self.ldr, ctypes.byref(out)))
         self.handle = out.value
 
-    def free(self):
-        if self.handle:
-            check(lib().gf2_circuit_destroy(self.ctx.handle, self.handle))
-            self.handle = None
-
-    def __del__(self):
-        try:
-            if self.handle and self.ctx.handle:
-                lib().gf2_circuit_destroy(self.ctx.handle, self.handle)
-        except Exception:
-            pass
 
 
-class Stream(object):
+class Stream(_Handle):
     """A block sequence on the device (gf2_stream_create): the block types' tables (locations of all types, 2, 3) and the blocks."""
+    _destroy = "gf2_stream_destroy"
 
     def __init__(self, ctx, type_eff, type_locations, type_flags, block_type, block_kind):
         self.ctx = ctx
@@ -837,21 +877,11 @@ class Stream(object):
         check(lib().gf2_stream_create(ctx.handle, *seq, ctypes.byref(out)))
         self.handle = out.value
 
-    def free(self):
-        if self.handle:
-            check(lib().gf2_stream_destroy(self.ctx.handle, self.handle))
-            self.handle = None
-
-    def __del__(self):
-        try:
-            if self.handle and self.ctx.handle:
-                lib().gf2_stream_destroy(self.ctx.handle, self.handle)
-        except Exception:
-            pass
 
 
-class Retry(object):
+class Retry(_Handle):
     """A block sequence and its regions on the device (gf2_retry_create)."""
+    _destroy = "gf2_retry_destroy"
 
     def __init__(self, ctx, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions):
         self.ctx = ctx
@@ -861,17 +891,6 @@ class Retry(object):
         check(lib().gf2_retry_create(ctx.handle, *seq, *regions, ctypes.byref(out)))
         self.handle = out.value
 
-    def free(self):
-        if self.handle:
-            check(lib().gf2_retry_destroy(self.ctx.handle, self.handle))
-            self.handle = None
-
-    def __del__(self):
-        try:
-            if self.handle and self.ctx.handle:
-                lib().gf2_retry_destroy(self.ctx.handle, self.handle)
-        except Exception:
-            pass
 
 
 class Context(object):
@@ -893,6 +912,18 @@ class Context(object):
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)
+
+    def outcomes(self, fill, obj, seed, first, count, p_x, p_y, p_z, ldo, *more):
+        """The (count, ldo) uint64 words of samples [first, first + count) that `fill` -- this context's circuit_outcomes_dev,
+        ft_outcomes_dev, stream_outcomes_dev or retry_outcomes_dev (more: its max_attempts) -- writes for `obj`, through a device
+        buffer that is freed whether the call succeeds or raises."""
+        count = int(count)
+        buf = self.alloc(max(1, count) * ldo * 8)
+        try:
+            fill(obj, int(seed), int(first), count, float(p_x), float(p_y), float(p_z), *more, buf, ldo)
+            return buf.download((count, ldo), np.uint64)
+        finally:
+            buf.free()
 
     def fill_workspace(self, byte):
         """Testing: every byte of the four workspace slots set to `byte`; returns the slots' sizes in bytes."""
@@ -1145,26 +1176,13 @@ class Context(object):
     def mc_circuit_decode(self, circ, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z):
         """gf2_mc_circuit_decode: keys (entries x 1 or 2 words), flips (entries bytes; None with keys = a null table).  Returns
         the five counts."""
-        counts = np.zeros(5, dtype=np.uint64)
-        tables = []
-        for keys, flips in ((keys1, flips1), (keys2, flips2)):
-            keys = np.ascontiguousarray(keys, dtype="<u8")
-            entries = len(keys)
-            flips = None if flips is None else np.ascontiguousarray(flips, dtype=np.uint8)
-            tables.append((keys, flips, entries))
-        (k1, f1, e1), (k2, f2, e2) = tables
-        check(lib().gf2_mc_circuit_decode(self.handle, circ.handle, r1, _ptr(k1) if e1 else None, None if f1 is None or not e1 else _ptr(f1),
-                                          e1, r2, _ptr(k2) if e2 else None, None if f2 is None or not e2 else _ptr(f2), e2,
-                                          seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, _ptr(counts)))
-        return counts
+        return _decode(lib().gf2_mc_circuit_decode, CIRCUIT_RULE, (self.handle, circ.handle), (), (r1, keys1, flips1, r2, keys2, flips2),
+                       seed, first, count, p_x, p_y, p_z, null_flips=True)
 
     def mc_ec_decode(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z):
         """gf2_mc_ec_decode: the eight counts of the error-correction cycle's tally over samples [first, first + count)."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        counts = np.zeros(EC_FIELDS_COUNT, dtype=np.uint64)
-        check(lib().gf2_mc_ec_decode(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF, first,
-                                     count, p_x, p_y, p_z, _ptr(counts)))
-        return counts
+        return _decode(lib().gf2_mc_ec_decode, EC_RULE, (self.handle, circ.handle), (rounds,), (r1, keys1, flips1, r2, keys2, flips2),
+                       seed, first, count, p_x, p_y, p_z)
 
     def ft_circuit_create(self, eff):
         """gf2_ft_circuit_create: an effect table of up to FT_MAX_LDR words, for ft_outcomes_dev and mc_ft_decode only."""
@@ -1175,11 +1193,8 @@ class Context(object):
 
     def mc_ft_decode(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z):
         """gf2_mc_ft_decode: the seven counts of the logical measurement's tally over samples [first, first + count)."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        counts = np.zeros(FT_FIELDS_COUNT, dtype=np.uint64)
-        check(lib().gf2_mc_ft_decode(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2), *t2,
-                                     seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, _ptr(counts)))
-        return counts
+        return _decode(lib().gf2_mc_ft_decode, FT_RULE, (self.handle, circ.handle), (nsteps, measure_mask),
+                       (r1, keys1, flips1, r2, keys2, flips2), seed, first, count, p_x, p_y, p_z)
 
     def stream_create(self, type_eff, type_locations, type_flags, block_type, block_kind):
         return Stream(self, type_eff, type_locations, type_flags, block_type, block_kind)
@@ -1189,11 +1204,8 @@ class Context(object):
 
     def mc_stream_decode(self, stream, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z):
         """gf2_mc_stream_decode: the twelve counts of the streamed tally over samples [first, first + count)."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        counts = np.zeros(STREAM_FIELDS_COUNT, dtype=np.uint64)
-        check(lib().gf2_mc_stream_decode(self.handle, stream.handle, int(r1), *t1, int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF, first, count,
-                                         p_x, p_y, p_z, _ptr(counts)))
-        return counts
+        return _decode(lib().gf2_mc_stream_decode, STREAM_RULE, (self.handle, stream.handle), (), (r1, keys1, flips1, r2, keys2, flips2),
+                       seed, first, count, p_x, p_y, p_z)
 
     def retry_create(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions):
         return Retry(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions)
@@ -1204,143 +1216,84 @@ class Context(object):
 
     def mc_retry_decode(self, retry, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z, max_attempts):
         """gf2_mc_retry_decode: the fourteen counts of the repeat-until-success tally over samples [first, first + count)."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        counts = np.zeros(RETRY_FIELDS_COUNT, dtype=np.uint64)
-        check(lib().gf2_mc_retry_decode(self.handle, retry.handle, int(r1), *t1, int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF, first, count,
-                                        p_x, p_y, p_z, int(max_attempts), _ptr(counts)))
-        return counts
+        return _decode(lib().gf2_mc_retry_decode, RETRY_RULE, (self.handle, retry.handle), (), (r1, keys1, flips1, r2, keys2, flips2),
+                       seed, first, count, p_x, p_y, p_z, int(max_attempts))
 
     def mc_circuit_decode_strata(self, circ, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x, k_y, k_z):
         """gf2_mc_circuit_decode_strata: mc_circuit_decode's tables; weights and counts per stratum.  Returns the (nstrata, 5) counts."""
-        k1, k2 = np.ascontiguousarray(keys1, dtype="<u8"), np.ascontiguousarray(keys2, dtype="<u8")
-        f1, f2 = np.ascontiguousarray(flips1, dtype=np.uint8), np.ascontiguousarray(flips2, dtype=np.uint8)
-        weights, counts, out = _strata_arrays(weights, counts)
-        check(lib().gf2_mc_circuit_decode_strata(self.handle, circ.handle, r1, _ptr(k1) if len(k1) else None, _ptr(f1) if len(k1) else None,
-                                                 len(k1), r2, _ptr(k2) if len(k2) else None, _ptr(f2) if len(k2) else None, len(k2),
-                                                 seed & 0xFFFFFFFFFFFFFFFF, first, len(weights), _ptr(weights), _ptr(counts),
-                                                 k_x, k_y, k_z, _ptr(out)))
-        return out
+        return _decode_strata(lib().gf2_mc_circuit_decode_strata, CIRCUIT_RULE, (self.handle, circ.handle), (),
+                              (r1, keys1, flips1, r2, keys2, flips2), seed, first, weights, counts, k_x, k_y, k_z)
 
     def mc_ec_decode_strata(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x, k_y, k_z):
         """gf2_mc_ec_decode_strata: mc_ec_decode's tables; weights and counts per stratum.  Returns the (nstrata, 8) counts."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        weights, counts, _ = _strata_arrays(weights, counts)
-        out = np.zeros((len(weights), EC_FIELDS_COUNT), dtype=np.uint64)
-        check(lib().gf2_mc_ec_decode_strata(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF,
-                                            first, len(weights), _ptr(weights), _ptr(counts), k_x, k_y, k_z, _ptr(out)))
-        return out
+        return _decode_strata(lib().gf2_mc_ec_decode_strata, EC_RULE, (self.handle, circ.handle), (rounds,),
+                              (r1, keys1, flips1, r2, keys2, flips2), seed, first, weights, counts, k_x, k_y, k_z)
 
     def mc_ft_decode_strata(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x,
                             k_y, k_z):
         """gf2_mc_ft_decode_strata: mc_ft_decode's tables; weights and counts per stratum.  Returns the (nstrata, 7) counts."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        weights, counts, _ = _strata_arrays(weights, counts)
-        out = np.zeros((len(weights), FT_FIELDS_COUNT), dtype=np.uint64)
-        check(lib().gf2_mc_ft_decode_strata(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1,
-                                            int(r2), *t2, seed & 0xFFFFFFFFFFFFFFFF, first, len(weights), _ptr(weights), _ptr(counts),
-                                            k_x, k_y, k_z, _ptr(out)))
-        return out
+        return _decode_strata(lib().gf2_mc_ft_decode_strata, FT_RULE, (self.handle, circ.handle), (nsteps, measure_mask),
+                              (r1, keys1, flips1, r2, keys2, flips2), seed, first, weights, counts, k_x, k_y, k_z)
 
     def circuit_enumerate(self, circ, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
         """gf2_circuit_enumerate: circuit_enumerate_host's counts from the device."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
-        out = np.zeros((side, side, 5), dtype=np.uint64)
-        check(lib().gf2_circuit_enumerate(self.handle, circ.handle, r1, *t1, r2, *t2, int(w), int(first_rank), int(count), _ptr(out)))
-        return out
+        return _enumerate(lib().gf2_circuit_enumerate, CIRCUIT_RULE, (self.handle, circ.handle), (),
+                          (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count)
 
     # -- syndromes ----------------------------------------------------------------------------------------
     def ec_enumerate(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
         """gf2_ec_enumerate: ec_enumerate_host's counts from the device."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
-        out = np.zeros((side, side, EC_FIELDS_COUNT), dtype=np.uint64)
-        check(lib().gf2_ec_enumerate(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, int(w), int(first_rank), int(count),
-                                     _ptr(out)))
-        return out
+        return _enumerate(lib().gf2_ec_enumerate, EC_RULE, (self.handle, circ.handle), (rounds,), (r1, keys1, flips1, r2, keys2, flips2),
+                          w, first_rank, count)
 
     def ft_enumerate(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count):
         """gf2_ft_enumerate: ft_enumerate_host's counts from the device."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        side = max(0, min(int(w), ENUMERATE_MAX_WEIGHT)) + 1
-        out = np.zeros((side, side, FT_FIELDS_COUNT), dtype=np.uint64)
-        check(lib().gf2_ft_enumerate(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2), *t2,
-                                     int(w), int(first_rank), int(count), _ptr(out)))
-        return out
+        return _enumerate(lib().gf2_ft_enumerate, FT_RULE, (self.handle, circ.handle), (nsteps, measure_mask),
+                          (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count)
 
     def ec_gate_enumerate(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count):
         """gf2_ec_gate_enumerate: ec_gate_enumerate_host's counts from the device."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        site_loc = _gate_sites(site_loc, n1, n2)
-        out = np.zeros((max(0, min(int(b), GATE_ENUMERATE_MAX_WEIGHT)) + 1, EC_FIELDS_COUNT), dtype=np.uint64)
-        check(lib().gf2_ec_gate_enumerate(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, _ptr(site_loc), int(n1), int(n2),
-                                          int(w), int(b), int(first_rank), int(count), _ptr(out)))
-        return out
+        return _gate_enumerate(lib().gf2_ec_gate_enumerate, EC_RULE, (self.handle, circ.handle), (rounds,),
+                               (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), w, b, first_rank, count)
 
     def ft_gate_enumerate(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count):
         """gf2_ft_gate_enumerate: ft_gate_enumerate_host's counts from the device."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        site_loc = _gate_sites(site_loc, n1, n2)
-        out = np.zeros((max(0, min(int(b), GATE_ENUMERATE_MAX_WEIGHT)) + 1, FT_FIELDS_COUNT), dtype=np.uint64)
-        check(lib().gf2_ft_gate_enumerate(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1, int(r2),
-                                          *t2, _ptr(site_loc), int(n1), int(n2), int(w), int(b), int(first_rank), int(count), _ptr(out)))
-        return out
+        return _gate_enumerate(lib().gf2_ft_gate_enumerate, FT_RULE, (self.handle, circ.handle), (nsteps, measure_mask),
+                               (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), w, b, first_rank, count)
 
     def mc_ec_decode_gate_strata(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, seed, first, strata, counts):
         """gf2_mc_ec_decode_gate_strata: mc_ec_decode's tables, gate_sites' site table; strata (nstrata, 2) rows (a, b) and counts per
         stratum.  Returns the (nstrata, 17, 8) counts [stratum][c][field]."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        site_loc = _gate_sites(site_loc, n1, n2)
-        wa, wb, counts, out = _gate_strata_arrays(strata, counts, EC_FIELDS_COUNT)
-        check(lib().gf2_mc_ec_decode_gate_strata(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, _ptr(site_loc), int(n1),
-                                                 int(n2), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), len(counts), _ptr(wa), _ptr(wb),
-                                                 _ptr(counts), _ptr(out)))
-        return out
+        return _decode_gate_strata(lib().gf2_mc_ec_decode_gate_strata, EC_RULE, (self.handle, circ.handle), (rounds,),
+                                   (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), seed, first, strata, counts)
 
     def mc_ft_decode_gate_strata(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, seed, first,
                                  strata, counts):
         """gf2_mc_ft_decode_gate_strata: mc_ft_decode's tables, likewise.  Returns the (nstrata, 17, 7) counts."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        site_loc = _gate_sites(site_loc, n1, n2)
-        wa, wb, counts, out = _gate_strata_arrays(strata, counts, FT_FIELDS_COUNT)
-        check(lib().gf2_mc_ft_decode_gate_strata(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1,
-                                                 int(r2), *t2, _ptr(site_loc), int(n1), int(n2), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first),
-                                                 len(counts), _ptr(wa), _ptr(wb), _ptr(counts), _ptr(out)))
-        return out
+        return _decode_gate_strata(lib().gf2_mc_ft_decode_gate_strata, FT_RULE, (self.handle, circ.handle), (nsteps, measure_mask),
+                                   (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), seed, first, strata, counts)
 
     def mc_ec_decode_gate(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, seed, first, count, p1, p2):
         """gf2_mc_ec_decode_gate: mc_ec_decode's eight counts over samples [first, first + count) when every gate fails on its own,
         a one-operand site of gate_sites' table with probability p1, a CNOT site with p2."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        site_loc = _gate_sites(site_loc, n1, n2)
-        counts = np.zeros(EC_FIELDS_COUNT, dtype=np.uint64)
-        check(lib().gf2_mc_ec_decode_gate(self.handle, circ.handle, int(rounds), int(r1), *t1, int(r2), *t2, _ptr(site_loc), int(n1), int(n2),
-                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), int(count), float(p1), float(p2), _ptr(counts)))
-        return counts
+        return _decode_gate(lib().gf2_mc_ec_decode_gate, EC_RULE, (self.handle, circ.handle), (rounds,),
+                            (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), seed, first, count, p1, p2)
 
     def mc_ft_decode_gate(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, seed, first, count,
                           p1, p2):
         """gf2_mc_ft_decode_gate: mc_ft_decode's seven counts, likewise."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        site_loc = _gate_sites(site_loc, n1, n2)
-        counts = np.zeros(FT_FIELDS_COUNT, dtype=np.uint64)
-        check(lib().gf2_mc_ft_decode_gate(self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF, int(r1), *t1,
-                                          int(r2), *t2, _ptr(site_loc), int(n1), int(n2), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first),
-                                          int(count), float(p1), float(p2), _ptr(counts)))
-        return counts
+        return _decode_gate(lib().gf2_mc_ft_decode_gate, FT_RULE, (self.handle, circ.handle), (nsteps, measure_mask),
+                            (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), seed, first, count, p1, p2)
 
     def ec_enumerate_list(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):
         """gf2_ec_enumerate_list: ec_enumerate_list_host's (found, records) from the device, byte for byte."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        return _fault_list_call(lib().gf2_ec_enumerate_list, (self.handle, circ.handle, int(rounds), int(r1)) + t1 + (int(r2),) + t2 +
-                                (int(w), int(first_rank), int(count)), select, capacity, FAULT_LIST_MAX_CAPACITY)
+        return _enumerate_list(lib().gf2_ec_enumerate_list, EC_RULE, (self.handle, circ.handle), (rounds,),
+                               (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count, select, capacity, FAULT_LIST_MAX_CAPACITY)
 
     def ft_enumerate_list(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, w, first_rank, count, select, capacity):
         """gf2_ft_enumerate_list: ft_enumerate_list_host's (found, records) from the device, byte for byte."""
-        keep, (t1, t2) = _enumerate_tables(keys1, flips1, keys2, flips2)
-        return _fault_list_call(lib().gf2_ft_enumerate_list, (self.handle, circ.handle, int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF,
-                                                              int(r1)) + t1 + (int(r2),) + t2 + (int(w), int(first_rank), int(count)),
-                                select, capacity, FAULT_LIST_MAX_CAPACITY)
+        return _enumerate_list(lib().gf2_ft_enumerate_list, FT_RULE, (self.handle, circ.handle), (nsteps, measure_mask),
+                               (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count, select, capacity, FAULT_LIST_MAX_CAPACITY)
 
     def check_create(self, packed, r, n):
         return Check(self, packed, r, n)

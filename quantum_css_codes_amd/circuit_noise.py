@@ -81,8 +81,8 @@ def code_tables(code):
 
 
 def gadget_enumerate_request(total, weights, first_rank, count, max_configurations, what):
-    """The argument rules of FaultCircuit.enumerate_strata for the gadgets' exact strata (ECCircuit / FTProgram.enumerate_strata):
-    (weights, firsts, counts) as lists of ints, ValueError for a weight, a range or a size that is refused."""
+    """The argument rules of the exact strata over `total` locations (FaultCircuit.enumerate_strata and ec_noise.Gadget's, `what`
+    naming the circuit or gadget): (weights, firsts, counts) as lists of ints, ValueError for a weight, a range or a size that is refused."""
     weights = [int(w) for w in np.asarray(weights).reshape(-1)]
     limit = min(total, _native.ENUMERATE_MAX_WEIGHT)
     if any(w < 0 or w > limit for w in weights):
@@ -192,13 +192,7 @@ class FaultCircuit(object):
     def outcomes(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
         """The outcome words of samples [first_sample, first_sample + num_samples): a (num_samples, ldr) uint64 array."""
         ctx = _native.default_context()
-        circ = self.device()
-        count = int(num_samples)
-        buf = ctx.alloc(max(1, count) * self.ldr * 8)
-        ctx.circuit_outcomes_dev(circ, int(seed), int(first_sample), count, float(p_x), float(p_y), float(p_z), buf, self.ldr)
-        out = buf.download((count, self.ldr), np.uint64)
-        buf.free()
-        return out
+        return ctx.outcomes(ctx.circuit_outcomes_dev, self.device(), seed, first_sample, num_samples, p_x, p_y, p_z, self.ldr)
 
     def _need_code(self):
         if self.code is None:
@@ -260,24 +254,8 @@ class FaultCircuit(object):
         code = self._need_code()
         if code.n > 128:
             raise ValueError("the table decode of a circuit's final frame needs n <= 128 (where the syndrome tables exist)")
-        weights = [int(w) for w in np.asarray(weights).reshape(-1)]
         total = self.num_locations
-        limit = min(total, _native.ENUMERATE_MAX_WEIGHT)
-        if any(w < 0 or w > limit for w in weights):
-            raise ValueError("an enumerated stratum's weight lies in [0, min(L = %d, %d)]" % (total, _native.ENUMERATE_MAX_WEIGHT))
-        if not 1 <= total <= MAX_LOCATIONS:
-            raise ValueError("the enumeration needs 1 <= L <= %d (2^20) fault locations, the circuit has %d" % (MAX_LOCATIONS, total))
-        subsets = [math.comb(total, w) for w in weights]
-        firsts = [0] * len(weights) if first_rank is None else [int(v) for v in np.broadcast_to(np.asarray(first_rank, dtype=object), (len(weights),))]
-        counts = ([c - f for c, f in zip(subsets, firsts)] if count is None
-                  else [int(v) for v in np.broadcast_to(np.asarray(count, dtype=object), (len(weights),))])
-        for w, c, f, n in zip(weights, subsets, firsts, counts):
-            if f < 0 or n < 0 or f + n > c:
-                raise ValueError("ranks [%d, %d + %d) leave the range [0, C(%d, %d) = %d)" % (f, f, n, total, w, c))
-        size = sum(n * 3**w for w, n in zip(weights, counts))
-        budget = ENUMERATE_BUDGET if max_configurations is None else int(max_configurations)
-        if size > budget:
-            raise ValueError("%d fault configurations to enumerate, more than max_configurations = %d" % (size, budget))
+        weights, firsts, counts = gadget_enumerate_request(total, weights, first_rank, count, max_configurations, "circuit")
         keys1, flips1, keys2, flips2 = self._tables()
         if host:
             run = lambda w, f, n: _native.circuit_enumerate_host(self.effects, code.r_1, keys1, flips1, code.r_2, keys2, flips2, w, f, n)

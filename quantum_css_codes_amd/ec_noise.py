@@ -211,18 +211,22 @@ def error_correct_gates(code, rounds=1, idle_data=False):
     return ECGates(gates, 3 * build.n, rounds, ldr, rows_x, rows_z, row_time, row_kind, row_round, flag_rows, build.spans)
 
 
-class ECCircuit(object):
-    """The error-correction cycle of a code prepared for the Monte-Carlo: the gadget (error_correct_gates), its effect table
-    (gf2_circuit_effects_timed, host code) and, on first use, the device copy."""
+PAULI_OF_MASK = ('I', 'X', 'Z', 'Y')                # the two bits of a kind mask: 1 = X, 2 = Z, 3 = Y
 
-    def __init__(self, code, rounds=1, idle_data=False):
-        self.code = code
-        self.rounds = int(rounds)
-        self.gadget = error_correct_gates(code, rounds, idle_data)
-        self.ldr = self.gadget.ldr
+
+class Gadget(object):
+    """A post-selected gadget prepared for the Monte-Carlo, what ECCircuit and ft_noise.FTProgram are: the gate list `gadget` (an
+    ECGates), its effect table (gf2_circuit_effects_timed, host code) and, on first use, the device copy, judged by one of _native's
+    tally rules.  A subclass states
+        rule, fields, class_names    the rule (_native.EC_RULE / FT_RULE), the names of its counts and of its class byte's bits
+        flip_mask, noun              the class bits that make an accepted fault one to list; the gadget's name in error messages
+        _create, _outcomes_dev       the Context methods that make the device copy and draw its outcome words
+    and _head(), the rule's own arguments.  {ec,ft} below stands for the rule's prefix in the names of entry points."""
+
+    def __init__(self, code, gadget):
+        self.code, self.gadget, self.ldr = code, gadget, gadget.ldr
         self.effects, self.locations = _native.circuit_effects_timed(
-            self.gadget.gates, self.gadget.qubits, _native.pack_rows(self.gadget.rows_x), _native.pack_rows(self.gadget.rows_z),
-            self.gadget.row_time, ldr=self.ldr)
+            gadget.gates, gadget.qubits, _native.pack_rows(gadget.rows_x), _native.pack_rows(gadget.rows_z), gadget.row_time, ldr=self.ldr)
         self._device = None
         self._sites = None
 
@@ -233,235 +237,226 @@ class ECCircuit(object):
     def device(self):
         if self._device is None:
             if not 1 <= self.num_locations <= circuit_noise.MAX_LOCATIONS:
-                raise ValueError("the Monte-Carlo needs 1 <= L <= %d (2^20) fault locations, the cycle has %d"
-                                 % (circuit_noise.MAX_LOCATIONS, self.num_locations))
-            self._device = _native.default_context().circuit_create(self.effects)
+                raise ValueError("the Monte-Carlo needs 1 <= L <= %d (2^20) fault locations, the %s has %d"
+                                 % (circuit_noise.MAX_LOCATIONS, self.noun, self.num_locations))
+            self._device = getattr(_native.default_context(), self._create)(self.effects)
         return self._device
 
     def _tables(self):
         keys1, flips1, keys2, flips2 = circuit_noise.code_tables(self.code)
         return self.code.r_1, keys1, flips1, self.code.r_2, keys2, flips2
 
+    def _entry(self, name, host=False):
+        """The rule's wrapper `name` (%s: the rule's prefix) with this gadget's leading arguments filled in: the default context's
+        method on the device copy or, host=True, _native's host statement `name`_host on the effect table (no GPU)."""
+        if host:
+            fn, table = getattr(_native, (name + "_host") % self.rule.name), self.effects
+        else:
+            fn, table = getattr(_native.default_context(), name % self.rule.name), self.device()
+        lead = (table,) + self._head() + self._tables()
+        return lambda *rest: fn(*lead, *rest)
+
+    def _tally(self, words, classes=False):
+        return getattr(_native, "%s_tally_host" % self.rule.name)(words, *self._head(), *self._tables(), classes=classes)
+
+    def _dict(self, counts, samples):
+        out = {name: int(v) for name, v in zip(self.fields, counts)}
+        out['samples'] = int(samples)
+        return out
+
     def outcomes(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
         """The outcome words of samples [first_sample, first_sample + num_samples), rejected ones included: a (num_samples, ldr)
-        uint64 array (gf2_circuit_outcomes_dev)."""
+        uint64 array (gf2_circuit_outcomes_dev; a program: gf2_ft_outcomes_dev)."""
         ctx = _native.default_context()
-        circ = self.device()
-        count = int(num_samples)
-        buf = ctx.alloc(max(1, count) * self.ldr * 8)
-        ctx.circuit_outcomes_dev(circ, int(seed), int(first_sample), count, float(p_x), float(p_y), float(p_z), buf, self.ldr)
-        out = buf.download((count, self.ldr), np.uint64)
-        buf.free()
-        return out
+        return ctx.outcomes(getattr(ctx, self._outcomes_dev), self.device(), seed, first_sample, num_samples, p_x, p_y, p_z, self.ldr)
 
-    def logical_error_rates(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
-        """The tally of samples [first_sample, first_sample + num_samples) on the device: a dict of EC_FIELDS plus 'samples'.
-        Every field after 'accepted' counts among accepted samples; the counts of sample ranges add."""
-        counts = _native.default_context().mc_ec_decode(self.device(), self.rounds, *self._tables(), int(seed), int(first_sample),
-                                                        int(num_samples), float(p_x), float(p_y), float(p_z))
-        out = {name: int(v) for name, v in zip(EC_FIELDS, counts)}
-        out['samples'] = int(num_samples)
-        return out
+    def _error_rates(self, num_samples, p_x, p_y, p_z, seed, first_sample):
+        counts = self._entry("mc_%s_decode")(int(seed), int(first_sample), int(num_samples), float(p_x), float(p_y), float(p_z))
+        return self._dict(counts, num_samples)
 
     def tally_host(self, words, classes=False):
-        """The tally rule over outcome words (samples, ldr) on the host (gf2_ec_tally_host, no GPU): the dict of EC_FIELDS plus
+        """The tally rule over outcome words (samples, ldr) on the host (gf2_{ec,ft}_tally_host, no GPU): the dict of `fields` plus
         'samples'; classes=True returns (dict, class byte per sample) instead."""
         words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, self.ldr)
-        got = _native.ec_tally_host(words, self.rounds, *self._tables(), classes=classes)
-        counts = got[0] if classes else got
-        out = {name: int(v) for name, v in zip(EC_FIELDS, counts)}
-        out['samples'] = len(words)
+        got = self._tally(words, classes)
+        out = self._dict(got[0] if classes else got, len(words))
         return (out, got[1]) if classes else out
 
     def enumerate_strata(self, weights, first_rank=None, count=None, max_configurations=None, host=False):
-        """Exact strata of the cycle (DESIGN.md "Exact strata of the cycle"): every configuration of exactly weights[s] <= 8 faults
-        -- each subset of the L locations with every assignment of X, Y, Z to its picks -- judged by logical_error_rates' tally
+        """Exact strata (DESIGN.md "Exact strata of the cycle", "Exact strata of the measurement"): every configuration of exactly
+        weights[s] <= 8 faults -- each subset of the L locations with every assignment of X, Y, Z to its picks -- judged by the tally
         rule, post-selection included, and counted per kind composition.  Arguments as FaultCircuit.enumerate_strata's: ranks
         [first_rank, first_rank + count) per weight (default: everything), more than `max_configurations` (default
         circuit_noise.ENUMERATE_BUDGET) configurations in all is a ValueError, host=True runs the serial host statement
-        (gf2_ec_enumerate_host) and needs no GPU.  Returns a montecarlo.PostSelectedStrata over nb = L."""
+        (gf2_{ec,ft}_enumerate_host) and needs no GPU.  Returns a montecarlo.PostSelectedStrata over nb = L."""
         from . import montecarlo
         weights, firsts, counts = circuit_noise.gadget_enumerate_request(self.num_locations, weights, first_rank, count, max_configurations,
-                                                                         "cycle")
-        if host:
-            run = lambda w, f, n: _native.ec_enumerate_host(self.effects, self.rounds, *self._tables(), w, f, n)
-        else:
-            ctx, circ = _native.default_context(), self.device()
-            run = lambda w, f, n: ctx.ec_enumerate(circ, self.rounds, *self._tables(), w, f, n)
+                                                                         self.noun)
+        run = self._entry("%s_enumerate", host)
         return montecarlo.PostSelectedStrata(self.num_locations, weights, [run(w, f, n) for w, f, n in zip(weights, firsts, counts)],
-                                             EC_FIELDS)
+                                             self.fields)
 
-    def malignant_faults(self, weight, select=CLASS_FLIP_X | CLASS_FLIP_Z, first_rank=None, count=None, max_configurations=None, host=False):
-        """The malignant fault sets of the cycle (DESIGN.md "Malignant fault sets of the cycle"): enumerate_strata's walk of the
-        configurations of exactly `weight` <= 8 faults over ranks [first_rank, first_rank + count) (default: everything), but the
-        accepted ones whose class byte has a bit of `select` (CLASS_* bits; CLASS_ACCEPTED lists every accepted one) are listed,
-        not counted (gf2_ec_enumerate_list; host=True: gf2_ec_enumerate_list_host, no GPU).  Budget as enumerate_strata's; more
-        than 2^26 records is a ValueError.  Returns a montecarlo.FaultList over nb = L, which describe() puts into words."""
+    def malignant_faults(self, weight, select=None, first_rank=None, count=None, max_configurations=None, host=False):
+        """The malignant fault sets (DESIGN.md "Malignant fault sets of the cycle", "... of the measurement"): enumerate_strata's walk
+        of the configurations of exactly `weight` <= 8 faults over ranks [first_rank, first_rank + count) (default: everything), but
+        the accepted ones whose class byte has a bit of `select` (CLASS_* bits, default `flip_mask`: CLASS_FLIP_X | CLASS_FLIP_Z for a
+        cycle, CLASS_WRONG for a program; CLASS_ACCEPTED lists every accepted one) are listed, not counted (gf2_{ec,ft}_enumerate_list;
+        host=True: gf2_{ec,ft}_enumerate_list_host, no GPU).  Budget as enumerate_strata's; more than 2^26 records is a ValueError.
+        Returns a montecarlo.FaultList over nb = L, which describe() puts into words."""
         from . import montecarlo
-        if host:
-            run = lambda w, f, n, select, capacity: _native.ec_enumerate_list_host(self.effects, self.rounds, *self._tables(), w, f, n, select, capacity)
-        else:
-            ctx, circ = _native.default_context(), self.device()
-            run = lambda w, f, n, select, capacity: ctx.ec_enumerate_list(circ, self.rounds, *self._tables(), w, f, n, select, capacity)
-        return montecarlo.malignant_faults(self.num_locations, weight, CLASS_NAMES, select, first_rank, count, max_configurations, "cycle", run)
+        return montecarlo.malignant_faults(self.num_locations, weight, self.class_names, self.flip_mask if select is None else select,
+                                           first_rank, count, max_configurations, self.noun, self._entry("%s_enumerate_list", host))
+
+    def _fault(self, location, kind):
+        g, q = (int(v) for v in self.locations[location])
+        return g, tuple(int(v) for v in self.gadget.gates[g]), q, KINDS[kind]
 
     def describe(self, fault_list):
-        """Every record of a FaultList of this cycle as a tuple over its picks of (gate index, gate (kind, a, b), qubit, 'X' / 'Y' /
+        """Every record of a FaultList of this gadget as a tuple over its picks of (gate index, gate (kind, a, b), qubit, 'X' / 'Y' /
         'Z'): single_faults' format, so the weight-1 list of the default select reads as single_faults()[1]."""
-        return describe_faults(self, fault_list)
+        if fault_list.nb != self.num_locations:
+            raise ValueError("the list is over %d locations, the gadget has %d" % (fault_list.nb, self.num_locations))
+        return [tuple(self._fault(l, k) for l, k in zip(picks, kinds))
+                for picks, kinds in zip(fault_list.locations().tolist(), fault_list.kinds().tolist())]
 
     def strata(self, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0, host=False):
-        """Sampled strata of the cycle (DESIGN.md "Sampled strata of the cycle"): stratum s draws samples [first_sample, first_sample +
-        samples[s]) of exactly weights[s] <= 16 faults among the L locations, kinds X : Y : Z = kinds, and judges them by
-        logical_error_rates' tally rule, post-selection included (gf2_mc_ec_decode_strata).  `samples` and `first_sample` are one
-        number for all strata or one per stratum.  host=True draws the outcome words with gf2_stratum_outcomes_host and tallies them
-        with gf2_ec_tally_host: no GPU.  Returns a montecarlo.SampledPostSelectedStrata over nb = L."""
+        """Sampled strata (DESIGN.md "Sampled strata of the cycle", "Sampled strata of the measurement"): stratum s draws samples
+        [first_sample, first_sample + samples[s]) of exactly weights[s] <= 16 faults among the L locations, kinds X : Y : Z = kinds,
+        and judges them by the tally rule, post-selection included (gf2_mc_{ec,ft}_decode_strata).  `samples` and `first_sample` are
+        one number for all strata or one per stratum.  host=True draws the outcome words with gf2_stratum_outcomes_host and tallies
+        them with gf2_{ec,ft}_tally_host: no GPU.  Returns a montecarlo.SampledPostSelectedStrata over nb = L."""
         from . import montecarlo
-        tables = self._tables()
         if host:
-            run = montecarlo.host_strata_run(self.effects, lambda words: _native.ec_tally_host(words, self.rounds, *tables), len(EC_FIELDS), seed)
+            run = montecarlo.host_strata_run(self.effects, self._tally, len(self.fields), seed)
         else:
-            ctx, circ = _native.default_context(), self.device()
-            run = lambda first, ws, ns, ks: ctx.mc_ec_decode_strata(circ, self.rounds, *tables, int(seed), int(first), ws, ns, *ks)
-        return montecarlo.gadget_strata_local(self.num_locations, EC_FIELDS, weights, samples, kinds, first_sample, run)
+            decode = self._entry("mc_%s_decode_strata")
+            run = lambda first, ws, ns, ks: decode(int(seed), int(first), ws, ns, *ks)
+        return montecarlo.gadget_strata_local(self.num_locations, self.fields, weights, samples, kinds, first_sample, run)
 
     def gate_sites(self):
-        """(site_loc, n1, n2, site_gate) of the cycle's gates (circuit_noise.gate_sites), made once."""
+        """(site_loc, n1, n2, site_gate) of the gadget's gates (circuit_noise.gate_sites), made once."""
         if self._sites is None:
             self._sites = circuit_noise.gate_sites(self.gadget.gates, self.locations)
         return self._sites
 
     def enumerate_gate_range(self, w, b, first_rank, count, host=False):
-        """One call of the gate-fault enumeration: the (b + 1, 8) uint64 counts [c][field] over the site
+        """One call of the gate-fault enumeration: the (b + 1, F) uint64 counts [c][field] over the site
         subsets of ranks [first_rank, first_rank + count) of weight w with b CNOT picks, c the number of two-operand kinds
-        (gf2_ec_gate_enumerate; host=True: gf2_ec_gate_enumerate_host, no GPU).  Counts of disjoint ranges add."""
+        (gf2_{ec,ft}_gate_enumerate; host=True: gf2_{ec,ft}_gate_enumerate_host, no GPU).  Counts of disjoint ranges add."""
         sites = self.gate_sites()[:3]
-        if host:
-            return _native.ec_gate_enumerate_host(self.effects, self.rounds, *self._tables(), *sites, w, b, first_rank, count)
-        return _native.default_context().ec_gate_enumerate(self.device(), self.rounds, *self._tables(), *sites, w, b, first_rank, count)
+        return self._entry("%s_gate_enumerate", host)(*sites, w, b, first_rank, count)
 
     def enumerate_gate_strata(self, weights, max_configurations=None, host=False):
-        """Exact strata of the cycle under gate-level faults: every configuration of exactly weights[s] <= 4
-        faulty gates -- a one-operand gate with X, Y or Z, a CNOT with one of the 15 two-qubit Paulis -- judged by
-        logical_error_rates' tally rule, post-selection included, whole strata, every CNOT count b.  More than `max_configurations`
-        (default circuit_noise.ENUMERATE_BUDGET) configurations in all is a ValueError.  Returns a montecarlo.GateStrata."""
-        return gate_strata(self, EC_FIELDS, weights, max_configurations, host, "cycle")
+        """Exact strata under gate-level faults: every configuration of exactly weights[s] <= 4 faulty gates
+        -- a one-operand gate with X, Y or Z, a CNOT with one of the 15 two-qubit Paulis -- judged by the tally rule, post-selection
+        included, whole strata, every CNOT count b, through enumerate_gate_range.  More than `max_configurations` (default
+        circuit_noise.ENUMERATE_BUDGET) configurations in all is a ValueError.  Returns a montecarlo.GateStrata, the counts of a
+        weight stacked into (w + 1, w + 1, F) [b][c]."""
+        from . import montecarlo
+        _, n1, n2, _ = self.gate_sites()
+        weights = circuit_noise.gate_enumerate_request(n1, n2, weights, max_configurations, self.noun)
+        if not host:
+            self.device()
+        counts = []
+        for w in weights:
+            stack = np.zeros((w + 1, w + 1, len(self.fields)), dtype=np.uint64)
+            for b in range(w + 1):
+                stack[b, :b + 1] = self.enumerate_gate_range(w, b, 0, math.comb(n1, w - b) * math.comb(n2, b), host=host)
+            counts.append(stack)
+        return montecarlo.GateStrata(n1, n2, weights, counts, self.fields)
 
     def gate_strata(self, strata, samples, seed=0, first_sample=0, host=False):
-        """Sampled strata of the cycle under gate-level faults (DESIGN.md section 5e "Sampled strata under gate-level faults"):
-        stratum s = (a, b) draws samples [first_sample, first_sample + samples[s]) of exactly a faulty one-operand gates and b faulty
-        CNOTs, a + b <= 16, kinds uniform over the 3 and the 15, and judges them by logical_error_rates' tally rule, post-selection
-        included, tallied by the number c of two-operand kinds (gf2_mc_ec_decode_gate_strata).  `samples` and `first_sample` are one
-        number for all strata or one per stratum.  host=True draws with gf2_gate_stratum_outcomes_host and tallies with
-        gf2_ec_tally_host: no GPU.  Returns a montecarlo.SampledGateStrata."""
+        """Sampled strata under gate-level faults (DESIGN.md section 5e "Sampled strata under gate-level faults"): stratum s = (a, b)
+        draws samples [first_sample, first_sample + samples[s]) of exactly a faulty one-operand gates and b faulty CNOTs, a + b <= 16,
+        kinds uniform over the 3 and the 15, and judges them by the tally rule, post-selection included, tallied by the number c of
+        two-operand kinds (gf2_mc_{ec,ft}_decode_gate_strata).  `samples` and `first_sample` are one number for all strata or one per
+        stratum.  host=True draws with gf2_gate_stratum_outcomes_host and tallies with gf2_{ec,ft}_tally_host: no GPU.  Returns a
+        montecarlo.SampledGateStrata."""
         from . import montecarlo
-        tables, sites = self._tables(), self.gate_sites()[:3]
+        sites = self.gate_sites()[:3]
         if host:
-            run = montecarlo.host_gate_strata_run(self.effects, sites, lambda words: _native.ec_tally_host(words, self.rounds, *tables),
-                                                  len(EC_FIELDS), seed)
+            run = montecarlo.host_gate_strata_run(self.effects, sites, self._tally, len(self.fields), seed)
         else:
-            ctx, circ = _native.default_context(), self.device()
-            run = lambda first, strata, ns: ctx.mc_ec_decode_gate_strata(circ, self.rounds, *tables, *sites, int(seed), int(first), strata, ns)
-        return montecarlo.gate_strata_local(sites[1], sites[2], EC_FIELDS, strata, samples, first_sample, run)
+            decode = self._entry("mc_%s_decode_gate_strata")
+            run = lambda first, strata, ns: decode(*sites, int(seed), int(first), strata, ns)
+        return montecarlo.gate_strata_local(sites[1], sites[2], self.fields, strata, samples, first_sample, run)
 
     def gate_error_rates(self, num_samples, p1, p2, seed=0, first_sample=0, host=False):
-        """The direct Monte-Carlo of the cycle under gate-level faults (DESIGN.md section 5e "Direct Monte-Carlo under gate-level
-        faults"): in samples [first_sample, first_sample + num_samples) every one-operand gate fails with probability p1 and one of
-        its 3 kinds, every CNOT as one event with probability p2 and one of its 15, and logical_error_rates' tally rule judges them,
-        post-selection included (gf2_mc_ec_decode_gate).  host=True draws with gf2_gate_outcomes_host and tallies with
-        gf2_ec_tally_host: no GPU.  Returns a dict of EC_FIELDS plus 'samples'; the counts of sample ranges add."""
-        tables, sites = self._tables(), self.gate_sites()[:3]
+        """The direct Monte-Carlo under gate-level faults (DESIGN.md section 5e "Direct Monte-Carlo under gate-level faults"): in
+        samples [first_sample, first_sample + num_samples) every one-operand gate fails with probability p1 and one of its 3 kinds,
+        every CNOT as one event with probability p2 and one of its 15, and the tally rule judges them, post-selection included
+        (gf2_mc_{ec,ft}_decode_gate).  host=True draws with gf2_gate_outcomes_host and tallies with gf2_{ec,ft}_tally_host: no GPU.
+        Returns a dict of `fields` plus 'samples'; the counts of sample ranges add."""
+        sites = self.gate_sites()[:3]
         if host:
             from . import montecarlo
-            counts = montecarlo.host_gate_counts(self.effects, sites, lambda words: _native.ec_tally_host(words, self.rounds, *tables),
-                                                 len(EC_FIELDS), num_samples, p1, p2, seed, first_sample)
+            counts = montecarlo.host_gate_counts(self.effects, sites, self._tally, len(self.fields), num_samples, p1, p2, seed, first_sample)
         else:
-            counts = _native.default_context().mc_ec_decode_gate(self.device(), self.rounds, *tables, *sites, int(seed), int(first_sample),
-                                                                 int(num_samples), float(p1), float(p2))
-        out = {name: int(v) for name, v in zip(EC_FIELDS, counts)}
-        out['samples'] = int(num_samples)
-        return out
+            counts = self._entry("mc_%s_decode_gate")(*sites, int(seed), int(first_sample), int(num_samples), float(p1), float(p2))
+        return self._dict(counts, num_samples)
+
+    def _listed(self, classes):
+        """The (row, column) pairs of a census' class bytes that are accepted and have a bit of flip_mask."""
+        return zip(*np.nonzero((classes & CLASS_ACCEPTED != 0) & (classes & self.flip_mask != 0)))
 
     def gate_single_faults(self):
-        """The census of every single gate fault, no GPU: (classes, flipping) -- classes (G, 15) uint8, the class byte (CLASS_* bits)
+        """The census of every single gate fault, no GPU: (classes, listed) -- classes (G, 15) uint8, the class byte (CLASS_* bits)
         of kind mask kappa (column kappa - 1; a one-operand gate uses columns 0 .. 2, the others stay 0) at every gate of the list;
-        flipping, the accepted faults with a logical flip as (gate index, gate (kind, a, b), Paulis) with Paulis one letter for a
-        one-operand gate and control then target, e.g. 'XI' or 'ZY', for a CNOT."""
-        return gate_single_faults(self, CLASS_FLIP_X | CLASS_FLIP_Z)
+        listed, the accepted faults with a bit of flip_mask (a logical flip of the cycle, a wrong measured bit of the program) as
+        (gate index, gate (kind, a, b), Paulis) with Paulis one letter for a one-operand gate and control then target, e.g. 'XI' or
+        'ZY', for a CNOT."""
+        site_loc, n1, n2, site_gate = self.gate_sites()
+        eff = self.effects
+        gates = self.gadget.gates
+        classes = np.zeros((len(gates), 15), dtype=np.uint8)
+        for sites, nbits in ((slice(0, n1), 2), (slice(n1, n1 + n2), 4)):
+            locs = site_loc[sites].astype(np.int64)
+            if not len(locs):
+                continue
+            words = np.zeros((len(locs), (1 << nbits) - 1, self.ldr), dtype=np.uint64)
+            for kappa in range(1, 1 << nbits):
+                for bit in range(nbits):
+                    if (kappa >> bit) & 1:
+                        words[:, kappa - 1] ^= eff[locs + (bit >> 1), bit & 1]
+            _, cls = self.tally_host(words.reshape(-1, self.ldr), classes=True)
+            classes[site_gate[sites], :(1 << nbits) - 1] = cls.reshape(len(locs), -1)
+        listed = []
+        for g, k in self._listed(classes):
+            kappa = int(k) + 1
+            gate = tuple(int(v) for v in gates[g])
+            paulis = PAULI_OF_MASK[kappa & 3] + (PAULI_OF_MASK[kappa >> 2] if gate[0] == GATE_CNOT else '')
+            listed.append((int(g), gate, paulis))
+        return classes, listed
 
     def single_faults(self):
-        """The census of all 3 L single faults, no GPU: (classes, flipping) -- classes (L, 3) uint8, the class byte (CLASS_* bits)
-        of an X, Y, Z fault (the columns, KINDS) at every location; flipping, the accepted faults with a logical flip as
+        """The census of all 3 L single faults, no GPU: (classes, listed) -- classes (L, 3) uint8, the class byte (CLASS_* bits)
+        of an X, Y, Z fault (the columns, KINDS) at every location; listed, the accepted faults with a bit of flip_mask as
         (gate index, gate (kind, a, b), qubit, 'X' / 'Y' / 'Z')."""
         eff = self.effects
         words = np.stack((eff[:, 0], eff[:, 0] ^ eff[:, 1], eff[:, 1]), axis=1)              # X, Y, Z
         _, classes = self.tally_host(words.reshape(-1, self.ldr), classes=True)
         classes = classes.reshape(-1, 3)
-        flipping = []
-        for l, k in zip(*np.nonzero((classes & CLASS_ACCEPTED != 0) & (classes & (CLASS_FLIP_X | CLASS_FLIP_Z) != 0))):
-            g, q = (int(v) for v in self.locations[l])
-            flipping.append((g, tuple(int(v) for v in self.gadget.gates[g]), q, KINDS[k]))
-        return classes, flipping
+        return classes, [self._fault(l, k) for l, k in self._listed(classes)]
 
 
-def describe_faults(gadget, fault_list):
-    """ECCircuit.describe and FTProgram.describe: `gadget` has num_locations, locations (location -> gate, qubit) and gadget.gates."""
-    if fault_list.nb != gadget.num_locations:
-        raise ValueError("the list is over %d locations, the gadget has %d" % (fault_list.nb, gadget.num_locations))
-    out = []
-    for picks, kinds in zip(fault_list.locations().tolist(), fault_list.kinds().tolist()):
-        row = []
-        for l, k in zip(picks, kinds):
-            g, q = (int(v) for v in gadget.locations[l])
-            row.append((g, tuple(int(v) for v in gadget.gadget.gates[g]), q, KINDS[k]))
-        out.append(tuple(row))
-    return out
+class ECCircuit(Gadget):
+    """The error-correction cycle of a code prepared for the Monte-Carlo: the gadget (error_correct_gates), its effect table
+    (gf2_circuit_effects_timed, host code) and, on first use, the device copy.  The methods are Gadget's, with the cycle's tally
+    rule (gf2_ec_tally_host, gf2_mc_ec_decode, ...), EC_FIELDS and this module's CLASS_* bits."""
+    rule, fields, class_names, flip_mask, noun = _native.EC_RULE, EC_FIELDS, CLASS_NAMES, CLASS_FLIP_X | CLASS_FLIP_Z, "cycle"
+    _create, _outcomes_dev = "circuit_create", "circuit_outcomes_dev"
 
+    def __init__(self, code, rounds=1, idle_data=False):
+        self.rounds = int(rounds)
+        Gadget.__init__(self, code, error_correct_gates(code, rounds, idle_data))
 
-def gate_strata(gadget, fields, weights, max_configurations, host, what):
-    """ECCircuit / FTProgram.enumerate_gate_strata: whole strata through gadget.enumerate_gate_range, stacked per weight into
-    (w + 1, w + 1, F) counts [b][c]."""
-    from . import montecarlo
-    _, n1, n2, _ = gadget.gate_sites()
-    weights = circuit_noise.gate_enumerate_request(n1, n2, weights, max_configurations, what)
-    if not host:
-        gadget.device()
-    counts = []
-    for w in weights:
-        stack = np.zeros((w + 1, w + 1, len(fields)), dtype=np.uint64)
-        for b in range(w + 1):
-            stack[b, :b + 1] = gadget.enumerate_gate_range(w, b, 0, math.comb(n1, w - b) * math.comb(n2, b), host=host)
-        counts.append(stack)
-    return montecarlo.GateStrata(n1, n2, weights, counts, fields)
+    def _head(self):
+        return (self.rounds,)
 
-
-PAULI_OF_MASK = ('I', 'X', 'Z', 'Y')                # the two bits of a kind mask: 1 = X, 2 = Z, 3 = Y
-
-
-def gate_single_faults(gadget, flip_mask):
-    """ECCircuit / FTProgram.gate_single_faults: `flip_mask` the class bits that make an accepted fault one to list."""
-    site_loc, n1, n2, site_gate = gadget.gate_sites()
-    eff = gadget.effects
-    gates = gadget.gadget.gates
-    classes = np.zeros((len(gates), 15), dtype=np.uint8)
-    for sites, nbits in ((slice(0, n1), 2), (slice(n1, n1 + n2), 4)):
-        locs = site_loc[sites].astype(np.int64)
-        if not len(locs):
-            continue
-        words = np.zeros((len(locs), (1 << nbits) - 1, gadget.ldr), dtype=np.uint64)
-        for kappa in range(1, 1 << nbits):
-            for bit in range(nbits):
-                if (kappa >> bit) & 1:
-                    words[:, kappa - 1] ^= eff[locs + (bit >> 1), bit & 1]
-        _, cls = gadget.tally_host(words.reshape(-1, gadget.ldr), classes=True)
-        classes[site_gate[sites], :(1 << nbits) - 1] = cls.reshape(len(locs), -1)
-    flipping = []
-    for g, k in zip(*np.nonzero((classes & CLASS_ACCEPTED != 0) & (classes & flip_mask != 0))):
-        kappa = int(k) + 1
-        gate = tuple(int(v) for v in gates[g])
-        paulis = PAULI_OF_MASK[kappa & 3] + (PAULI_OF_MASK[kappa >> 2] if gate[0] == GATE_CNOT else '')
-        flipping.append((int(g), gate, paulis))
-    return classes, flipping
+    def logical_error_rates(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """The tally of samples [first_sample, first_sample + num_samples) on the device (gf2_mc_ec_decode): a dict of EC_FIELDS plus
+        'samples'.  Every field after 'accepted' counts among accepted samples; the counts of sample ranges add."""
+        return self._error_rates(num_samples, p_x, p_y, p_z, seed, first_sample)
 
 
 def circuit_for(code, rounds=1, idle_data=False):

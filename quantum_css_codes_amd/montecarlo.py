@@ -28,6 +28,14 @@ def shard_range(first, count, rank, world):
     return start, mine
 
 
+def _rank_world(group=None):
+    """(rank, world size) of this process in the torch.distributed group; (0, 1) when no process group is initialised."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(group), dist.get_world_size(group)
+    return 0, 1
+
+
 def pick_mode(r_1, r_2, mode=None):
     if mode is None:
         mode = 'full' if (r_1 <= 24 and r_2 <= 24) else 'weight'
@@ -102,11 +110,7 @@ def run_sharded(code, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, mode=N
     """This rank's shard of the global range, then the histogram all-reduce (over `comm` when given, see
     all_reduce_histograms).  `local_fn` (same signature as run_local) replaces the GPU computation; the CPU tests of the
     sharding use it."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-    else:
-        rank, world = 0, 1
+    rank, world = _rank_world(group)
     start, mine = shard_range(first_sample, num_samples, rank, world)
     fn = local_fn or run_local
     part = fn(code, mine, p_x, p_y, p_z, seed=seed, first_sample=start, mode=mode)
@@ -194,11 +198,7 @@ def decode_local(code, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, hashe
 
 def decode_sharded(code, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, group=None, local_fn=None):
     """This rank's shard of the global range, then one all-reduce of the five counts."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-    else:
-        rank, world = 0, 1
+    rank, world = _rank_world(group)
     start, mine = shard_range(first_sample, num_samples, rank, world)
     part = (local_fn or decode_local)(code, mine, p_x, p_y, p_z, seed=seed, first_sample=start)
     total, = all_reduce_histograms([np.array([part[f] for f in DECODE_FIELDS], dtype=np.uint64)], group=group)
@@ -324,11 +324,7 @@ def strata_local(code, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0
 def strata_sharded(code, weights, samples, kinds=(1, 1, 1), seed=0, first_sample=0, group=None, local_fn=None):
     """Every stratum's sample range cut into this rank's shard (shard_range), then one all-reduce of the nstrata x 5 counts.
     `local_fn` (strata_local's signature; FaultCircuit.strata_local for a circuit) replaces the computation."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-    else:
-        rank, world = 0, 1
+    rank, world = _rank_world(group)
     weights, samples, firsts, kinds = _strata_request(weights, samples, kinds, first_sample)
     shards = [shard_range(first, count, rank, world) for first, count in zip(firsts.tolist(), samples.tolist())]
     part = (local_fn or strata_local)(code, weights, [mine for _, mine in shards], kinds=kinds, seed=seed,
@@ -1076,11 +1072,7 @@ def gadget_strata_sharded(gadget, weights, samples, kinds=(1, 1, 1), seed=0, fir
     range is cut by shard_range, this rank runs its part, and one all-reduce sums the nstrata x F counts.  `local_fn(gadget, weights,
     samples, kinds=, seed=, first_sample=)` replaces gadget.strata (the CPU tests pass the host statement).  Returns a
     SampledPostSelectedStrata with the whole sample counts."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-    else:
-        rank, world = 0, 1
+    rank, world = _rank_world(group)
     weights, samples, firsts, kinds = _strata_request(weights, samples, kinds, first_sample)
     shards = [shard_range(first, count, rank, world) for first, count in zip(firsts.tolist(), samples.tolist())]
     fn = local_fn or (lambda g, ws, ns, kinds, seed, first_sample: g.strata(ws, ns, kinds=kinds, seed=seed, first_sample=first_sample))
@@ -1329,11 +1321,7 @@ def gate_strata_sharded(gadget, strata, samples, seed=0, first_sample=0, group=N
     every stratum's sample range is cut by shard_range, this rank runs its part, and one all-reduce sums the nstrata x 17 x F counts.
     `local_fn(gadget, strata, samples, seed=, first_sample=)` replaces gadget.gate_strata (the CPU tests pass the host statement).
     Returns a SampledGateStrata with the whole sample counts."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-    else:
-        rank, world = 0, 1
+    rank, world = _rank_world(group)
     _, n1, n2, _ = gadget.gate_sites()
     strata, samples, firsts = _gate_strata_request(n1, n2, strata, samples, first_sample)
     shards = [shard_range(first, count, rank, world) for first, count in zip(firsts.tolist(), samples.tolist())]
@@ -1364,11 +1352,7 @@ def gate_error_rates_sharded(gadget, num_samples, p1, p2, seed=0, first_sample=0
     group: the sample range is cut by shard_range, this rank runs its part, and one all-reduce sums the counts (counts of sample
     ranges add).  `local_fn(gadget, num_samples, p1, p2, seed=, first_sample=)` replaces gadget.gate_error_rates (the CPU tests pass
     the host statement).  Returns gate_error_rates' dict with the whole sample count."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-    else:
-        rank, world = 0, 1
+    rank, world = _rank_world(group)
     start, mine = shard_range(first_sample, num_samples, rank, world)
     fn = local_fn or (lambda g, n, p1, p2, seed, first_sample: g.gate_error_rates(n, p1, p2, seed=seed, first_sample=first_sample))
     part = fn(gadget, mine, p1, p2, seed=seed, first_sample=start)
@@ -1385,11 +1369,7 @@ def enumerate_sharded(circuit, weights, group=None, local_fn=None):
     count)` replaces circuit.enumerate_strata (the CPU tests pass the host statement).  Returns an ExactStrata -- or, for an
     ec_noise.ECCircuit or an ft_noise.FTProgram, whose parts are PostSelectedStrata, a PostSelectedStrata: the field count and the
     class of the result are those of the part."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        rank, world = dist.get_rank(group), dist.get_world_size(group)
-    else:
-        rank, world = 0, 1
+    rank, world = _rank_world(group)
     weights = [int(w) for w in np.asarray(weights).reshape(-1)]
     shards = [shard_range(0, math.comb(circuit.num_locations, w), rank, world) for w in weights]
     fn = local_fn or (lambda circ, ws, first_rank, count: circ.enumerate_strata(ws, first_rank=first_rank, count=count))

@@ -265,13 +265,7 @@ class StreamedGadget(object):
         """The stream-layout words of samples [first_sample, first_sample + num_samples), rejected ones included: a (num_samples,
         ldw) uint64 array (gf2_stream_outcomes_dev)."""
         ctx = _native.default_context()
-        stream = self.device()
-        count = int(num_samples)
-        buf = ctx.alloc(max(1, count) * self.ldw * 8)
-        ctx.stream_outcomes_dev(stream, int(seed), int(first_sample), count, float(p_x), float(p_y), float(p_z), buf, self.ldw)
-        out = buf.download((count, self.ldw), np.uint64)
-        buf.free()
-        return out
+        return ctx.outcomes(ctx.stream_outcomes_dev, self.device(), seed, first_sample, num_samples, p_x, p_y, p_z, self.ldw)
 
     def counts(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
         """The twelve STREAM_FIELDS counts of samples [first_sample, first_sample + num_samples) on the device (gf2_mc_stream_decode)."""
@@ -313,13 +307,8 @@ class StreamedGadget(object):
         zero unless the sample is exhausted] [attempts of the sample] (gf2_retry_outcomes_dev).  The rates are those of the
         post-selected routes at every p; the samples are different samples."""
         ctx = _native.default_context()
-        retry = self.retry_device()
-        count, ldo = int(num_samples), self.ldw + 1
-        buf = ctx.alloc(max(1, count) * ldo * 8)
-        ctx.retry_outcomes_dev(retry, int(seed), int(first_sample), count, float(p_x), float(p_y), float(p_z), int(max_attempts), buf, ldo)
-        out = buf.download((count, ldo), np.uint64)
-        buf.free()
-        return out
+        return ctx.outcomes(ctx.retry_outcomes_dev, self.retry_device(), seed, first_sample, num_samples, p_x, p_y, p_z, self.ldw + 1,
+                            int(max_attempts))
 
     def retry_counts(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, max_attempts=256):
         """The fourteen RETRY_FIELDS counts of samples [first_sample, first_sample + num_samples) on the device (gf2_mc_retry_decode):
