@@ -901,6 +901,54 @@ int gf2_mc_retry_decode(gf2_ctx* ctx, const gf2_retry* retry, int64_t r1, const 
                         int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed, int64_t first_sample,
                         int64_t count, double p_x, double p_y, double p_z, int64_t max_attempts, uint64_t* counts_out);
 
+/* ---- repeat-until-success under gate-level faults ------------------------------------------------------
+ * [build-defined, DESIGN.md section 5d "Repeat-until-success under gate-level faults"]  The retried walk above with the fault model
+ * of "direct Monte-Carlo ... under gate-level faults": every one-operand gate of a region fails with probability p_1 and one of 3
+ * kinds, every CNOT as one event with probability p_2 and one of 15.  Regions are cut at gate boundaries, so a region's locations are
+ * partitioned by its SITES: site_regions holds (n_1, n_2) per region of every type, in type_regions' order, with n_1 + 2 n_2 the
+ * region's locations; site_loc holds the type-local first location of every site, region by region, a region's n_1 one-operand sites
+ * before its n_2 CNOT sites, each class ascending; a CNOT's second location is site_loc + 1.  Besides the rules of
+ * gf2_retry_words_host, GF2_E_ARG naming the rule: a region whose n_1 + 2 n_2 is not its location count, sites that do not
+ * partition their region's locations or are not ascending within a class, more than GF2_RETRY_MAX_SIZES distinct segment sizes per
+ * class, p_1 or p_2 outside [0, 1].
+ *
+ * Sample i is a pure function of (seed, i, p_1, p_2, the sequence, its regions and sites, max_attempts).  ks, the region number g,
+ * kr = segment_draw(ks, 2^32 + g) and ka = mix64(kr + G (a + 1)) are those above.  Under ka the region's two classes are drawn as the
+ * direct gate sampler draws a sample's under ks: the one-operand sites (m = n_1, radix 3, T = quantise(p_1), slots
+ * GF2_GATE_MC_SLOT_ONE + s), then the CNOT sites (m = n_2, radix 15, T = quantise(p_2), slots GF2_GATE_MC_SLOT_CNOT + s), segments
+ * of 512 sites from the class's first site in the region, K from the inverse binomial CDF table of (T, nb), picks and Floyd's rule
+ * as there, kappa = 1 + ((lo radix) >> 32); a class without sites draws nothing.  Bits 0-1 of kappa select the X / Z effect of
+ * location site_loc[site], bits 2-3 (a CNOT) those of site_loc[site] + 1.  The inner slots (>= 4096) are disjoint from the location
+ * version's (s < 2048): the two retried samplers of a seed are independent streams.  Attempts, exhaustion, blocks, steps, the tally
+ * and the layout of a sample [steps] [F flag words] [attempts] are those above, word for word. */
+typedef struct gf2_retry_gate gf2_retry_gate;
+
+/* The words on the host, serial, no GPU needed; words_out, ldw and attempts_out as gf2_retry_words_host's.  gf2_stream_tally_host on
+ * the first nsteps + F words completes the statement. */
+int gf2_retry_gate_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                              const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                              const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, uint64_t seed,
+                              int64_t first_sample, int64_t count, double p1, double p2, int64_t max_attempts, uint64_t* words_out, int64_t ldw,
+                              uint32_t* attempts_out);
+
+/* A sequence, its regions and their sites on the device.  Argument rules as gf2_retry_gate_words_host's (max_attempts, the rates
+ * and the range belong to the calls).  Destroyed by gf2_retry_gate_destroy. */
+int gf2_retry_gate_create(gf2_ctx* ctx, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                          const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                          const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, gf2_retry_gate** retry_out);
+int gf2_retry_gate_destroy(gf2_ctx* ctx, gf2_retry_gate* retry);
+
+/* The words of samples first_sample .. first_sample + count - 1 in device memory, ldo >= nsteps + F + 1 words per sample; words past
+ * those are left as they were.  out_dev: any 8-byte-aligned address. */
+int gf2_retry_gate_outcomes_dev(gf2_ctx* ctx, const gf2_retry_gate* retry, uint64_t seed, int64_t first_sample, int64_t count, double p1,
+                                double p2, int64_t max_attempts, uint64_t* out_dev, int64_t ldo);
+
+/* The tally of those samples on the device, no word stored: counts_out[GF2_RETRY_FIELDS] on the host, as gf2_mc_retry_decode's.
+ * Counts of sample ranges add.  The inverse-CDF tables are made per call and freed with it: no state beyond the handle. */
+int gf2_mc_retry_gate_decode(gf2_ctx* ctx, const gf2_retry_gate* retry, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                             int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed,
+                             int64_t first_sample, int64_t count, double p1, double p2, int64_t max_attempts, uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

@@ -195,6 +195,13 @@ SIGNATURES = {
     "gf2_retry_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_i64, _p, _c_i64],
     "gf2_mc_retry_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
                             ctypes.c_double, _c_i64, _p],
+    "gf2_retry_gate_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
+                                  _c_i64, _p, _c_i64, _p],
+    "gf2_retry_gate_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _p, _pp],
+    "gf2_retry_gate_destroy": [_p, _p],
+    "gf2_retry_gate_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, _c_i64, _p, _c_i64],
+    "gf2_mc_retry_gate_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
+                                 _c_i64, _p],
     "gf2_comm_unique_id": [_p, ctypes.c_size_t],
     "gf2_comm_create": [_p, _p, ctypes.c_int, ctypes.c_int, _pp],
     "gf2_comm_create_all": [_pp, ctypes.c_int, _pp],
@@ -535,6 +542,32 @@ def retry_words_host(type_eff, type_locations, type_flags, block_type, block_kin
     attempts = np.zeros((max(1, count), max(1, int(preparations))), dtype=np.uint32)
     check(lib().gf2_retry_words_host(*seq, *regions, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p_x), float(p_y), float(p_z),
                                      int(max_attempts), _ptr(out), int(ldw), _ptr(attempts)))
+    return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
+
+
+def _retry_sites(site_loc, site_regions, regions):
+    """The site table of a sequence's regions as the gf2_retry_gate_* entry points take it, and its pointer arguments."""
+    counts = np.ascontiguousarray(site_regions, dtype=np.int64).reshape(-1, 2)
+    loc = np.ascontiguousarray(site_loc, dtype=np.int32).reshape(-1)
+    if len(counts) != regions or int(counts.clip(0).sum()) != len(loc):
+        raise ValueError("one (n_1, n_2) per region, site_loc as long as their sum")
+    keep = (np.concatenate([loc, np.zeros(1, dtype=np.int32)]), counts)             # (never empty: a pointer to pass)
+    return keep, (_ptr(keep[0]), _ptr(counts) if len(counts) else None)
+
+
+def retry_gate_words_host(type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc, site_regions, seed,
+                          first, count, p1, p2, max_attempts, ldw, preparations):
+    """gf2_retry_gate_words_host (host code, no GPU): the (count, ldw) words [steps] [flag words] [attempts] of samples [first, first +
+    count) of the repeat-until-success sampler under gate-level faults and the (count, preparations) uint32 attempts of every
+    retried region."""
+    keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+    keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+    keep_sites, sites = _retry_sites(site_loc, site_regions, len(keep_regions[0]))
+    count = int(count)
+    out = np.zeros((max(1, count), max(1, int(ldw))), dtype="<u8")
+    attempts = np.zeros((max(1, count), max(1, int(preparations))), dtype=np.uint32)
+    check(lib().gf2_retry_gate_words_host(*seq, *regions, *sites, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p1), float(p2),
+                                          int(max_attempts), _ptr(out), int(ldw), _ptr(attempts)))
     return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
 
 
@@ -893,6 +926,21 @@ class Retry(_Handle):
 
 
 
+class RetryGate(_Handle):
+    """A block sequence, its regions and their sites on the device (gf2_retry_gate_create)."""
+    _destroy = "gf2_retry_gate_destroy"
+
+    def __init__(self, ctx, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc, site_regions):
+        self.ctx = ctx
+        keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+        keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+        keep_sites, sites = _retry_sites(site_loc, site_regions, len(keep_regions[0]))
+        out = ctypes.c_void_p()
+        check(lib().gf2_retry_gate_create(ctx.handle, *seq, *regions, *sites, ctypes.byref(out)))
+        self.handle = out.value
+
+
+
 class Context(object):
     """One HIP stream on one MI355X (gf2_ctx)."""
 
@@ -1218,6 +1266,21 @@ class Context(object):
         """gf2_mc_retry_decode: the fourteen counts of the repeat-until-success tally over samples [first, first + count)."""
         return _decode(lib().gf2_mc_retry_decode, RETRY_RULE, (self.handle, retry.handle), (), (r1, keys1, flips1, r2, keys2, flips2),
                        seed, first, count, p_x, p_y, p_z, int(max_attempts))
+
+    def retry_gate_create(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc, site_regions):
+        return RetryGate(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc, site_regions)
+
+    def retry_gate_outcomes_dev(self, retry, seed, first, count, p1, p2, max_attempts, out_buf, ldo):
+        check(lib().gf2_retry_gate_outcomes_dev(self.handle, retry.handle, seed & 0xFFFFFFFFFFFFFFFF, first, count, p1, p2, int(max_attempts),
+                                                out_buf.ptr, ldo))
+
+    def mc_retry_gate_decode(self, retry, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p1, p2, max_attempts):
+        """gf2_mc_retry_gate_decode: the fourteen counts of the repeat-until-success tally under gate-level faults."""
+        keep, rest = _rule_arguments(RETRY_RULE, (), (r1, keys1, flips1, r2, keys2, flips2))
+        counts = np.zeros(RETRY_RULE.fields, dtype=np.uint64)
+        check(lib().gf2_mc_retry_gate_decode(self.handle, retry.handle, *rest, seed & 0xFFFFFFFFFFFFFFFF, first, count, p1, p2, int(max_attempts),
+                                             _ptr(counts)))
+        return counts
 
     def mc_circuit_decode_strata(self, circ, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x, k_y, k_z):
         """gf2_mc_circuit_decode_strata: mc_circuit_decode's tables; weights and counts per stratum.  Returns the (nstrata, 5) counts."""

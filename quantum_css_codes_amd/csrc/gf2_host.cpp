@@ -1662,3 +1662,190 @@ int gf2_retry_words_host(const uint64_t* type_eff, const int64_t* type_locations
 }
 
 }  // extern "C"
+
+// ---- repeat-until-success under gate-level faults (include/gf2hip.h) -------------------------------------
+#include "gf2_retry_gate_plan.h"
+
+int gf2_retry_gate_plan(const char* who, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                        const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                        const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, int64_t max_attempts,
+                        StreamPlan* plan, RetryPlan* retry, RetryGatePlan* gate) {
+    if (int rc = gf2_retry_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
+                                max_attempts, plan, retry))
+        return rc;
+    if (!site_loc || !site_regions || !gate) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    const int64_t total = retry->type_first[(size_t)ntypes];
+    std::vector<uint8_t> seen;
+    std::vector<int32_t> sizes[2];                                               // sets of at most GF2_RETRY_MAX_SIZES + 1 values
+    try {
+        gate->site_first.assign((size_t)total, 0);
+        for (int c = 0; c < 2; ++c) {
+            gate->n[c].assign((size_t)total, 0);
+            gate->last_size[c].assign((size_t)total, -1);
+            sizes[c].reserve(GF2_RETRY_MAX_SIZES + 1);
+        }
+        int64_t most = 0;
+        for (int64_t t = 0; t < ntypes; ++t) most = type_locations[t] > most ? type_locations[t] : most;
+        seen.assign((size_t)most, 0);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    auto note_size = [&](int c, int32_t nb) {
+        if (std::find(sizes[c].begin(), sizes[c].end(), nb) == sizes[c].end() && sizes[c].size() <= (size_t)GF2_RETRY_MAX_SIZES) sizes[c].push_back(nb);
+    };
+    int64_t at = 0;                                                              // the next site of site_loc
+    for (int64_t t = 0; t < ntypes; ++t) {
+        for (int64_t q = retry->type_first[(size_t)t]; q < retry->type_first[(size_t)t + 1]; ++q) {
+            const int64_t r = q - retry->type_first[(size_t)t], first = retry->first[(size_t)q], count = retry->count[(size_t)q];
+            const int64_t n1 = site_regions[2 * q], n2 = site_regions[2 * q + 1];
+            if (n1 < 0 || n2 < 0 || n2 > count || n1 + 2 * n2 != count)
+                GF2_FAIL(GF2_E_ARG, "%s: region %lld of block type %lld has n_1 + 2 n_2 = %lld + 2 * %lld sites' locations, not its %lld locations", who,
+                         (long long)r, (long long)t, (long long)n1, (long long)n2, (long long)count);
+            gate->site_first[(size_t)q] = at;
+            gate->n[0][(size_t)q] = (int32_t)n1;
+            gate->n[1][(size_t)q] = (int32_t)n2;
+            for (int64_t l = 0; l < count; ++l) seen[(size_t)(first + l)] = 0;
+            for (int c = 0; c < 2; ++c) {
+                const int64_t m = c ? n2 : n1, width = c + 1;
+                for (int64_t s = 0; s < m; ++s, ++at) {
+                    const int64_t l = site_loc[at];
+                    if (l < first || l + width > first + count || seen[(size_t)l] || seen[(size_t)(l + width - 1)])
+                        GF2_FAIL(GF2_E_ARG, "%s: the sites of region %lld of block type %lld do not partition its locations %lld .. %lld: %s site %lld at "
+                                 "location %lld", who, (long long)r, (long long)t, (long long)first, (long long)(first + count - 1),
+                                 c ? "CNOT" : "one-operand", (long long)s, (long long)l);
+                    if (s > 0 && l <= site_loc[at - 1])
+                        GF2_FAIL(GF2_E_ARG, "%s: the %s sites of region %lld of block type %lld are not ascending: site %lld at location %lld follows "
+                                 "location %lld", who, c ? "CNOT" : "one-operand", (long long)r, (long long)t, (long long)s, (long long)l,
+                                 (long long)site_loc[at - 1]);
+                    seen[(size_t)l] = seen[(size_t)(l + width - 1)] = 1;
+                }
+                if (m > 512) note_size(c, 512);
+                if (m > 0) note_size(c, (int32_t)(m - (m - 1) / 512 * 512));
+            }                                                                     // (n_1 + 2 n_2 = count disjoint locations inside the region: a partition)
+        }
+    }
+    gate->sites = at;
+    for (int c = 0; c < 2; ++c) {
+        if (sizes[c].size() > (size_t)GF2_RETRY_MAX_SIZES)
+            GF2_FAIL(GF2_E_ARG, "%s: the %s sites of the regions have more than GF2_RETRY_MAX_SIZES = %d distinct segment sizes, one inverse-CDF table "
+                     "each", who, c ? "CNOT" : "one-operand", GF2_RETRY_MAX_SIZES);
+        std::sort(sizes[c].begin(), sizes[c].end());
+        gate->sizes[c] = sizes[c];
+        gate->full_size[c] = !sizes[c].empty() && sizes[c].back() == 512 ? (int32_t)sizes[c].size() - 1 : -1;
+        for (int64_t q = 0; q < total; ++q) {
+            const int32_t m = gate->n[c][(size_t)q];
+            if (m > 0) gate->last_size[c][(size_t)q] = (int32_t)(std::find(sizes[c].begin(), sizes[c].end(), m - (m - 1) / 512 * 512) - sizes[c].begin());
+        }
+    }
+    return GF2_OK;
+}
+
+extern "C" {
+
+// The definition of gf2_retry_gate_outcomes_dev's words (DESIGN.md section 5d "Repeat-until-success under gate-level faults"),
+// serial: gf2_retry_words_host's walk, an attempt drawn as gf2_gate_outcomes_host draws a sample -- the region's one-operand sites,
+// then its CNOT sites, each class with its own slots, rate and radix of kinds -- under the attempt's key.
+int gf2_retry_gate_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                              const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                              const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, uint64_t seed,
+                              int64_t first_sample, int64_t count, double p1, double p2, int64_t max_attempts, uint64_t* words_out, int64_t ldw,
+                              uint32_t* attempts_out) {
+    const char* who = "gf2_retry_gate_words_host";
+    StreamPlan plan;
+    RetryPlan retry;
+    RetryGatePlan gate;
+    if (int rc = gf2_retry_gate_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
+                                     site_loc, site_regions, max_attempts, &plan, &retry, &gate))
+        return rc;
+    if (int rc = gf2_gate_check_mc(who, p1, p2, first_sample, count)) return rc;
+    const int64_t ldr = plan.nsteps + plan.flag_words + 1;
+    if (ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the sequence's nsteps + F + 1 = %lld words", who, (long long)ldr);
+    if (count == 0) return GF2_OK;
+    if (!words_out) GF2_FAIL(GF2_E_ARG, "%s: null buffer", who);
+    const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
+    const int SEG = 512;
+    const uint64_t radix[2] = {3, 15}, slot_base[2] = {GF2_GATE_MC_SLOT_ONE, GF2_GATE_MC_SLOT_CNOT};
+    const uint64_t T[2] = {host_quantise(p1), host_quantise(p2)};
+    std::vector<uint64_t> cdf[2];                                                // per class: [size][SEG + 1]
+    try {
+        for (int cl = 0; cl < 2; ++cl) cdf[cl].resize(gate.sizes[cl].size() * (SEG + 1));
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    for (int cl = 0; cl < 2; ++cl)
+        for (size_t k = 0; k < gate.sizes[cl].size(); ++k) host_binomial_cdf_table(T[cl], gate.sizes[cl][k], &cdf[cl][k * (SEG + 1)]);
+    for (int64_t i = 0; i < count; ++i) {
+        uint64_t* const out = words_out + i * ldw;
+        for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
+        uint32_t* const tries = attempts_out ? attempts_out + i * retry.preparations : nullptr;
+        for (int64_t q = 0; tries && q < retry.preparations; ++q) tries[q] = 0;
+        const uint64_t ks = host_mix64(seed + golden * ((uint64_t)(first_sample + i) + 1));
+        uint64_t frame = 0, attempts = 0;
+        int64_t g = 0, prep = 0;
+        bool exhausted = false;
+        for (int64_t b = 0; b < nblocks && !exhausted; ++b) {
+            uint64_t local = 0, tail = 0;
+            if (block_kind[b] != GF2_STREAM_FINAL) {
+                const int64_t t = block_type[b];
+                for (int64_t r = retry.type_first[(size_t)t]; r < retry.type_first[(size_t)t + 1] && !exhausted; ++r, ++g) {
+                    const int64_t limit = retry.retried[(size_t)r] ? max_attempts : 1;
+                    const uint64_t* const rows = type_eff + (size_t)plan.type_offset[(size_t)t] * 6;   // the type's table: sites are type-local
+                    const uint64_t kr = host_mix64(ks + stream * (GF2_RETRY_SLOT_BASE + (uint64_t)g + 1));
+                    uint64_t acc[3] = {0, 0, 0};
+                    int64_t a = 0;
+                    do {
+                        const uint64_t ka = host_mix64(kr + golden * ((uint64_t)a + 1));
+                        acc[0] = acc[1] = acc[2] = 0;
+                        int64_t site_base = gate.site_first[(size_t)r];
+                        for (int cl = 0; cl < 2; site_base += gate.n[cl][(size_t)r], ++cl) {
+                            const int64_t m = gate.n[cl][(size_t)r], nseg = (m + SEG - 1) / SEG;      // (none for an empty class)
+                            for (int64_t s = 0; s < nseg; ++s) {
+                                const bool last = s == nseg - 1;
+                                const int nb = last ? (int)(m - SEG * s) : SEG;
+                                const uint64_t* table = &cdf[cl][(size_t)(last ? gate.last_size[cl][(size_t)r] : gate.full_size[cl]) * (SEG + 1)];
+                                const uint64_t d = host_mix64(ka + stream * (slot_base[cl] + (uint64_t)s + 1));
+                                const uint64_t u = d >> 32;
+                                int K = 0;
+                                while (K < nb && u >= table[K]) K += 1;
+                                uint64_t taken[SEG / 64] = {0, 0, 0, 0, 0, 0, 0, 0};
+                                for (int k = 0; k < K; ++k) {
+                                    const uint64_t v = host_mix64(d + golden * (uint64_t)(k + 1));
+                                    const uint64_t hi = v >> 32, lo = v & 0xFFFFFFFFull;
+                                    const uint64_t j = (uint64_t)(nb - K + k);
+                                    const uint64_t pick = (hi * (j + 1)) >> 32;          // Floyd: a candidate in [0, j]
+                                    const uint64_t pos = ((taken[pick >> 6] >> (pick & 63)) & 1ull) ? j : pick;
+                                    taken[pos >> 6] |= 1ull << (pos & 63);
+                                    const uint64_t kappa = 1 + ((lo * radix[cl]) >> 32);
+                                    const uint64_t* e = rows + (size_t)site_loc[site_base + SEG * s + (int64_t)pos] * 6;
+                                    for (int bit = 0; bit < 4; ++bit)                     // bits 2, 3: the CNOT's second location
+                                        if ((kappa >> bit) & 1)
+                                            for (int q = 0; q < 3; ++q) acc[q] ^= e[3 * bit + q];
+                                }
+                            }
+                        }
+                        a += 1;
+                    } while (acc[2] != 0 && a < limit);
+                    if (retry.retried[(size_t)r]) {
+                        attempts += (uint64_t)a;
+                        if (tries) tries[prep] = (uint32_t)a;
+                        prep += 1;
+                    }
+                    if (acc[2] != 0) {                                           // no attempt passed: the walk stops here
+                        exhausted = true;
+                        const int64_t row = plan.flag[(size_t)b];
+                        out[plan.nsteps + (row >> 6)] |= acc[2] << (row & 63);
+                        if ((row & 63) && (acc[2] >> (64 - (row & 63)))) out[plan.nsteps + (row >> 6) + 1] |= acc[2] >> (64 - (row & 63));
+                    }
+                    local ^= acc[0], tail ^= acc[1];
+                }
+            }
+            if (exhausted) break;
+            if (plan.step[(size_t)b] >= 0) out[plan.step[(size_t)b]] = (frame & gf2_stream_frame_mask(block_kind[b])) ^ local;
+            frame ^= tail;
+        }
+        out[plan.nsteps + plan.flag_words] = attempts;
+    }
+    return GF2_OK;
+}
+
+}  // extern "C"

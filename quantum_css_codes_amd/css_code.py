@@ -533,6 +533,22 @@ class CSSCode(QECC):
         gadget = stream_noise.stream_for(self, "program", ft_noise.check_ops(ops))
         return gadget.retry_error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample, max_attempts=max_attempts)
 
+    def error_correct_retried_gate_error_rates(self, num_samples, p1, p2, rounds, seed=0, first_sample=0, idle_data=False, max_attempts=256):
+        """[build-defined]  error_correct_retried_error_rates under gate-level faults (stream_noise.StreamedGadget
+        .retry_gate_error_rates): every one-operand gate fails with probability p1 and one of 3 kinds, every CNOT as one event with
+        probability p2 and one of 15 two-qubit Paulis.  Any number of rounds; the rates per accepted sample are those of
+        error_correct_gate_error_rates where that accepts the size, the samples are different samples.  max_attempts = 1 is
+        gate-level post-selection of any length."""
+        from . import stream_noise
+        gadget = stream_noise.stream_for(self, "cycle", (int(rounds), bool(idle_data)))
+        return gadget.retry_gate_error_rates(num_samples, p1, p2, seed=seed, first_sample=first_sample, max_attempts=max_attempts)
+
+    def logical_program_retried_gate_error_rates(self, ops, num_samples, p1, p2, seed=0, first_sample=0, max_attempts=256):
+        """[build-defined]  logical_program_retried_error_rates under gate-level faults, likewise."""
+        from . import ft_noise, stream_noise
+        gadget = stream_noise.stream_for(self, "program", ft_noise.check_ops(ops))
+        return gadget.retry_gate_error_rates(num_samples, p1, p2, seed=seed, first_sample=first_sample, max_attempts=max_attempts)
+
 
 # -- free functions -----------------------------------------------------------------------------------------
 

@@ -32,6 +32,10 @@ BlockType.regions, every `prep ...` part of the builder a retried region, and a 
 verifications pass.  Locations fail independently and a flag row depends on one region only, so the accepted samples have exactly
 the distribution post-selection gives, essentially every sample is accepted, and the cost is linear in the number of blocks.  The
 samples are other samples than the post-selected routes draw: the rates agree, the counts of a seed do not.
+
+The retry_gate_* methods run the same walk under gate-level faults (DESIGN.md section 5d "Repeat-until-success under gate-level
+faults"): BlockType.gate_regions gives every region its sites, a one-operand gate fails with probability p1 and one of 3 kinds, a
+CNOT as one event with probability p2 and one of 15.  Regions are cut at gate boundaries, so the argument above holds for sites.
 """
 import numpy as np
 
@@ -99,6 +103,24 @@ class BlockType(object):
         return np.array([np.bitwise_or.reduce(self.effects[first:first + count, :, 2].reshape(-1)) for first, count, _ in self.regions],
                         dtype=np.uint64)
 
+    def gate_regions(self):
+        """The sites of the gate-level fault model (circuit_noise.gate_sites) region by region: (site_loc, site_regions).  site_loc
+        (int32) is the type-local first location of every site in region-major order -- for each region of `regions` in order its
+        one-operand gates in gate order, then its CNOTs in gate order, a CNOT's second location being site_loc + 1 -- and
+        site_regions (R, 2) int64 rows (n1, n2) with n1 + 2 n2 the region's locations.  The regions are cut at gate boundaries; a
+        gate whose locations fall into two regions is a ValueError."""
+        loc, n1, _, _ = circuit_noise.gate_sites(self.gates, self.locations)
+        loc = loc.astype(np.int64)
+        width = np.where(np.arange(len(loc)) < n1, 1, 2)
+        stops = np.cumsum(self.regions[:, 1])
+        region = np.searchsorted(stops, loc, side="right")
+        if np.any(np.searchsorted(stops, loc + width - 1, side="right") != region):
+            raise ValueError("a gate of block type %s has its locations in two regions" % self.name)
+        order = np.lexsort((np.arange(len(loc)), width, region))       # by region, one-operand sites first, gate order inside a class
+        counts = np.zeros((len(self.regions), 2), dtype=np.int64)
+        np.add.at(counts, (region, width - 1), 1)
+        return loc[order].astype(np.int32), counts
+
 
 def _emit_prepare(build):
     build.prep(build.data, 'zero', 0, verifier=build.anc_1)        # ftqc.py:78
@@ -151,8 +173,12 @@ class StreamedGadget(object):
         self.type_regions = np.ascontiguousarray(np.concatenate([t.regions for t in self.types]))
         self.type_nregions = np.array([len(t.regions) for t in self.types], dtype=np.int64)
         self.preparations = int(sum(int(self.types[t].regions[:, 2].sum()) for t in self.block_type if t >= 0))
+        sites = [t.gate_regions() for t in self.types]
+        self.type_site_loc = np.ascontiguousarray(np.concatenate([loc for loc, _ in sites]), dtype=np.int32)
+        self.type_site_regions = np.ascontiguousarray(np.concatenate([counts for _, counts in sites]), dtype=np.int64)
         self._device = None
         self._retry_device = None
+        self._retry_gate_device = None
 
     @classmethod
     def cycle(cls, code, rounds, idle_data=False):
@@ -332,6 +358,51 @@ class StreamedGadget(object):
         those of the post-selected routes at every p; the samples are different samples."""
         return _native.retry_words_host(*self._retry_sequence(), seed, first_sample, num_samples, p_x, p_y, p_z, max_attempts, self.ldw + 1,
                                         self.preparations)
+
+    # -- repeat-until-success under gate-level faults ----------------------------------------------------------------------------
+    def _retry_gate_sequence(self):
+        return self._retry_sequence() + (self.type_site_loc, self.type_site_regions)
+
+    def retry_gate_device(self):
+        if self._retry_gate_device is None:
+            self._retry_gate_device = _native.default_context().retry_gate_create(*self._retry_gate_sequence())
+        return self._retry_gate_device
+
+    def retry_gate_outcomes(self, num_samples, p1, p2, seed=0, first_sample=0, max_attempts=256):
+        """retry_outcomes under gate-level faults (DESIGN.md section 5d "Repeat-until-success under gate-level faults"): every
+        one-operand gate fails with probability p1 and one of 3 kinds, every CNOT as one event with probability p2 and one of 15; a
+        (num_samples, ldw + 1) uint64 array [steps] [flag words, zero unless the sample is exhausted] [attempts of the sample]
+        (gf2_retry_gate_outcomes_dev).  max_attempts = 1 is gate-level post-selection of any length."""
+        ctx = _native.default_context()
+        count = int(num_samples)
+        buf = ctx.alloc(max(1, count) * (self.ldw + 1) * 8)
+        try:
+            ctx.retry_gate_outcomes_dev(self.retry_gate_device(), int(seed), int(first_sample), count, float(p1), float(p2), int(max_attempts),
+                                        buf, self.ldw + 1)
+            return buf.download((count, self.ldw + 1), np.uint64)
+        finally:
+            buf.free()
+
+    def retry_gate_counts(self, num_samples, p1, p2, seed=0, first_sample=0, max_attempts=256):
+        """The fourteen RETRY_FIELDS counts of samples [first_sample, first_sample + num_samples) under gate-level faults on the
+        device (gf2_mc_retry_gate_decode)."""
+        return _native.default_context().mc_retry_gate_decode(self.retry_gate_device(), *self._tables(), int(seed), int(first_sample),
+                                                               int(num_samples), float(p1), float(p2), int(max_attempts))
+
+    def retry_gate_error_rates(self, num_samples, p1, p2, seed=0, first_sample=0, max_attempts=256):
+        """retry_error_rates' dict under gate-level faults: the rates per accepted sample are those of ECCircuit / FTProgram
+        .gate_error_rates at every (p1, p2) where those accept the size; the samples are different samples.  The counts of sample
+        ranges add."""
+        counts = self.retry_gate_counts(num_samples, p1, p2, seed, first_sample, max_attempts)
+        out = self._dict(counts, num_samples)
+        out.update(exhausted=int(counts[12]), attempts=int(counts[13]), preparations=self.preparations)
+        return out
+
+    def retry_gate_words_host(self, num_samples, p1, p2, seed=0, first_sample=0, max_attempts=256):
+        """retry_gate_outcomes' words on the host (gf2_retry_gate_words_host, no GPU) and the (num_samples, preparations) uint32
+        attempts of every preparation in order, 0 for one never reached.  tally_host on words[:, :ldw] completes the statement."""
+        return _native.retry_gate_words_host(*self._retry_gate_sequence(), seed, first_sample, num_samples, p1, p2, max_attempts, self.ldw + 1,
+                                             self.preparations)
 
 
 def stream_for(code, what, key):
