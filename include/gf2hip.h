@@ -658,6 +658,49 @@ int gf2_ft_enumerate_list(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nste
                           int64_t w, int64_t first_rank, int64_t count, uint64_t select, int64_t capacity, uint64_t* records_out,
                           int64_t* found_out);
 
+/* ---- malignant fault sets under gate-level faults ------------------------------------------------------
+ * [build-defined, DESIGN.md section 5e "Malignant fault sets under gate-level faults"]  The walk of "exact strata of the two
+ * post-selected gadgets under gate-level faults" above, unchanged -- site table, ranks [first_rank, first_rank + count) of one
+ * (w, b), all 3^a 15^b kind assignments each, the same judgement -- but the configurations of a chosen class are listed instead of
+ * counted.  Class byte and `select` as "malignant fault sets" above define them (GF2_EC_CLASS_BITS, GF2_FT_CLASS_BITS): a
+ * configuration is listed iff it is accepted and (class & select) != 0.  A record is GF2_FAULT_RECORD_WORDS words:
+ *   word 0: the rank r_s + C(n_1, a) r_c within (w, b), absolute (the rank first_rank counts in);
+ *   word 1: bits 0 .. 15 the kind masks kappa of the picks, one nibble each: the a one-operand picks first in ascending site order
+ *           (kappa in 1 .. 3), then the b CNOT picks in ascending site order (kappa in 1 .. 15, the bit meaning above); bits
+ *           32 .. 39 the class byte; every other bit zero.  The number c of two-operand kinds is a function of the record.
+ * *found_out is the number of listed configurations of the range, whatever the capacity; records_out (capacity records) holds them
+ * sorted by (word 0, word 1 bits 0 .. 15) ascending and is written only if capacity >= *found_out (capacity 0 just counts, and
+ * records_out may then be null).  The lists of disjoint ranges concatenate.
+ *
+ * The definitions on the host, serial, no GPU needed: gf2_ec_gate_enumerate_host's / gf2_ft_gate_enumerate_host's walk, rule and
+ * argument errors, plus GF2_E_ARG for select == 0, for a select bit outside the rule's class bits and for capacity < 0. */
+int gf2_ec_gate_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                                    const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                                    int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b,
+                                    int64_t first_rank, int64_t count, uint64_t select, int64_t capacity, uint64_t* records_out,
+                                    int64_t* found_out);
+int gf2_ft_gate_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                                    const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                                    const uint8_t* flips2, int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w,
+                                    int64_t b, int64_t first_rank, int64_t count, uint64_t select, int64_t capacity, uint64_t* records_out,
+                                    int64_t* found_out);
+
+/* The same lists from the device.  Every check of gf2_ec_gate_enumerate / gf2_ft_gate_enumerate, the list's arguments as above, and
+ * capacity <= GF2_FAULT_LIST_MAX_CAPACITY.  The hash tables and the device copy of site_loc are made once per call and the range is
+ * cut into launches of at most 2^28 configurations; ranks stay absolute across them.  A wavefront that has anything to list takes
+ * its slots with one atomic add on a 64-bit counter that is zeroed once per call and runs on across the launches, and a record is
+ * stored only if its slot is below capacity.  The call allocates `capacity` records on the device, downloads them only when
+ * *found_out <= capacity and sorts them on the host by (word 0, kind masks): the result does not depend on the order the wavefronts
+ * arrived in, nor on what an earlier call left in the workspace, and is byte-identical to the host statement's. */
+int gf2_ec_gate_enumerate_list(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t rounds, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                               int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                               const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b, int64_t first_rank, int64_t count,
+                               uint64_t select, int64_t capacity, uint64_t* records_out, int64_t* found_out);
+int gf2_ft_gate_enumerate_list(gf2_ctx* ctx, const gf2_circuit* circuit, int64_t nsteps, uint64_t measure_mask, int64_t r1, const uint64_t* keys1,
+                               const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                               const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b, int64_t first_rank, int64_t count,
+                               uint64_t select, int64_t capacity, uint64_t* records_out, int64_t* found_out);
+
 /* ---- sampled strata of the two post-selected gadgets ----------------------------------------------------
  * [build-defined, DESIGN.md "Sampled strata of the cycle" and "Sampled strata of the measurement"]  The two notions above combined,
  * neither changed: stratified sample i of weight w over the gadget's L locations is the pure function of (seed, i, w) of

@@ -164,6 +164,14 @@ SIGNATURES = {
                               ctypes.POINTER(_c_i64)],
     "gf2_ft_enumerate_list": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p,
                               ctypes.POINTER(_c_i64)],
+    "gf2_ec_gate_enumerate_list_host": [_p, _c_i64, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_i64, _c_i64,
+                                        _c_i64, _c_i64, _c_u64, _c_i64, _p, ctypes.POINTER(_c_i64)],
+    "gf2_ft_gate_enumerate_list_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_i64,
+                                        _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _p, ctypes.POINTER(_c_i64)],
+    "gf2_ec_gate_enumerate_list": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
+                                   _c_u64, _c_i64, _p, ctypes.POINTER(_c_i64)],
+    "gf2_ft_gate_enumerate_list": [_p, _p, _c_i64, _c_u64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
+                                   _c_i64, _c_u64, _c_i64, _p, ctypes.POINTER(_c_i64)],
     "gf2_stratum_outcomes_host": [_p, _c_i64, _c_i64, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p,
                                   _c_i64],
     "gf2_mc_ec_decode_strata": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, _p, _p,
@@ -749,6 +757,46 @@ def ft_enumerate_list_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, key
     eff, table = _effects(eff)
     return _enumerate_list(lib().gf2_ft_enumerate_list_host, FT_RULE, table, (nsteps, measure_mask), (r1, keys1, flips1, r2, keys2, flips2),
                            w, first_rank, count, select, capacity)
+
+
+def _gate_enumerate_list(fn, rule, front, head, tables, sites, w, b, first_rank, count, select, capacity, limit=None, into=None):
+    """A gf2_*_gate_enumerate_list(_host) entry point, front as _enumerate's: (found, records) as _enumerate_list gives them, the
+    records' word 1 holding a kind mask per pick.  into: a C-contiguous uint64 array of at least `capacity` records that the entry
+    point writes in place of a fresh one (the records returned are then a view of it)."""
+    keep, rest = _gate_arguments(rule, head, tables, sites)
+    capacity = int(capacity)
+    if into is None:
+        records = np.zeros((max(1, capacity if limit is None else min(capacity, limit)), FAULT_RECORD_WORDS), dtype="<u8")
+    else:
+        records = into
+        if records.dtype != np.dtype("<u8") or not records.flags.c_contiguous or records.size < FAULT_RECORD_WORDS * max(0, capacity):
+            raise ValueError("into must be a C-contiguous uint64 array of at least capacity records")
+        records = records.reshape(-1)[:records.size // FAULT_RECORD_WORDS * FAULT_RECORD_WORDS].reshape(-1, FAULT_RECORD_WORDS)
+    found = _c_i64(0)
+    check(fn(*front, *rest, int(w), int(b), int(first_rank), int(count), int(select) & 0xFFFFFFFFFFFFFFFF, capacity,
+             _ptr(records) if capacity > 0 else None, ctypes.byref(found)))
+    found = int(found.value)
+    if found > capacity:
+        return found, None
+    return found, (records[:found].copy() if into is None else records[:found])
+
+
+def ec_gate_enumerate_list_host(eff, rounds, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count, select, capacity,
+                                into=None):
+    """gf2_ec_gate_enumerate_list_host (host code, no GPU): (found, records) of the error-correction cycle over the site subsets of
+    ranks [first_rank, first_rank + count) of (w, b) -- found, the number of accepted configurations whose class byte has a bit of
+    `select`; records, their (found, 2) uint64 words sorted by (rank, kind masks), or None when `capacity` records do not hold them."""
+    eff, table = _effects(eff)
+    return _gate_enumerate_list(lib().gf2_ec_gate_enumerate_list_host, EC_RULE, table, (rounds,), (r1, keys1, flips1, r2, keys2, flips2),
+                                (site_loc, n1, n2), w, b, first_rank, count, select, capacity, into=into)
+
+
+def ft_gate_enumerate_list_host(eff, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count,
+                                select, capacity, into=None):
+    """gf2_ft_gate_enumerate_list_host (host code, no GPU): (found, records) of the logical measurement, likewise."""
+    eff, table = _effects(eff)
+    return _gate_enumerate_list(lib().gf2_ft_gate_enumerate_list_host, FT_RULE, table, (nsteps, measure_mask),
+                                (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), w, b, first_rank, count, select, capacity, into=into)
 
 
 def _decode(fn, rule, front, head, tables, seed, first, count, p_x, p_y, p_z, *more, null_flips=False):
@@ -1357,6 +1405,20 @@ class Context(object):
         """gf2_ft_enumerate_list: ft_enumerate_list_host's (found, records) from the device, byte for byte."""
         return _enumerate_list(lib().gf2_ft_enumerate_list, FT_RULE, (self.handle, circ.handle), (nsteps, measure_mask),
                                (r1, keys1, flips1, r2, keys2, flips2), w, first_rank, count, select, capacity, FAULT_LIST_MAX_CAPACITY)
+
+    def ec_gate_enumerate_list(self, circ, rounds, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank, count, select,
+                               capacity, into=None):
+        """gf2_ec_gate_enumerate_list: ec_gate_enumerate_list_host's (found, records) from the device, byte for byte."""
+        return _gate_enumerate_list(lib().gf2_ec_gate_enumerate_list, EC_RULE, (self.handle, circ.handle), (rounds,),
+                                    (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), w, b, first_rank, count, select, capacity,
+                                    FAULT_LIST_MAX_CAPACITY, into)
+
+    def ft_gate_enumerate_list(self, circ, nsteps, measure_mask, r1, keys1, flips1, r2, keys2, flips2, site_loc, n1, n2, w, b, first_rank,
+                               count, select, capacity, into=None):
+        """gf2_ft_gate_enumerate_list: ft_gate_enumerate_list_host's (found, records) from the device, byte for byte."""
+        return _gate_enumerate_list(lib().gf2_ft_gate_enumerate_list, FT_RULE, (self.handle, circ.handle), (nsteps, measure_mask),
+                                    (r1, keys1, flips1, r2, keys2, flips2), (site_loc, n1, n2), w, b, first_rank, count, select, capacity,
+                                    FAULT_LIST_MAX_CAPACITY, into)
 
     def check_create(self, packed, r, n):
         return Check(self, packed, r, n)

@@ -1,7 +1,7 @@
 // What the kernels over a circuit's effect table share -- gf2_circuit.hip (the fault Monte-Carlo), gf2_enumerate.hip (the exact
 // strata), gf2_stream.hip (the streamed route) and the entry points of the two post-selected gadgets: gf2_ec.hip (the
 // error-correction cycle), gf2_ft.hip (the fault-tolerant logical measurement), gf2_gadget_strata.hip (their sampled strata),
-// gf2_gadget_enumerate.hip (their exact strata), gf2_gate_enumerate.hip (those under gate-level faults) and gf2_gadget_list.hip
+// gf2_gadget_enumerate.hip (their exact strata), gf2_gate_enumerate.hip (those under gate-level faults), gf2_gadget_list.hip and gf2_gate_list.hip
 // (their malignant fault sets): the circuit object, the Monte-Carlo layout of its outcome words, whether a launch stages the effect
 // table in LDS, the device side of the tally's syndrome tables and the gather loop of a Monte-Carlo sample.
 #pragma once

@@ -933,8 +933,9 @@ void subset_successor(int64_t k, int32_t* pos) {
 
 // The walk of a rank range of sites, serial: the first subset unranked part by part (rank = r_s + C(n_1, a) r_c), the others by
 // the successor of the product order (the one-operand part steps; when it wraps, the CNOT part does), every kind assignment by an
-// odometer over [1, 3]^a x [1, 15]^b, the outcome words XOR-ed from scratch and handed to visit(site, kappa, c, out): site[k] and
-// kappa[k] the site and kind mask of pick k (the a one-operand picks first), c the number of two-operand kinds.
+// odometer over [1, 3]^a x [1, 15]^b, the outcome words XOR-ed from scratch and handed to visit(i, site, kappa, c, out): i the
+// subset's place in the range, site[k] and kappa[k] the site and kind mask of pick k (the a one-operand picks first, each part in
+// ascending site order), c the number of two-operand kinds.  The counting and the listing statements below share it.
 template <class Visit>
 void gate_walk(const uint64_t* eff, int64_t ldr, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b, int64_t first_rank,
                int64_t count, Visit visit) {
@@ -965,13 +966,70 @@ void gate_walk(const uint64_t* eff, int64_t ldr, const int32_t* site_loc, int64_
                 }
                 c += (kappa[k] & 3) != 0 && (kappa[k] >> 2) != 0;
             }
-            visit(site, kappa, c, out);
+            visit(i, site, kappa, c, out);
             int64_t k = 0;                                                   // odometer over 1 .. 3 or 1 .. 15
             while (k < w && kappa[k] == (k < a ? 3 : 15)) kappa[k++] = 1;
             if (k == w) break;
             kappa[k] += 1;
         }
     }
+}
+
+// ... every configuration of which is either counted (the statements below call gate_walk themselves) or listed (include/gf2hip.h
+// "malignant fault sets under gate-level faults"): classify(out) is the configuration's class byte; the records of the listed ones,
+// sorted by (rank, kind masks), go to records_out if they fit `capacity`, their number to *found_out either way.
+template <class Classify>
+int gate_list_walk(const char* who, const uint64_t* eff, int64_t ldr, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b,
+                   int64_t first_rank, int64_t count, uint64_t select, int64_t capacity, uint64_t* records_out, int64_t* found_out,
+                   Classify classify) {
+    struct Record { uint64_t rank, tail; };
+    std::vector<Record> records;
+    int64_t found = 0;
+    try {
+        gate_walk(eff, ldr, site_loc, n1, n2, w, b, first_rank, count, [&](int64_t i, const int32_t*, const int* kappa, int64_t, const uint64_t* out) {
+            const uint8_t cls = classify(out);
+            if (!(cls & 1) || !(cls & select)) return;
+            if (found++ >= capacity) return;                                 // (counted; the list is dropped once it cannot fit)
+            uint64_t kinds = 0;
+            for (int64_t k = 0; k < w; ++k) kinds |= (uint64_t)kappa[k] << (4 * k);
+            records.push_back(Record{(uint64_t)first_rank + (uint64_t)i, kinds | (uint64_t)cls << 32});
+        });
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    *found_out = found;
+    if (found > capacity) return GF2_OK;
+    std::sort(records.begin(), records.end(), [](const Record& a, const Record& b) {
+        return a.rank != b.rank ? a.rank < b.rank : (a.tail & 0xFFFFull) < (b.tail & 0xFFFFull);
+    });
+    for (size_t k = 0; k < records.size(); ++k) {
+        records_out[GF2_FAULT_RECORD_WORDS * k] = records[k].rank;
+        records_out[GF2_FAULT_RECORD_WORDS * k + 1] = records[k].tail;
+    }
+    return GF2_OK;
+}
+
+// The argument rules gf2_ec_gate_enumerate_host and gf2_ec_gate_enumerate_list_host share (eff not null) ...
+int ec_gate_enumerate_check(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                            const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                            const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b, int64_t first_rank, int64_t count) {
+    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
+    if (int rc = ec_check_layout(who, ldr, rounds, r1, r2)) return rc;
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    if (int rc = gf2_gate_check_range(who, locations, site_loc, n1, n2, w, b, first_rank, count)) return rc;
+    return ec_check_effects(who, eff, locations, ldr, rounds, r1, r2);
+}
+
+// ... and those of gf2_ft_gate_enumerate_host and gf2_ft_gate_enumerate_list_host.
+int ft_gate_enumerate_check(const char* who, const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                            const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                            int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b, int64_t first_rank,
+                            int64_t count) {
+    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
+    if (int rc = ft_check_layout(who, ldr, nsteps, measure_mask, r1, r2)) return rc;
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    if (int rc = gf2_gate_check_range(who, locations, site_loc, n1, n2, w, b, first_rank, count)) return rc;
+    return ft_check_effects(who, eff, locations, ldr, nsteps, measure_mask, r1, r2);
 }
 }  // namespace
 
@@ -985,17 +1043,15 @@ int gf2_ec_gate_enumerate_host(const uint64_t* eff, int64_t locations, int64_t l
                                int64_t count, uint64_t* counts_out) {
     const char* who = "gf2_ec_gate_enumerate_host";
     if (!eff || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
-    if (int rc = ec_check_layout(who, ldr, rounds, r1, r2)) return rc;
-    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
-    if (int rc = gf2_gate_check_range(who, locations, site_loc, n1, n2, w, b, first_rank, count)) return rc;
-    if (int rc = ec_check_effects(who, eff, locations, ldr, rounds, r1, r2)) return rc;
+    if (int rc = ec_gate_enumerate_check(who, eff, locations, ldr, rounds, r1, keys1, flips1, entries1, r2, keys2, flips2, entries2, site_loc, n1, n2, w, b,
+                                         first_rank, count))
+        return rc;
     const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
     for (int64_t k = 0; k < (b + 1) * GF2_EC_FIELDS; ++k) counts_out[k] = 0;
     if (count == 0) return GF2_OK;
     HostTable tab[2];
     if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
-    gate_walk(eff, ldr, site_loc, n1, n2, w, b, first_rank, count, [&](const int32_t*, const int*, int64_t c, const uint64_t* out) {
+    gate_walk(eff, ldr, site_loc, n1, n2, w, b, first_rank, count, [&](int64_t, const int32_t*, const int*, int64_t c, const uint64_t* out) {
         (void)ec_tally_sample(out, ldr, rounds, mask, tab, counts_out + c * GF2_EC_FIELDS);
     });
     return GF2_OK;
@@ -1008,21 +1064,67 @@ int gf2_ft_gate_enumerate_host(const uint64_t* eff, int64_t locations, int64_t l
                                int64_t first_rank, int64_t count, uint64_t* counts_out) {
     const char* who = "gf2_ft_gate_enumerate_host";
     if (!eff || !counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
-    if (ldr < 1) GF2_FAIL(GF2_E_ARG, "%s: needs ldr >= 1 words per effect", who);
-    if (int rc = ft_check_layout(who, ldr, nsteps, measure_mask, r1, r2)) return rc;
-    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
-    if (int rc = gf2_gate_check_range(who, locations, site_loc, n1, n2, w, b, first_rank, count)) return rc;
-    if (int rc = ft_check_effects(who, eff, locations, ldr, nsteps, measure_mask, r1, r2)) return rc;
+    if (int rc = ft_gate_enumerate_check(who, eff, locations, ldr, nsteps, measure_mask, r1, keys1, flips1, entries1, r2, keys2, flips2, entries2, site_loc,
+                                         n1, n2, w, b, first_rank, count))
+        return rc;
     const int trials = __builtin_popcountll(measure_mask);
     const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
     for (int64_t k = 0; k < (b + 1) * GF2_FT_FIELDS; ++k) counts_out[k] = 0;
     if (count == 0) return GF2_OK;
     HostTable tab[2];
     if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
-    gate_walk(eff, ldr, site_loc, n1, n2, w, b, first_rank, count, [&](const int32_t*, const int*, int64_t c, const uint64_t* out) {
+    gate_walk(eff, ldr, site_loc, n1, n2, w, b, first_rank, count, [&](int64_t, const int32_t*, const int*, int64_t c, const uint64_t* out) {
         (void)ft_tally_sample(out, ldr, nsteps, measure_mask, trials, mask, tab, counts_out + c * GF2_FT_FIELDS);
     });
     return GF2_OK;
+}
+
+// The definition of gf2_ec_gate_enumerate_list (DESIGN.md section 5e "Malignant fault sets under gate-level faults"), serial:
+// gf2_ec_gate_enumerate_host's walk and rule, the class byte of every configuration kept instead of its counts.
+int gf2_ec_gate_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t rounds, int64_t r1, const uint64_t* keys1,
+                                    const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2,
+                                    int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w, int64_t b,
+                                    int64_t first_rank, int64_t count, uint64_t select, int64_t capacity, uint64_t* records_out,
+                                    int64_t* found_out) {
+    const char* who = "gf2_ec_gate_enumerate_list_host";
+    if (!eff) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (int rc = list_check_args(who, select, GF2_EC_CLASS_BITS, capacity, records_out, found_out)) return rc;
+    if (int rc = ec_gate_enumerate_check(who, eff, locations, ldr, rounds, r1, keys1, flips1, entries1, r2, keys2, flips2, entries2, site_loc, n1, n2, w, b,
+                                         first_rank, count))
+        return rc;
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    *found_out = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    return gate_list_walk(who, eff, ldr, site_loc, n1, n2, w, b, first_rank, count, select, capacity, records_out, found_out, [&](const uint64_t* out) {
+        uint64_t unused[GF2_EC_FIELDS] = {0};
+        return ec_tally_sample(out, ldr, rounds, mask, tab, unused);
+    });
+}
+
+// The definition of gf2_ft_gate_enumerate_list, likewise.
+int gf2_ft_gate_enumerate_list_host(const uint64_t* eff, int64_t locations, int64_t ldr, int64_t nsteps, uint64_t measure_mask, int64_t r1,
+                                    const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                                    const uint8_t* flips2, int64_t entries2, const int32_t* site_loc, int64_t n1, int64_t n2, int64_t w,
+                                    int64_t b, int64_t first_rank, int64_t count, uint64_t select, int64_t capacity, uint64_t* records_out,
+                                    int64_t* found_out) {
+    const char* who = "gf2_ft_gate_enumerate_list_host";
+    if (!eff) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (int rc = list_check_args(who, select, GF2_FT_CLASS_BITS, capacity, records_out, found_out)) return rc;
+    if (int rc = ft_gate_enumerate_check(who, eff, locations, ldr, nsteps, measure_mask, r1, keys1, flips1, entries1, r2, keys2, flips2, entries2, site_loc,
+                                         n1, n2, w, b, first_rank, count))
+        return rc;
+    const int trials = __builtin_popcountll(measure_mask);
+    const uint64_t mask[2] = {(1ull << r2) - 1, (1ull << r1) - 1};
+    *found_out = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    return gate_list_walk(who, eff, ldr, site_loc, n1, n2, w, b, first_rank, count, select, capacity, records_out, found_out, [&](const uint64_t* out) {
+        uint64_t unused[GF2_FT_FIELDS] = {0};
+        return ft_tally_sample(out, ldr, nsteps, measure_mask, trials, mask, tab, unused);
+    });
 }
 
 }  // extern "C"

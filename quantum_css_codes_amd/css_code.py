@@ -433,6 +433,13 @@ class CSSCode(QECC):
         from . import ec_noise
         return ec_noise.circuit_for(self, rounds, idle_data).gate_error_rates(num_samples, p1, p2, **options)
 
+    def error_correct_malignant_gate_faults(self, weight, rounds=1, idle_data=False, **options):
+        """The sets of exactly `weight` faulty gates of the cycle that are accepted and, by default, flip the logical state, listed
+        (ec_noise.ECCircuit.malignant_gate_faults; DESIGN.md section 5e "Malignant fault sets under gate-level faults"): a
+        montecarlo.GateFaultList for one CNOT count b, a montecarlo.GateFaultLists over every b by default."""
+        from . import ec_noise
+        return ec_noise.circuit_for(self, rounds, idle_data).malignant_gate_faults(weight, **options)
+
     def error_correct_gate_single_faults(self, rounds=1):
         """[build-defined]  The census of every single gate fault of the cycle, no GPU needed: ECCircuit.gate_single_faults."""
         from . import ec_noise
@@ -493,6 +500,13 @@ class CSSCode(QECC):
         ft_noise.FT_FIELDS plus 'samples'; wrong / accepted estimates the probability that the measured bit is wrong."""
         from . import ft_noise
         return ft_noise.program_for(self, ops).gate_error_rates(num_samples, p1, p2, **options)
+
+    def logical_program_malignant_gate_faults(self, ops, weight, **options):
+        """The sets of exactly `weight` faulty gates of the rewritten program `ops; MEASURE` that are accepted and, by default, make
+        the measured bit wrong, listed (ft_noise.FTProgram.malignant_gate_faults; DESIGN.md section 5e "Malignant fault sets under
+        gate-level faults"): a montecarlo.GateFaultList for one CNOT count b, a montecarlo.GateFaultLists over every b by default."""
+        from . import ft_noise
+        return ft_noise.program_for(self, ops).malignant_gate_faults(weight, **options)
 
     def logical_program_gate_single_faults(self, ops):
         """[build-defined]  The census of every single gate fault of the rewritten program, no GPU needed:

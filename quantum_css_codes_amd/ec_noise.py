@@ -365,6 +365,40 @@ class Gadget(object):
             counts.append(stack)
         return montecarlo.GateStrata(n1, n2, weights, counts, self.fields)
 
+    def malignant_gate_faults(self, weight, b=None, select=None, first_rank=0, count=None, max_configurations=None, host=False):
+        """The malignant fault sets under gate-level faults (DESIGN.md section 5e "Malignant fault sets under gate-level faults"):
+        enumerate_gate_range's walk of the configurations of exactly `weight` <= 4 faulty gates, b of them CNOTs, over ranks
+        [first_rank, first_rank + count) (default: everything), but the accepted ones whose class byte has a bit of `select`
+        (default `flip_mask`, as malignant_faults) are listed, not counted (gf2_{ec,ft}_gate_enumerate_list; host=True:
+        gf2_{ec,ft}_gate_enumerate_list_host, no GPU).  b=None lists the whole stratum of every b and takes no rank range.  Budget
+        as enumerate_gate_strata's; more than 2^26 records is a ValueError.  Returns a montecarlo.GateFaultList -- a
+        montecarlo.GateFaultLists over b for b=None -- which describe_gate_faults() puts into words."""
+        from . import montecarlo
+        site_loc, n1, n2, _ = self.gate_sites()
+        entry = self._entry("%s_gate_enumerate_list", host)
+        run = lambda w, k, first, n, sel, capacity: entry(site_loc, n1, n2, w, k, first, n, sel, capacity)
+        return montecarlo.malignant_gate_faults(n1, n2, weight, b, self.class_names, self.flip_mask if select is None else select,
+                                                first_rank, count, max_configurations, self.noun, run)
+
+    def describe_gate_faults(self, fault_list):
+        """Every record of a GateFaultList of this gadget (or of every list of a GateFaultLists, b ascending) as a tuple over its
+        picks of (gate index, gate (kind, a, b), qubits, Paulis): qubits the gate's operands -- one, or control then target -- and
+        Paulis one letter per operand, gate_single_faults' format ('XI', 'ZY', ...)."""
+        from . import montecarlo
+        if isinstance(fault_list, montecarlo.GateFaultLists):
+            return [record for part in fault_list for record in self.describe_gate_faults(part)]
+        _, n1, n2, site_gate = self.gate_sites()
+        if (fault_list.n1, fault_list.n2) != (n1, n2):
+            raise ValueError("the list is over %d + %d sites, the gadget has %d + %d" % (fault_list.n1, fault_list.n2, n1, n2))
+
+        def pick(g, kappa):
+            gate = tuple(int(v) for v in self.gadget.gates[g])
+            two = gate[0] == GATE_CNOT
+            return (g, gate, (gate[1], gate[2]) if two else (gate[1],), PAULI_OF_MASK[kappa & 3] + (PAULI_OF_MASK[kappa >> 2] if two else ''))
+
+        return [tuple(pick(g, k) for g, k in zip(gates, kinds))
+                for gates, kinds in zip(fault_list.gates(site_gate).tolist(), fault_list.kinds().tolist())]
+
     def gate_strata(self, strata, samples, seed=0, first_sample=0, host=False):
         """Sampled strata under gate-level faults (DESIGN.md section 5e "Sampled strata under gate-level faults"): stratum s = (a, b)
         draws samples [first_sample, first_sample + samples[s]) of exactly a faulty one-operand gates and b faulty CNOTs, a + b <= 16,

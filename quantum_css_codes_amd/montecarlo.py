@@ -889,6 +889,215 @@ def malignant_faults(nb, weight, class_names, select, first_rank, count, max_con
     return FaultList(nb, weight, records, class_names, [(first, count)])
 
 
+# ---- malignant fault sets under gate-level faults (DESIGN.md section 5e "Malignant fault sets under gate-level faults") ------------
+
+def _unrank_subsets(n, k, ranks):
+    """(len(ranks), k) int64: the subsets of [0, n) of the given ranks in the combinatorial number system, ascending along a row
+    (FaultList.locations' exact-binomial search)."""
+    out = np.zeros((len(ranks), k), dtype=np.int64)
+    left = np.array(ranks, dtype=np.uint64)
+    top = (1 << 63) - 1                                              # ranks lie below 2^63; larger binomials only need to compare above
+    for j in range(k, 0, -1):
+        table = np.array([min(math.comb(s, j), top) for s in range(n + 1)], dtype=np.uint64)
+        pick = np.searchsorted(table, left, side='right') - 1
+        out[:, j - 1] = pick
+        left = left - table[pick]
+    return out
+
+
+class GateFaultList(object):
+    """The listed configurations of faulty gates of a post-selected gadget (ec_noise.ECCircuit / ft_noise.FTProgram
+    .malignant_gate_faults): the accepted configurations of exactly `weight` faulty gates, `b` of them CNOTs, among `n1` one-operand
+    sites and `n2` CNOT sites whose class byte has a bit of the call's `select`, over the rank `ranges` ((first_rank, count) pairs,
+    ascending and disjoint, rank = r_s + C(n1, weight - b) r_c).  `records` is the (found, 2) uint64 array of include/gf2hip.h
+    "malignant fault sets under gate-level faults", sorted by (rank, kind masks); `class_names` names the bits of the class byte from
+    bit 0 ('accepted') up.  ranks, kind_masks (the 16 bits of nibbles) and classes are its columns.  The object and its arrays are
+    read-only."""
+
+    def __init__(self, n1, n2, weight, b, records, class_names, ranges=None):
+        records = np.array(records, dtype=np.uint64).reshape(-1, _native.FAULT_RECORD_WORDS)
+        n1, n2, weight, b = int(n1), int(n2), int(weight), int(b)
+        if n1 < 0 or n2 < 0 or not 0 <= b <= weight <= _native.GATE_ENUMERATE_MAX_WEIGHT:
+            raise ValueError("a gate-fault list has n1, n2 >= 0 sites and 0 <= b <= weight <= %d" % _native.GATE_ENUMERATE_MAX_WEIGHT)
+        class_names = tuple(class_names)
+        if not class_names or class_names[0] != 'accepted' or len(class_names) > 8:
+            raise ValueError("the class byte's bit 0 is 'accepted', and it has at most 8 bits")
+        a = weight - b
+        total = math.comb(n1, a) * math.comb(n2, b)
+        ranges = ((0, total),) if ranges is None else tuple((int(f), int(n)) for f, n in ranges)
+        if any(f < 0 or n < 0 or f + n > total for f, n in ranges) or any(p[0] + p[1] > q[0] for p, q in zip(ranges[:-1], ranges[1:])):
+            raise ValueError("the rank ranges of a gate-fault list are ascending, disjoint and within [0, C(n1, a) C(n2, b))")
+        ranks = records[:, 0].copy()
+        masks = (records[:, 1] & np.uint64(0xFFFF)).astype(np.int64)
+        classes = ((records[:, 1] >> np.uint64(32)) & np.uint64(0xFF)).astype(np.uint8)
+        if len(records):
+            ordered = (ranks[1:] > ranks[:-1]) | ((ranks[1:] == ranks[:-1]) & (masks[1:] > masks[:-1]))
+            covered = np.zeros(len(records), dtype=bool)
+            for f, n in ranges:
+                covered |= (ranks >= np.uint64(f)) & (ranks < np.uint64(f + n))
+            nibbles = (masks[:, None] >> (4 * np.arange(4))) & 15
+            legal = np.ones(len(records), dtype=bool)
+            for j in range(4):
+                top = 3 if j < a else 15 if j < weight else 0
+                legal &= (nibbles[:, j] <= top) & ((nibbles[:, j] >= 1) | (j >= weight))
+            if (not covered.all() or not legal.all() or not ordered.all() or (records[:, 1] & ~np.uint64(0xFF0000FFFF)).any()
+                    or not (classes & 1).all()):
+                raise ValueError("records must be accepted configurations of the ranges, sorted by (rank, kind masks), stray bits zero")
+        for arr in (records, ranks, masks, classes):
+            arr.setflags(write=False)
+        for name, value in (('n1', n1), ('n2', n2), ('weight', weight), ('b', b), ('records', records), ('class_names', class_names),
+                            ('ranges', ranges), ('ranks', ranks), ('kind_masks', masks), ('classes', classes)):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a GateFaultList is immutable")
+
+    def __len__(self):
+        return len(self.records)
+
+    def __add__(self, other):
+        """The list over both lists' ranges: `other`'s ranges lie above this one's; the records are concatenated in order."""
+        if not isinstance(other, GateFaultList):
+            return NotImplemented
+        if (self.n1, self.n2, self.weight, self.b, self.class_names) != (other.n1, other.n2, other.weight, other.b, other.class_names):
+            raise ValueError("only lists of one (n1, n2, weight, b) and one gadget's classes concatenate")
+        return GateFaultList(self.n1, self.n2, self.weight, self.b, np.concatenate((self.records, other.records)), self.class_names,
+                             self.ranges + other.ranges)
+
+    def _hit(self, mask):
+        return np.ones(len(self), dtype=bool) if mask is None else (self.classes & np.uint8(int(mask) & 0xFF)) != 0
+
+    def sites(self):
+        """(found, weight) int64: the sites of every record's picks -- the weight - b one-operand sites first, then the b CNOT sites
+        (n1 + their index among the CNOTs), each part ascending: the two parts of its rank unranked on the host."""
+        a = self.weight - self.b
+        c1 = np.uint64(math.comb(self.n1, a))
+        out = np.zeros((len(self), self.weight), dtype=np.int64)
+        if len(self):
+            out[:, :a] = _unrank_subsets(self.n1, a, self.ranks % c1)
+            out[:, a:] = self.n1 + _unrank_subsets(self.n2, self.b, self.ranks // c1)
+        return out
+
+    def gates(self, site_gate):
+        """sites() mapped to gate indices by `site_gate` (Gadget.gate_sites()[3])."""
+        site_gate = np.asarray(site_gate, dtype=np.int64).reshape(-1)
+        if len(site_gate) != self.n1 + self.n2:
+            raise ValueError("site_gate has one gate index per site: %d, not %d" % (self.n1 + self.n2, len(site_gate)))
+        return site_gate[self.sites()]
+
+    def kinds(self):
+        """(found, weight) uint8: the kind mask kappa of every pick, in the order of sites(): 1 X, 2 Z, 3 Y on a one-operand gate;
+        on a CNOT bits 0, 1 the control's X and Z components and bits 2, 3 the target's."""
+        return ((self.kind_masks[:, None] >> (4 * np.arange(self.weight, dtype=np.int64))) & 15).astype(np.uint8).reshape(len(self), self.weight)
+
+    def two_operand(self):
+        """(found,) int64: c, the number of CNOT picks of every record whose kind acts on both operands."""
+        kappa = self.kinds()[:, self.weight - self.b:]
+        return (((kappa & 3) != 0) & ((kappa >> 2) != 0)).sum(axis=1).astype(np.int64)
+
+    def counts(self, mask=None):
+        """(b + 1,) int64 [c]: the records whose class byte has a bit of `mask` (None: all) per number c of two-operand kinds --
+        GateStrata.counts[weight][b][:, field] of the matching indicator field when the list is whole."""
+        return np.bincount(self.two_operand()[self._hit(mask)], minlength=self.b + 1).astype(np.int64)
+
+    def gate_counts(self, site_gate, mask=None):
+        """(gates,) int64: in how many of the listed sets (with a class bit of `mask`; None: all) each gate takes part."""
+        gates = self.gates(site_gate)[self._hit(mask)]
+        return np.bincount(gates.reshape(-1), minlength=int(np.max(site_gate, initial=-1)) + 1).astype(np.int64)
+
+    def coefficient(self, odds, mask=None):
+        """sum over the records (with a class bit of `mask`) of x^(weight - b) y1^(b - c) y2^c at the odds (x, y1, y2) of
+        GateStrata.depolarising_odds / independent_odds (fractions.Fraction odds give an exact result): the list's term of
+        GateStrata.joint without its factor Z."""
+        x, y1, y2 = odds
+        return sum((int(n) * x**(self.weight - self.b) * y1**(self.b - c) * y2**c for c, n in enumerate(self.counts(mask)) if n), 0 * x)
+
+
+class GateFaultLists(object):
+    """The whole strata of one weight listed for every CNOT count: `lists[b]`, b = 0 .. weight, a GateFaultList each (what
+    malignant_gate_faults returns for b=None).  Indexing and iteration go over b; counts, gate_counts and coefficient are the
+    GateFaultList's, stacked or summed over b."""
+
+    def __init__(self, lists):
+        lists = tuple(lists)
+        if not lists or any(not isinstance(l, GateFaultList) for l in lists):
+            raise ValueError("one GateFaultList per CNOT count")
+        head = lists[0]
+        if len(lists) != head.weight + 1 or any((l.n1, l.n2, l.weight, l.b, l.class_names) != (head.n1, head.n2, head.weight, b, head.class_names)
+                                                for b, l in enumerate(lists)):
+            raise ValueError("the lists are those of b = 0 .. weight of one (n1, n2, weight) and one gadget's classes")
+        self.lists = lists
+        self.n1, self.n2, self.weight, self.class_names = head.n1, head.n2, head.weight, head.class_names
+
+    def __getitem__(self, b):
+        return self.lists[b]
+
+    def __iter__(self):
+        return iter(self.lists)
+
+    def __len__(self):
+        """The records of all the lists."""
+        return sum(len(l) for l in self.lists)
+
+    def counts(self, mask=None):
+        """(weight + 1, weight + 1) int64 [b][c]: GateStrata.counts[weight][:, :, field] of the matching indicator field."""
+        out = np.zeros((self.weight + 1, self.weight + 1), dtype=np.int64)
+        for b, l in enumerate(self.lists):
+            out[b, :b + 1] = l.counts(mask)
+        return out
+
+    def gate_counts(self, site_gate, mask=None):
+        return sum(l.gate_counts(site_gate, mask) for l in self.lists)
+
+    def coefficient(self, odds, mask=None):
+        return sum((l.coefficient(odds, mask) for l in self.lists), 0 * odds[0])
+
+
+def malignant_gate_faults(n1, n2, weight, b, class_names, select, first_rank, count, max_configurations, what, run):
+    """What ECCircuit.malignant_gate_faults and FTProgram.malignant_gate_faults share.  The request is checked as the exact gate
+    strata's (circuit_noise.gate_enumerate_request's limits and budget, the size named); b=None lists the whole stratum of every b and
+    takes no rank range.  run(w, b, first, count, select, capacity) -> (found, records or None) is called with
+    FAULT_LIST_FIRST_CAPACITY records and, if they do not hold the list, once more with exactly `found`.  Returns a GateFaultList, or
+    a GateFaultLists for b=None."""
+    from . import circuit_noise
+    weight = int(weight)
+    if not 0 <= weight <= _native.GATE_ENUMERATE_MAX_WEIGHT:
+        raise ValueError("a gate-fault stratum's weight lies in [0, %d]" % _native.GATE_ENUMERATE_MAX_WEIGHT)
+    if not 1 <= n1 + 2 * n2 <= circuit_noise.MAX_LOCATIONS:
+        raise ValueError("the enumeration needs 1 <= L <= %d (2^20) fault locations, the %s has %d" % (circuit_noise.MAX_LOCATIONS, what, n1 + 2 * n2))
+    select = int(select)
+    if select <= 0 or select >> len(class_names):
+        raise ValueError("select is a non-empty subset of the class bits 0x%x (%s)" % ((1 << len(class_names)) - 1, ', '.join(class_names)))
+    subsets = lambda k: math.comb(n1, weight - k) * math.comb(n2, k)
+    if b is None:
+        if not (first_rank is None or int(first_rank) == 0) or count is not None:
+            raise ValueError("b=None lists whole strata: a rank range needs one b")
+        requests = [(k, 0, subsets(k)) for k in range(weight + 1)]
+    else:
+        b = int(b)
+        if not 0 <= b <= weight:
+            raise ValueError("%d CNOT picks outside [0, weight = %d]" % (b, weight))
+        first = 0 if first_rank is None else int(first_rank)
+        n = subsets(b) - first if count is None else int(count)
+        if first < 0 or n < 0 or first + n > subsets(b):
+            raise ValueError("ranks [%d, %d + %d) leave the range [0, C(%d, %d) C(%d, %d) = %d)" % (first, first, n, n1, weight - b, n2, b, subsets(b)))
+        requests = [(b, first, n)]
+    size = sum(n * 3**(weight - k) * 15**k for k, _, n in requests)
+    budget = circuit_noise.ENUMERATE_BUDGET if max_configurations is None else int(max_configurations)
+    if size > budget:
+        raise ValueError("%d gate-fault configurations to enumerate, more than max_configurations = %d" % (size, budget))
+    lists = []
+    for k, first, n in requests:
+        found, records = run(weight, k, first, n, select, FAULT_LIST_FIRST_CAPACITY)
+        if records is None:
+            if found > FAULT_LIST_MAX_RECORDS:
+                raise ValueError("%d fault configurations to list, more than %d (2^26): choose a narrower select or a smaller rank range"
+                                 % (found, FAULT_LIST_MAX_RECORDS))
+            found, records = run(weight, k, first, n, select, found)
+        lists.append(GateFaultList(n1, n2, weight, k, records, class_names, [(first, n)]))
+    return GateFaultLists(lists) if b is None else lists[0]
+
+
 # ---- sampled strata of a post-selected gadget (DESIGN.md "Sampled strata of the cycle", "Sampled strata of the measurement") --------
 
 # MergedPostSelectedStrata.rate's result: the conditional rate lies in [lower, upper] up to the statistical error `stderr` of `estimate`.
