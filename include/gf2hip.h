@@ -944,6 +944,53 @@ int gf2_mc_retry_decode(gf2_ctx* ctx, const gf2_retry* retry, int64_t r1, const 
                         int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed, int64_t first_sample,
                         int64_t count, double p_x, double p_y, double p_z, int64_t max_attempts, uint64_t* counts_out);
 
+/* ---- repeat-until-success with waiting faults on the data block ------------------------------------------
+ * [build-defined, DESIGN.md section 5d "Repeat-until-success with waiting faults"]  The retried walk above, in which the data block
+ * also pays for the retries: a retried region g has W_g WAIT ROWS, the (local, tail) words of an X and of a Z fault on a qubit that
+ * waits while the region is prepared, and every attempt actually made of the region, the failed ones included, draws each of them
+ * with the memory error rates (q_x, q_y, q_z).  wait_count holds W per region of every type, in type_regions' order; wait_eff holds
+ * the rows region by region, four uint64 each: X local, X tail, Z local, Z tail.  Besides the rules above, GF2_E_ARG naming the rule:
+ * a wait count outside [0, 512], a wait count above 0 on a region that is not retried, more than GF2_RETRY_MAX_SIZES distinct
+ * non-zero wait counts, bad q rates.
+ *
+ * Everything of the definition above stands.  In addition, for region g with W_g > 0 and every attempt a = 0, 1, ... made of it:
+ *   kw = segment_draw(ks, 2^33 + g),  kwa = mix64(kw + G (a + 1)),  d = segment_draw(kwa, 0),
+ * K from the inverse binomial CDF table of (T_any(q), W_g), the picks, Floyd's rule and the kinds error_draw's with q's thresholds.
+ * The picked rows' words are XORed into the block's local and tail words for every attempt made: the data is never reset.  Neither
+ * the region's own draw nor its key changes, so the attempts of every preparation are those of the walk above.
+ * Layout of a sample, nsteps + F + 2 words: [steps] [F flag words] [attempts] [wait faults: those drawn over all attempts of the
+ * sample, up to where an exhausted sample stopped]. */
+#define GF2_RETRY_WAIT_FIELDS 15                /* the GF2_RETRY_FIELDS, then the wait faults of all samples of the call */
+typedef struct gf2_retry_wait gf2_retry_wait;
+
+/* The words on the host, serial, no GPU needed; words_out (ldw >= nsteps + F + 2) and attempts_out as gf2_retry_words_host's.
+ * gf2_stream_tally_host on the first nsteps + F words completes the statement. */
+int gf2_retry_wait_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                              const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                              const int64_t* type_nregions, const uint64_t* wait_eff, const int64_t* wait_count, uint64_t seed,
+                              int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, double q_x, double q_y, double q_z,
+                              int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out);
+
+/* A sequence, its regions and their wait rows on the device.  Argument rules as gf2_retry_wait_words_host's (max_attempts, the
+ * rates and the range belong to the calls).  Destroyed by gf2_retry_wait_destroy. */
+int gf2_retry_wait_create(gf2_ctx* ctx, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                          const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                          const int64_t* type_nregions, const uint64_t* wait_eff, const int64_t* wait_count, gf2_retry_wait** retry_out);
+int gf2_retry_wait_destroy(gf2_ctx* ctx, gf2_retry_wait* retry);
+
+/* The words of samples first_sample .. first_sample + count - 1 in device memory, ldo >= nsteps + F + 2 words per sample; words past
+ * those are left as they were.  out_dev: any 8-byte-aligned address. */
+int gf2_retry_wait_outcomes_dev(gf2_ctx* ctx, const gf2_retry_wait* retry, uint64_t seed, int64_t first_sample, int64_t count, double p_x,
+                                double p_y, double p_z, double q_x, double q_y, double q_z, int64_t max_attempts, uint64_t* out_dev,
+                                int64_t ldo);
+
+/* The tally of those samples on the device, no word stored: counts_out[GF2_RETRY_WAIT_FIELDS] on the host, gf2_mc_retry_decode's
+ * fourteen and the wait faults of all samples of the call.  Counts of sample ranges add. */
+int gf2_mc_retry_wait_decode(gf2_ctx* ctx, const gf2_retry_wait* retry, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                             int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed,
+                             int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, double q_x, double q_y, double q_z,
+                             int64_t max_attempts, uint64_t* counts_out);
+
 /* ---- repeat-until-success under gate-level faults ------------------------------------------------------
  * [build-defined, DESIGN.md section 5d "Repeat-until-success under gate-level faults"]  The retried walk above with the fault model
  * of "direct Monte-Carlo ... under gate-level faults": every one-operand gate of a region fails with probability p_1 and one of 3

@@ -27,6 +27,7 @@ FT_FIELDS_COUNT, FT_MAX_LDR = 7, 16
 STREAM_FIELDS_COUNT, STREAM_MAX_TYPES, STREAM_MAX_OVERLAP = 12, 64, 8
 STREAM_NONE, STREAM_EC, STREAM_MEASURE, STREAM_FINAL = 0, 1, 2, 3
 RETRY_FIELDS_COUNT, RETRY_MAX_ATTEMPTS, RETRY_MAX_SIZES = 14, 65536, 16
+RETRY_WAIT_FIELDS_COUNT, RETRY_WAIT_MAX_ROWS = 15, 512
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 ENUMERATE_MAX_WEIGHT = 8
@@ -203,6 +204,13 @@ SIGNATURES = {
     "gf2_retry_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_i64, _p, _c_i64],
     "gf2_mc_retry_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
                             ctypes.c_double, _c_i64, _p],
+    "gf2_retry_wait_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _p, _c_u64, _c_i64, _c_i64] + [ctypes.c_double] * 6 +
+                                 [_c_i64, _p, _c_i64, _p],
+    "gf2_retry_wait_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _p, _pp],
+    "gf2_retry_wait_destroy": [_p, _p],
+    "gf2_retry_wait_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64] + [ctypes.c_double] * 6 + [_c_i64, _p, _c_i64],
+    "gf2_mc_retry_wait_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64] + [ctypes.c_double] * 6 +
+                                [_c_i64, _p],
     "gf2_retry_gate_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
                                   _c_i64, _p, _c_i64, _p],
     "gf2_retry_gate_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _p, _pp],
@@ -426,8 +434,9 @@ def circuit_effects_timed(gates, n, rows_x, rows_z, row_time, ldr=None):
 Rule = collections.namedtuple("Rule", "name fields head")
 EC_RULE = Rule("ec", EC_FIELDS_COUNT, lambda rounds: (int(rounds),))
 FT_RULE = Rule("ft", FT_FIELDS_COUNT, lambda nsteps, measure_mask: (int(nsteps), int(measure_mask) & 0xFFFFFFFFFFFFFFFF))
-CIRCUIT_RULE, STREAM_RULE, RETRY_RULE = (Rule(name, fields, lambda: ()) for name, fields in
-                                         (("circuit", 5), ("stream", STREAM_FIELDS_COUNT), ("retry", RETRY_FIELDS_COUNT)))
+CIRCUIT_RULE, STREAM_RULE, RETRY_RULE, RETRY_WAIT_RULE = (Rule(name, fields, lambda: ()) for name, fields in
+                                                          (("circuit", 5), ("stream", STREAM_FIELDS_COUNT), ("retry", RETRY_FIELDS_COUNT),
+                                                           ("retry_wait", RETRY_WAIT_FIELDS_COUNT)))
 
 
 def _enumerate_tables(keys1, flips1, keys2, flips2, null_flips=False):
@@ -550,6 +559,31 @@ def retry_words_host(type_eff, type_locations, type_flags, block_type, block_kin
     attempts = np.zeros((max(1, count), max(1, int(preparations))), dtype=np.uint32)
     check(lib().gf2_retry_words_host(*seq, *regions, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p_x), float(p_y), float(p_z),
                                      int(max_attempts), _ptr(out), int(ldw), _ptr(attempts)))
+    return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
+
+
+def _retry_waits(wait_eff, wait_count, regions):
+    """The wait rows of a sequence's regions as the gf2_retry_wait_* entry points take them, and their pointer arguments."""
+    counts = np.ascontiguousarray(wait_count, dtype=np.int64).reshape(-1)
+    eff = np.ascontiguousarray(wait_eff, dtype="<u8").reshape(-1, 2, 2)
+    if len(counts) != regions or int(counts.clip(0).sum()) != len(eff):
+        raise ValueError("one wait count per region, wait_eff (rows, 2, 2) as long as their sum")
+    return (eff, counts), (_ptr(eff) if len(eff) else None, _ptr(counts) if len(counts) else None)
+
+
+def retry_wait_words_host(type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, wait_eff, wait_count, seed,
+                          first, count, p_x, p_y, p_z, q_x, q_y, q_z, max_attempts, ldw, preparations):
+    """gf2_retry_wait_words_host (host code, no GPU): the (count, ldw) words [steps] [flag words] [attempts] [wait faults] of samples
+    [first, first + count) of the repeat-until-success sampler with waiting faults and the (count, preparations) uint32 attempts
+    of every retried region."""
+    keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+    keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+    keep_waits, waits = _retry_waits(wait_eff, wait_count, len(keep_regions[0]))
+    count = int(count)
+    out = np.zeros((max(1, count), max(1, int(ldw))), dtype="<u8")
+    attempts = np.zeros((max(1, count), max(1, int(preparations))), dtype=np.uint32)
+    check(lib().gf2_retry_wait_words_host(*seq, *regions, *waits, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p_x), float(p_y),
+                                          float(p_z), float(q_x), float(q_y), float(q_z), int(max_attempts), _ptr(out), int(ldw), _ptr(attempts)))
     return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
 
 
@@ -974,6 +1008,21 @@ class Retry(_Handle):
 
 
 
+class RetryWait(_Handle):
+    """A block sequence, its regions and their wait rows on the device (gf2_retry_wait_create)."""
+    _destroy = "gf2_retry_wait_destroy"
+
+    def __init__(self, ctx, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, wait_eff, wait_count):
+        self.ctx = ctx
+        keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+        keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+        keep_waits, waits = _retry_waits(wait_eff, wait_count, len(keep_regions[0]))
+        out = ctypes.c_void_p()
+        check(lib().gf2_retry_wait_create(ctx.handle, *seq, *regions, *waits, ctypes.byref(out)))
+        self.handle = out.value
+
+
+
 class RetryGate(_Handle):
     """A block sequence, its regions and their sites on the device (gf2_retry_gate_create)."""
     _destroy = "gf2_retry_gate_destroy"
@@ -1011,8 +1060,8 @@ class Context(object):
 
     def outcomes(self, fill, obj, seed, first, count, p_x, p_y, p_z, ldo, *more):
         """The (count, ldo) uint64 words of samples [first, first + count) that `fill` -- this context's circuit_outcomes_dev,
-        ft_outcomes_dev, stream_outcomes_dev or retry_outcomes_dev (more: its max_attempts) -- writes for `obj`, through a device
-        buffer that is freed whether the call succeeds or raises."""
+        ft_outcomes_dev, stream_outcomes_dev, retry_outcomes_dev (more: its max_attempts) or retry_wait_outcomes_dev (more: the q rates
+        and max_attempts) -- writes for `obj`, through a device buffer that is freed whether the call succeeds or raises."""
         count = int(count)
         buf = self.alloc(max(1, count) * ldo * 8)
         try:
@@ -1314,6 +1363,18 @@ class Context(object):
         """gf2_mc_retry_decode: the fourteen counts of the repeat-until-success tally over samples [first, first + count)."""
         return _decode(lib().gf2_mc_retry_decode, RETRY_RULE, (self.handle, retry.handle), (), (r1, keys1, flips1, r2, keys2, flips2),
                        seed, first, count, p_x, p_y, p_z, int(max_attempts))
+
+    def retry_wait_create(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, wait_eff, wait_count):
+        return RetryWait(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, wait_eff, wait_count)
+
+    def retry_wait_outcomes_dev(self, retry, seed, first, count, p_x, p_y, p_z, q_x, q_y, q_z, max_attempts, out_buf, ldo):
+        check(lib().gf2_retry_wait_outcomes_dev(self.handle, retry.handle, seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, float(q_x),
+                                                float(q_y), float(q_z), int(max_attempts), out_buf.ptr, ldo))
+
+    def mc_retry_wait_decode(self, retry, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z, q_x, q_y, q_z, max_attempts):
+        """gf2_mc_retry_wait_decode: the fifteen counts of the repeat-until-success tally with waiting faults."""
+        return _decode(lib().gf2_mc_retry_wait_decode, RETRY_WAIT_RULE, (self.handle, retry.handle), (), (r1, keys1, flips1, r2, keys2, flips2),
+                       seed, first, count, p_x, p_y, p_z, float(q_x), float(q_y), float(q_z), int(max_attempts))
 
     def retry_gate_create(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc, site_regions):
         return RetryGate(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc, site_regions)

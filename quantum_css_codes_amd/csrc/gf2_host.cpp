@@ -1662,44 +1662,144 @@ int gf2_retry_check_range(const char* who, double p_x, double p_y, double p_z, i
     return GF2_OK;
 }
 
-extern "C" {
+// ---- ... with waiting faults on the data block (include/gf2hip.h, DESIGN.md section 5d "Repeat-until-success with waiting faults") ----
+#include "gf2_retry_wait_plan.h"
+
+int gf2_retry_wait_plan(const char* who, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                        const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                        const int64_t* type_nregions, const uint64_t* wait_eff, const int64_t* wait_count, int64_t max_attempts,
+                        StreamPlan* plan, RetryPlan* retry, RetryWaitPlan* wait) {
+    if (int rc = gf2_retry_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
+                                max_attempts, plan, retry))
+        return rc;
+    if (!wait_count || !wait) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    const int64_t total = retry->type_first[(size_t)ntypes];
+    std::vector<int32_t> sizes;                                                  // a set of at most GF2_RETRY_MAX_SIZES + 1 values
+    try {
+        wait->first.assign((size_t)total, 0);
+        wait->count.assign((size_t)total, 0);
+        wait->size.assign((size_t)total, -1);
+        sizes.reserve(GF2_RETRY_MAX_SIZES + 1);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    int64_t rows = 0;
+    for (int64_t t = 0; t < ntypes; ++t)
+        for (int64_t q = retry->type_first[(size_t)t]; q < retry->type_first[(size_t)t + 1]; ++q) {
+            const int64_t r = q - retry->type_first[(size_t)t], w = wait_count[q];
+            if (w < 0 || w > GF2_RETRY_WAIT_MAX_ROWS)
+                GF2_FAIL(GF2_E_ARG, "%s: region %lld of block type %lld has %lld wait rows, a region holds 0 <= wait rows <= %d (one segment)", who,
+                         (long long)r, (long long)t, (long long)w, GF2_RETRY_WAIT_MAX_ROWS);
+            if (w > 0 && !retry->retried[(size_t)q])
+                GF2_FAIL(GF2_E_ARG, "%s: region %lld of block type %lld is not retried but has %lld wait rows", who, (long long)r, (long long)t,
+                         (long long)w);
+            wait->first[(size_t)q] = rows;
+            wait->count[(size_t)q] = (int32_t)w;
+            rows += w;
+            if (w > 0 && std::find(sizes.begin(), sizes.end(), (int32_t)w) == sizes.end() && sizes.size() <= (size_t)GF2_RETRY_MAX_SIZES)
+                sizes.push_back((int32_t)w);
+        }
+    if (sizes.size() > (size_t)GF2_RETRY_MAX_SIZES)
+        GF2_FAIL(GF2_E_ARG, "%s: the regions have more than GF2_RETRY_MAX_SIZES = %d distinct wait sizes, one inverse-CDF table each", who,
+                 GF2_RETRY_MAX_SIZES);
+    if (rows > 0 && !wait_eff) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    std::sort(sizes.begin(), sizes.end());
+    wait->sizes = sizes;
+    wait->rows = rows;
+    for (int64_t q = 0; q < total; ++q)
+        if (wait->count[(size_t)q] > 0)
+            wait->size[(size_t)q] = (int32_t)(std::find(sizes.begin(), sizes.end(), wait->count[(size_t)q]) - sizes.begin());
+    wait->locations = 0;
+    for (int64_t b = 0; b < nblocks; ++b) {                                      // the wait rows act on their block's local and tail words
+        if (block_kind[b] == GF2_STREAM_FINAL) continue;
+        const int64_t t = block_type[b];
+        for (int64_t q = retry->type_first[(size_t)t]; q < retry->type_first[(size_t)t + 1]; ++q) {
+            wait->locations += wait->count[(size_t)q];
+            const uint64_t* e = wait_eff + (size_t)wait->first[(size_t)q] * 4;
+            for (int64_t l = 0; l < wait->count[(size_t)q]; ++l) {
+                plan->any_local[block_kind[b]] |= e[4 * l] | e[4 * l + 2];
+                plan->any_tail |= e[4 * l + 1] | e[4 * l + 3];
+            }
+        }
+    }
+    return GF2_OK;
+}
+
+int gf2_retry_wait_check_rates(const char* who, double q_x, double q_y, double q_z) {
+    if (!(q_x >= 0.0) || !(q_y >= 0.0) || !(q_z >= 0.0) || q_x + q_y + q_z > 1.0 + 1e-12)
+        GF2_FAIL(GF2_E_ARG, "%s: the waiting probabilities must be non-negative and sum to at most 1", who);
+    return GF2_OK;
+}
+
+namespace {
+// One sampler segment of nb rows under the draw d: K from the inverse-CDF table, the picks by Floyd's rule, their kinds by (t_1, t_2);
+// every pick XORs its row's X and / or Z component, `width` words each, into acc.  Returns K.
+int retry_segment_host(uint64_t d, int nb, const uint64_t* table, uint64_t t_1, uint64_t t_2, const uint64_t* rows, int width, uint64_t* acc) {
+    const uint64_t golden = 0x9E3779B97F4A7C15ull;
+    const uint64_t u = d >> 32;
+    int K = 0;
+    while (K < nb && u >= table[K]) K += 1;
+    uint64_t taken[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < K; ++k) {
+        const uint64_t v = host_mix64(d + golden * (uint64_t)(k + 1));
+        const uint64_t j = (uint64_t)(nb - K + k);
+        const uint64_t pick = ((v >> 32) * (j + 1)) >> 32;                       // Floyd: a candidate in [0, j]
+        const uint64_t pos = ((taken[pick >> 6] >> (pick & 63)) & 1ull) ? j : pick;
+        taken[pos >> 6] |= 1ull << (pos & 63);
+        const uint64_t c = v & 0xFFFFFFFFull;
+        const int kind = (c < t_2 ? 1 : 0) | (c >= t_1 ? 2 : 0);
+        const uint64_t* e = rows + (size_t)pos * 2 * width;
+        for (int comp = 0; comp < 2; ++comp)
+            if (kind >> comp & 1)
+                for (int q = 0; q < width; ++q) acc[q] ^= e[width * comp + q];
+    }
+    return K;
+}
+
+struct RetryWaitDraw {                                                           // the waiting faults of a call
+    const RetryWaitPlan* plan;
+    const uint64_t* eff;
+    double q_x, q_y, q_z;
+};
 
 // The definition of gf2_retry_outcomes_dev's words (DESIGN.md section 5d "Repeat-until-success"), serial: the blocks in order, the
 // regions of a block in order, a retried region redrawn under the key of (region, attempt) until its flags are zero.  The draw of a
-// segment is gf2_gate_outcomes_host's with the location sampler's kinds; the block rule is gf2_stream_words_host's.
-int gf2_retry_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
-                         const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
-                         const int64_t* type_nregions, uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z,
-                         int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out) {
-    const char* who = "gf2_retry_words_host";
-    StreamPlan plan;
-    RetryPlan retry;
-    if (int rc = gf2_retry_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
-                                max_attempts, &plan, &retry))
-        return rc;
-    if (int rc = gf2_retry_check_range(who, p_x, p_y, p_z, first_sample, count)) return rc;
-    const int64_t ldr = plan.nsteps + plan.flag_words + 1;
-    if (ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the sequence's nsteps + F + 1 = %lld words", who, (long long)ldr);
+// segment is gf2_gate_outcomes_host's with the location sampler's kinds; the block rule is gf2_stream_words_host's.  With `waits`
+// (gf2_retry_wait_outcomes_dev's words, "Repeat-until-success with waiting faults") every attempt made of a region with wait rows
+// also draws that region's waiting faults, under a key of its own, into the block's local and tail words, which no retry clears;
+// a sample then has one word more, the waiting faults it drew.
+int retry_walk_host(const char* who, const StreamPlan& plan, const RetryPlan& retry, const RetryWaitDraw* waits, const uint64_t* type_eff,
+                    const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, uint64_t seed, int64_t first_sample, int64_t count,
+                    double p_x, double p_y, double p_z, int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out) {
+    const int64_t ldr = plan.nsteps + plan.flag_words + (waits ? 2 : 1);
+    if (ldw < ldr)
+        GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the sequence's nsteps + F + %d = %lld words", who, waits ? 2 : 1, (long long)ldr);
     if (count == 0) return GF2_OK;
     if (!words_out) GF2_FAIL(GF2_E_ARG, "%s: null buffer", who);
     const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
     const int SEG = 512;
     const double p_t = p_x + p_y + p_z, p_xy = p_x + p_y;
     const uint64_t t_any = host_quantise(p_t), t_1 = p_t > 0.0 ? host_quantise(p_x / p_t) : 0, t_2 = p_t > 0.0 ? host_quantise(p_xy / p_t) : 0;
-    std::vector<uint64_t> cdf;                                                   // [size][SEG + 1]
+    const double q_t = waits ? waits->q_x + waits->q_y + waits->q_z : 0.0;
+    const uint64_t w_any = host_quantise(q_t), w_1 = q_t > 0.0 ? host_quantise(waits->q_x / q_t) : 0,
+                   w_2 = q_t > 0.0 ? host_quantise((waits->q_x + waits->q_y) / q_t) : 0;
+    const size_t wait_sizes = waits ? waits->plan->sizes.size() : 0;
+    std::vector<uint64_t> cdf, wait_cdf;                                         // [size][SEG + 1]
     try {
         cdf.resize(retry.sizes.size() * (SEG + 1));
+        wait_cdf.resize(wait_sizes * (SEG + 1));
     } catch (const std::bad_alloc&) {
         GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
     }
     for (size_t k = 0; k < retry.sizes.size(); ++k) host_binomial_cdf_table(t_any, retry.sizes[k], &cdf[k * (SEG + 1)]);
+    for (size_t k = 0; k < wait_sizes; ++k) host_binomial_cdf_table(w_any, waits->plan->sizes[k], &wait_cdf[k * (SEG + 1)]);
     for (int64_t i = 0; i < count; ++i) {
         uint64_t* const out = words_out + i * ldw;
         for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
         uint32_t* const tries = attempts_out ? attempts_out + i * retry.preparations : nullptr;
         for (int64_t q = 0; tries && q < retry.preparations; ++q) tries[q] = 0;
         const uint64_t ks = host_mix64(seed + golden * ((uint64_t)(first_sample + i) + 1));
-        uint64_t T = 0, attempts = 0;
+        uint64_t T = 0, attempts = 0, wait_faults = 0;
         int64_t g = 0, prep = 0;
         bool exhausted = false;
         for (int64_t b = 0; b < nblocks && !exhausted; ++b) {
@@ -1710,7 +1810,9 @@ int gf2_retry_words_host(const uint64_t* type_eff, const int64_t* type_locations
                     const int64_t rows = plan.type_offset[(size_t)t] + retry.first[(size_t)r], m = retry.count[(size_t)r];
                     const int64_t nseg = (m + SEG - 1) / SEG, limit = retry.retried[(size_t)r] ? max_attempts : 1;
                     const uint64_t kr = host_mix64(ks + stream * (GF2_RETRY_SLOT_BASE + (uint64_t)g + 1));
-                    uint64_t acc[3] = {0, 0, 0};
+                    const int nw = waits ? waits->plan->count[(size_t)r] : 0;
+                    const uint64_t kw = host_mix64(ks + stream * (GF2_RETRY_WAIT_SLOT_BASE + (uint64_t)g + 1));
+                    uint64_t acc[3] = {0, 0, 0}, waited[2] = {0, 0};
                     int64_t a = 0;
                     do {
                         const uint64_t ka = host_mix64(kr + golden * ((uint64_t)a + 1));
@@ -1719,24 +1821,14 @@ int gf2_retry_words_host(const uint64_t* type_eff, const int64_t* type_locations
                             const bool last = s == nseg - 1;
                             const int nb = last ? (int)(m - SEG * s) : SEG;
                             const uint64_t* table = &cdf[(size_t)(last ? retry.last_size[(size_t)r] : retry.full_size) * (SEG + 1)];
-                            const uint64_t d = host_mix64(ka + stream * ((uint64_t)s + 1));
-                            const uint64_t u = d >> 32;
-                            int K = 0;
-                            while (K < nb && u >= table[K]) K += 1;
-                            uint64_t taken[SEG / 64] = {0, 0, 0, 0, 0, 0, 0, 0};
-                            for (int k = 0; k < K; ++k) {
-                                const uint64_t v = host_mix64(d + golden * (uint64_t)(k + 1));
-                                const uint64_t j = (uint64_t)(nb - K + k);
-                                const uint64_t pick = ((v >> 32) * (j + 1)) >> 32;   // Floyd: a candidate in [0, j]
-                                const uint64_t pos = ((taken[pick >> 6] >> (pick & 63)) & 1ull) ? j : pick;
-                                taken[pos >> 6] |= 1ull << (pos & 63);
-                                const uint64_t c = v & 0xFFFFFFFFull;
-                                const int kind = (c < t_2 ? 1 : 0) | (c >= t_1 ? 2 : 0);
-                                const uint64_t* e = type_eff + (size_t)(rows + SEG * s + (int64_t)pos) * 6;
-                                for (int comp = 0; comp < 2; ++comp)
-                                    if (kind >> comp & 1)
-                                        for (int q = 0; q < 3; ++q) acc[q] ^= e[3 * comp + q];
-                            }
+                            (void)retry_segment_host(host_mix64(ka + stream * ((uint64_t)s + 1)), nb, table, t_1, t_2, type_eff + (size_t)(rows + SEG * s) * 6,
+                                                     3, acc);
+                        }
+                        if (nw > 0) {                                            // the data waits through this attempt, passed or not
+                            const uint64_t kwa = host_mix64(kw + golden * ((uint64_t)a + 1));
+                            wait_faults += (uint64_t)retry_segment_host(host_mix64(kwa + stream), nw,
+                                                                        &wait_cdf[(size_t)waits->plan->size[(size_t)r] * (SEG + 1)], w_1, w_2,
+                                                                        waits->eff + (size_t)waits->plan->first[(size_t)r] * 4, 2, waited);
                         }
                         a += 1;
                     } while (acc[2] != 0 && a < limit);
@@ -1751,7 +1843,7 @@ int gf2_retry_words_host(const uint64_t* type_eff, const int64_t* type_locations
                         out[plan.nsteps + (row >> 6)] |= acc[2] << (row & 63);
                         if ((row & 63) && (acc[2] >> (64 - (row & 63)))) out[plan.nsteps + (row >> 6) + 1] |= acc[2] >> (64 - (row & 63));
                     }
-                    local ^= acc[0], tail ^= acc[1];
+                    local ^= acc[0] ^ waited[0], tail ^= acc[1] ^ waited[1];
                 }
             }
             if (exhausted) break;
@@ -1759,8 +1851,46 @@ int gf2_retry_words_host(const uint64_t* type_eff, const int64_t* type_locations
             T ^= tail;
         }
         out[plan.nsteps + plan.flag_words] = attempts;
+        if (waits) out[plan.nsteps + plan.flag_words + 1] = wait_faults;
     }
     return GF2_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gf2_retry_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                         const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                         const int64_t* type_nregions, uint64_t seed, int64_t first_sample, int64_t count, double p_x, double p_y, double p_z,
+                         int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out) {
+    const char* who = "gf2_retry_words_host";
+    StreamPlan plan;
+    RetryPlan retry;
+    if (int rc = gf2_retry_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
+                                max_attempts, &plan, &retry))
+        return rc;
+    if (int rc = gf2_retry_check_range(who, p_x, p_y, p_z, first_sample, count)) return rc;
+    return retry_walk_host(who, plan, retry, nullptr, type_eff, block_type, block_kind, nblocks, seed, first_sample, count, p_x, p_y, p_z, max_attempts,
+                           words_out, ldw, attempts_out);
+}
+
+int gf2_retry_wait_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                              const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                              const int64_t* type_nregions, const uint64_t* wait_eff, const int64_t* wait_count, uint64_t seed,
+                              int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, double q_x, double q_y, double q_z,
+                              int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out) {
+    const char* who = "gf2_retry_wait_words_host";
+    StreamPlan plan;
+    RetryPlan retry;
+    RetryWaitPlan wait;
+    if (int rc = gf2_retry_wait_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
+                                     wait_eff, wait_count, max_attempts, &plan, &retry, &wait))
+        return rc;
+    if (int rc = gf2_retry_check_range(who, p_x, p_y, p_z, first_sample, count)) return rc;
+    if (int rc = gf2_retry_wait_check_rates(who, q_x, q_y, q_z)) return rc;
+    const RetryWaitDraw waits = {&wait, wait_eff, q_x, q_y, q_z};
+    return retry_walk_host(who, plan, retry, &waits, type_eff, block_type, block_kind, nblocks, seed, first_sample, count, p_x, p_y, p_z, max_attempts,
+                           words_out, ldw, attempts_out);
 }
 
 }  // extern "C"

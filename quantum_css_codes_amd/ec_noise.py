@@ -16,7 +16,9 @@ every measured qubit immediately before.  RESET clears the frame of its qubit an
 Repeat-until-success is post-selection.  One sample is one draw of the Monte-Carlo sampler over all L locations -- one attempt
 per preparation -- and a sample with any flag bit set is rejected.  Attempts are independent, and the model puts no fault on the
 data block while it waits, so the accepted samples have exactly the distribution of the reference's while_do loop;
-samples / accepted is the expected number of whole-cycle attempts per accepted one under this model.
+samples / accepted is the expected number of whole-cycle attempts per accepted one under this model.  (The model that does put
+faults on the waiting data block, on every attempt of every preparation, is stream_noise.py's retry_wait_* route: DESIGN.md section
+5d "Repeat-until-success with waiting faults".)
 
 Corrections are recorded (CodeBlock.x_errors, quil_classical_correct, css_code.py:649-685), never applied to the qubits, so
 everything but the table lookups is linear over GF(2) and one effect table carries the whole gadget.  The tally rule -- round

@@ -36,6 +36,10 @@ samples are other samples than the post-selected routes draw: the rates agree, t
 The retry_gate_* methods run the same walk under gate-level faults (DESIGN.md section 5d "Repeat-until-success under gate-level
 faults"): BlockType.gate_regions gives every region its sites, a one-operand gate fails with probability p1 and one of 3 kinds, a
 CNOT as one event with probability p2 and one of 15.  Regions are cut at gate boundaries, so the argument above holds for sites.
+
+The retry_wait_* methods make the data block pay for the retries (DESIGN.md section 5d "Repeat-until-success with waiting faults"):
+BlockType.waits gives every retried region its wait rows, one per qubit of the data block that no gate of the region touches, and
+every attempt made of the region, the failed ones included, draws them with memory error rates (q_x, q_y, q_z) of their own.
 """
 import numpy as np
 
@@ -61,7 +65,8 @@ class BlockType(object):
     """One type of block: `name`, `kind` (NONE, EC or MEASURE), its gate list `gates` (g, 3) int32 on 3n qubits, `locations` (L_b, 2)
     rows (gate, qubit), `num_flags` flag rows and `effects` (L_b, 2, 3) uint64: (local, tail, flags) of an X and of a Z fault;
     `regions` (R, 3) int64 rows (first location, count, retried) that partition the locations in order -- every `prep ...` part of
-    the builder a retried region, the locations between and around them maximal regions that are not."""
+    the builder a retried region, the locations between and around them maximal regions that are not.  waits() gives the retried
+    regions' wait rows."""
 
     def __init__(self, code, name, kind, emit):
         build = ec_noise.GadgetBuilder(code)
@@ -79,19 +84,23 @@ class BlockType(object):
                              % (name, self.num_flags, MAX_FLAG_ROWS))
         gates, rows_x, rows_z, row_time, _, _, _ = build.arrays(3, 2)
         self.gates = gates
-        self.effects, self.locations = _native.circuit_effects_timed(gates, 3 * build.n, _native.pack_rows(rows_x), _native.pack_rows(rows_z),
-                                                                     row_time, ldr=3)
+        self._rows = (3 * build.n, [int(q) for q in build.data], _native.pack_rows(rows_x), _native.pack_rows(rows_z), np.asarray(row_time, dtype=np.int64))
+        self.effects, self.locations = _native.circuit_effects_timed(gates, *self._rows[:1], *self._rows[2:], ldr=3)
         gate_of = self.locations[:, 0]                              # non-descending: locations are in gate order
         regions, at = [], 0
+        self._region_gates, self._waits = [], {}                    # per region: its gates [first, stop) if retried, else None
         for first, stop, path in sorted(span for span in build.spans if span[2][-1].startswith("prep ")):
             lo, hi = (int(v) for v in np.searchsorted(gate_of, [first, stop]))
             if lo > at:
                 regions.append((at, lo - at, 0))
+                self._region_gates.append(None)
             if hi > lo:
                 regions.append((lo, hi - lo, 1))
+                self._region_gates.append((int(first), int(stop)))
             at = max(at, hi)
         if at < len(gate_of):
             regions.append((at, len(gate_of) - at, 0))
+            self._region_gates.append(None)
         self.regions = np.array(regions, dtype=np.int64).reshape(-1, 3)
 
     @property
@@ -102,6 +111,59 @@ class BlockType(object):
         """Per region, the OR of the flag words of its locations: the flag rows it sets."""
         return np.array([np.bitwise_or.reduce(self.effects[first:first + count, :, 2].reshape(-1)) for first, count, _ in self.regions],
                         dtype=np.uint64)
+
+    def waits(self, wait_steps=1):
+        """The wait rows of the retried regions (DESIGN.md section 5d "Repeat-until-success with waiting faults"): (wait_eff, wait_count).
+        A retried region's waiting qubits are the data-block qubits that none of its gates touches; a wait row holds the (local, tail)
+        words of an X and of a Z fault of an IDLE on such a qubit placed immediately before the region's first gate.  wait_eff is
+        (rows, 2, 2) uint64, region by region, a region's rows in the data block's qubit order and repeated wait_steps times (more
+        waiting periods per attempt); wait_count (R,) int64 has a region's rows, 0 for one that is not retried.  Computed on the
+        block's own gate list with those IDLEs inserted, where two things are checked: an inserted location sets no flag row, and
+        the rows of all other locations are those of `effects`.  More than 512 wait rows in a region is a ValueError."""
+        wait_steps = int(wait_steps)
+        if wait_steps < 1:
+            raise ValueError("wait_steps must be at least 1")
+        if wait_steps in self._waits:
+            return self._waits[wait_steps]
+        qubits, data, rows_x, rows_z, row_time = self._rows
+        inserts = []                                                # (gate in front of which they go, the qubits that wait)
+        for span in self._region_gates:
+            if span is not None:
+                part = self.gates[span[0]:span[1]]
+                touched = set(part[:, 1].tolist()) | set(part[part[:, 0] == GATE_CNOT, 2].tolist())
+                inserts.append((span[0], [q for q in data if q not in touched]))
+        points = np.array([at for at, _ in inserts], dtype=np.int64)
+        sizes = np.array([len(waiting) for _, waiting in inserts], dtype=np.int64)
+        moved = lambda gate: gate + (sizes[None, :] * (points[None, :] <= np.asarray(gate)[:, None])).sum(axis=1)   # an old gate's new number
+        pieces, at = [], 0
+        for point, waiting in inserts:
+            pieces += [self.gates[at:point], np.array([(GATE_IDLE, q, 0) for q in waiting], dtype=np.int32).reshape(-1, 3)]
+            at = point
+        gates = np.concatenate(pieces + [self.gates[at:]]) if inserts else self.gates
+        effects, locations = _native.circuit_effects_timed(gates, qubits, rows_x, rows_z, moved(row_time), ldr=3)
+        firsts = moved(points) - sizes                              # the new numbers of every region's first IDLE
+        inserted = np.zeros(len(locations), dtype=bool)
+        parts = []
+        for first, size in zip(firsts, sizes):
+            rows = (locations[:, 0] >= first) & (locations[:, 0] < first + size)
+            assert int(rows.sum()) == size
+            inserted |= rows
+            parts.append(effects[rows])
+        if any(int(part[:, :, 2].any()) for part in parts):
+            raise ValueError("a waiting fault of block type %s sets a flag row: a preparation's flags depend on its own blocks only" % self.name)
+        kept = locations[~inserted]
+        if not (np.array_equal(effects[~inserted], self.effects) and np.array_equal(kept[:, 1], self.locations[:, 1]) and
+                np.array_equal(kept[:, 0], moved(self.locations[:, 0]))):
+            raise ValueError("inserting the waiting locations changed the rows of block type %s" % self.name)
+        count = np.zeros(len(self.regions), dtype=np.int64)
+        count[[r for r, span in enumerate(self._region_gates) if span is not None]] = sizes * wait_steps
+        if count.max(initial=0) > _native.RETRY_WAIT_MAX_ROWS:
+            raise ValueError("a region of block type %s has %d wait rows, more than the %d of one sampler segment"
+                             % (self.name, int(count.max()), _native.RETRY_WAIT_MAX_ROWS))
+        rows = [np.tile(part[:, :, :2], (wait_steps, 1, 1)) for part in parts]
+        wait_eff = np.ascontiguousarray(np.concatenate(rows + [np.zeros((0, 2, 2), dtype=np.uint64)]), dtype=np.uint64)
+        self._waits[wait_steps] = (wait_eff, count)
+        return self._waits[wait_steps]
 
     def gate_regions(self):
         """The sites of the gate-level fault model (circuit_noise.gate_sites) region by region: (site_loc, site_regions).  site_loc
@@ -179,6 +241,8 @@ class StreamedGadget(object):
         self._device = None
         self._retry_device = None
         self._retry_gate_device = None
+        self._retry_wait = {}                                       # per wait_steps: (wait_eff, wait_count, wait rows of a sample's preparations)
+        self._retry_wait_device = {}
 
     @classmethod
     def cycle(cls, code, rounds, idle_data=False):
@@ -358,6 +422,58 @@ class StreamedGadget(object):
         those of the post-selected routes at every p; the samples are different samples."""
         return _native.retry_words_host(*self._retry_sequence(), seed, first_sample, num_samples, p_x, p_y, p_z, max_attempts, self.ldw + 1,
                                         self.preparations)
+
+    # -- repeat-until-success with waiting faults ---------------------------------------------------------------------------------
+    def _retry_wait_sequence(self, wait_steps=1):
+        wait_steps = int(wait_steps)
+        if wait_steps not in self._retry_wait:
+            waits = [t.waits(wait_steps) for t in self.types]
+            self._retry_wait[wait_steps] = (np.ascontiguousarray(np.concatenate([eff for eff, _ in waits])),
+                                            np.concatenate([count for _, count in waits]).astype(np.int64),
+                                            int(sum(int(waits[t][1].sum()) for t in self.block_type if t >= 0)))
+        return self._retry_sequence() + self._retry_wait[wait_steps][:2]
+
+    def wait_locations(self, wait_steps=1):
+        """The wait rows per attempt summed over the sequence's preparations."""
+        self._retry_wait_sequence(wait_steps)
+        return self._retry_wait[int(wait_steps)][2]
+
+    def retry_wait_device(self, wait_steps=1):
+        wait_steps = int(wait_steps)
+        if wait_steps not in self._retry_wait_device:
+            self._retry_wait_device[wait_steps] = _native.default_context().retry_wait_create(*self._retry_wait_sequence(wait_steps))
+        return self._retry_wait_device[wait_steps]
+
+    def retry_wait_outcomes(self, num_samples, p_x, p_y, p_z, q_x, q_y, q_z, seed=0, first_sample=0, wait_steps=1, max_attempts=256):
+        """retry_outcomes with waiting faults (DESIGN.md section 5d "Repeat-until-success with waiting faults"): every attempt made of
+        a retried region, the failed ones included, also draws the region's wait rows (BlockType.waits) with the memory error rates
+        (q_x, q_y, q_z) into the block's words.  A (num_samples, ldw + 2) uint64 array [steps] [flag words] [attempts] [wait faults
+        drawn over all attempts of the sample] (gf2_retry_wait_outcomes_dev).  With q = 0 the first ldw + 1 words are retry_outcomes'."""
+        ctx = _native.default_context()
+        return ctx.outcomes(ctx.retry_wait_outcomes_dev, self.retry_wait_device(wait_steps), seed, first_sample, num_samples, p_x, p_y, p_z,
+                            self.ldw + 2, float(q_x), float(q_y), float(q_z), int(max_attempts))
+
+    def retry_wait_counts(self, num_samples, p_x, p_y, p_z, q_x, q_y, q_z, seed=0, first_sample=0, wait_steps=1, max_attempts=256):
+        """The fifteen counts -- the RETRY_FIELDS, then the wait faults of all samples -- of samples [first_sample, first_sample +
+        num_samples) on the device (gf2_mc_retry_wait_decode)."""
+        return _native.default_context().mc_retry_wait_decode(self.retry_wait_device(wait_steps), *self._tables(), int(seed), int(first_sample),
+                                                               int(num_samples), float(p_x), float(p_y), float(p_z), float(q_x), float(q_y),
+                                                               float(q_z), int(max_attempts))
+
+    def retry_wait_error_rates(self, num_samples, p_x, p_y, p_z, q_x, q_y, q_z, seed=0, first_sample=0, wait_steps=1, max_attempts=256):
+        """retry_error_rates' dict with waiting faults, plus 'wait_faults' (those drawn over all attempts of all samples) and
+        'wait_locations' (the wait rows per attempt summed over the sequence's preparations).  The counts of sample ranges add."""
+        counts = self.retry_wait_counts(num_samples, p_x, p_y, p_z, q_x, q_y, q_z, seed, first_sample, wait_steps, max_attempts)
+        out = self._dict(counts, num_samples)
+        out.update(exhausted=int(counts[12]), attempts=int(counts[13]), preparations=self.preparations, wait_faults=int(counts[14]),
+                   wait_locations=self.wait_locations(wait_steps))
+        return out
+
+    def retry_wait_words_host(self, num_samples, p_x, p_y, p_z, q_x, q_y, q_z, seed=0, first_sample=0, wait_steps=1, max_attempts=256):
+        """retry_wait_outcomes' words on the host (gf2_retry_wait_words_host, no GPU) and the (num_samples, preparations) uint32
+        attempts of every preparation in order, 0 for one never reached.  tally_host on words[:, :ldw] completes the statement."""
+        return _native.retry_wait_words_host(*self._retry_wait_sequence(wait_steps), seed, first_sample, num_samples, p_x, p_y, p_z, q_x, q_y, q_z,
+                                             max_attempts, self.ldw + 2, self.preparations)
 
     # -- repeat-until-success under gate-level faults ----------------------------------------------------------------------------
     def _retry_gate_sequence(self):
