@@ -1039,6 +1039,57 @@ int gf2_mc_retry_gate_decode(gf2_ctx* ctx, const gf2_retry_gate* retry, int64_t 
                              int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed,
                              int64_t first_sample, int64_t count, double p1, double p2, int64_t max_attempts, uint64_t* counts_out);
 
+/* ---- repeat-until-success with waiting faults under gate-level faults ------------------------------------
+ * [build-defined, DESIGN.md section 5d "Repeat-until-success with waiting faults under gate-level faults"]  The gate-level retried
+ * walk above, in which the data block pays for the retries as in "repeat-until-success with waiting faults".  Everything of
+ * "repeat-until-success under gate-level faults" stands: ks, g, kr = segment_draw(ks, 2^32 + g), ka = mix64(kr + G (a + 1)), the two
+ * classes of sites under ka with radix 3 and 15 and the slots GF2_GATE_MC_SLOT_ONE / GF2_GATE_MC_SLOT_CNOT, exhaustion, blocks, steps
+ * and the tally.  In addition, for a retried region g with W_g > 0 wait rows and every attempt a = 0, 1, ... actually made of it, the
+ * wait draw is that of "repeat-until-success with waiting faults", word for word:
+ *   kw = segment_draw(ks, GF2_RETRY_WAIT_SLOT_BASE + g) = segment_draw(ks, 2^33 + g),  kwa = mix64(kw + G (a + 1)),
+ *   d = segment_draw(kwa, 0),
+ * K from the inverse binomial CDF table of (T_any(q), W_g), the picks, Floyd's rule and the kinds error_draw's with q's thresholds.
+ * The picked rows' (local, tail) words are XORed into the block's words for every attempt made and are never cleared.  The memory
+ * rates stay (q_x, q_y, q_z): a memory's noise may be biased where the gates' noise is uniform over kinds.  Neither the region's own
+ * draw nor its key changes, so the attempts of every preparation are gf2_retry_gate_words_host's.
+ * Arguments: gf2_retry_gate_*'s with wait_eff, wait_count (as gf2_retry_wait_*'s) and the q rates added.  Besides the rules of
+ * gf2_retry_gate_words_host, GF2_E_ARG naming the rule: a wait count outside [0, 512], a wait count above 0 on a region that is not
+ * retried, more than GF2_RETRY_GATE_WAIT_MAX_SIZES distinct non-zero wait counts (the kernel keeps their inverse-CDF tables in LDS
+ * beside those of the two gate classes), bad q rates.
+ * Layout of a sample, nsteps + F + 2 words: [steps] [F flag words] [attempts] [wait faults].  The tally has the fifteen counts of
+ * GF2_RETRY_WAIT_FIELDS: the fourteen GF2_RETRY_FIELDS, then the wait faults, in 64 bits at every level. */
+#define GF2_RETRY_GATE_WAIT_MAX_SIZES 3
+typedef struct gf2_retry_gate_wait gf2_retry_gate_wait;
+
+/* The words on the host, serial, no GPU needed; words_out (ldw >= nsteps + F + 2) and attempts_out as gf2_retry_words_host's.
+ * gf2_stream_tally_host on the first nsteps + F words completes the statement. */
+int gf2_retry_gate_wait_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                                   const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                                   const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, const uint64_t* wait_eff,
+                                   const int64_t* wait_count, uint64_t seed, int64_t first_sample, int64_t count, double p1, double p2, double q_x,
+                                   double q_y, double q_z, int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out);
+
+/* A sequence, its regions, their sites and their wait rows on the device.  Argument rules as gf2_retry_gate_wait_words_host's
+ * (max_attempts, the rates and the range belong to the calls).  Destroyed by gf2_retry_gate_wait_destroy. */
+int gf2_retry_gate_wait_create(gf2_ctx* ctx, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                               const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                               const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, const uint64_t* wait_eff,
+                               const int64_t* wait_count, gf2_retry_gate_wait** retry_out);
+int gf2_retry_gate_wait_destroy(gf2_ctx* ctx, gf2_retry_gate_wait* retry);
+
+/* The words of samples first_sample .. first_sample + count - 1 in device memory, ldo >= nsteps + F + 2 words per sample; words past
+ * those are left as they were.  out_dev: any 8-byte-aligned address. */
+int gf2_retry_gate_wait_outcomes_dev(gf2_ctx* ctx, const gf2_retry_gate_wait* retry, uint64_t seed, int64_t first_sample, int64_t count,
+                                     double p1, double p2, double q_x, double q_y, double q_z, int64_t max_attempts, uint64_t* out_dev,
+                                     int64_t ldo);
+
+/* The tally of those samples on the device, no word stored: counts_out[GF2_RETRY_WAIT_FIELDS] on the host.  Counts of sample ranges
+ * add.  The inverse-CDF tables are made per call and freed with it: no state beyond the handle. */
+int gf2_mc_retry_gate_wait_decode(gf2_ctx* ctx, const gf2_retry_gate_wait* retry, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                                  int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed,
+                                  int64_t first_sample, int64_t count, double p1, double p2, double q_x, double q_y, double q_z,
+                                  int64_t max_attempts, uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

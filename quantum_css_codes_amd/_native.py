@@ -28,6 +28,7 @@ STREAM_FIELDS_COUNT, STREAM_MAX_TYPES, STREAM_MAX_OVERLAP = 12, 64, 8
 STREAM_NONE, STREAM_EC, STREAM_MEASURE, STREAM_FINAL = 0, 1, 2, 3
 RETRY_FIELDS_COUNT, RETRY_MAX_ATTEMPTS, RETRY_MAX_SIZES = 14, 65536, 16
 RETRY_WAIT_FIELDS_COUNT, RETRY_WAIT_MAX_ROWS = 15, 512
+RETRY_GATE_WAIT_MAX_SIZES = 3
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 ENUMERATE_MAX_WEIGHT = 8
@@ -218,6 +219,13 @@ SIGNATURES = {
     "gf2_retry_gate_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, _c_i64, _p, _c_i64],
     "gf2_mc_retry_gate_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
                                  _c_i64, _p],
+    "gf2_retry_gate_wait_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _p, _p, _p, _c_u64, _c_i64, _c_i64] + [ctypes.c_double] * 5 +
+                                      [_c_i64, _p, _c_i64, _p],
+    "gf2_retry_gate_wait_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _p, _p, _p, _p, _pp],
+    "gf2_retry_gate_wait_destroy": [_p, _p],
+    "gf2_retry_gate_wait_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64] + [ctypes.c_double] * 5 + [_c_i64, _p, _c_i64],
+    "gf2_mc_retry_gate_wait_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64] + [ctypes.c_double] * 5 +
+                                     [_c_i64, _p],
     "gf2_comm_unique_id": [_p, ctypes.c_size_t],
     "gf2_comm_create": [_p, _p, ctypes.c_int, ctypes.c_int, _pp],
     "gf2_comm_create_all": [_pp, ctypes.c_int, _pp],
@@ -610,6 +618,24 @@ def retry_gate_words_host(type_eff, type_locations, type_flags, block_type, bloc
     attempts = np.zeros((max(1, count), max(1, int(preparations))), dtype=np.uint32)
     check(lib().gf2_retry_gate_words_host(*seq, *regions, *sites, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p1), float(p2),
                                           int(max_attempts), _ptr(out), int(ldw), _ptr(attempts)))
+    return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
+
+
+def retry_gate_wait_words_host(type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc, site_regions,
+                               wait_eff, wait_count, seed, first, count, p1, p2, q_x, q_y, q_z, max_attempts, ldw, preparations):
+    """gf2_retry_gate_wait_words_host (host code, no GPU): the (count, ldw) words [steps] [flag words] [attempts] [wait faults] of
+    samples [first, first + count) of the repeat-until-success sampler under gate-level faults with waiting faults and the (count,
+    preparations) uint32 attempts of every retried region."""
+    keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+    keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+    keep_sites, sites = _retry_sites(site_loc, site_regions, len(keep_regions[0]))
+    keep_waits, waits = _retry_waits(wait_eff, wait_count, len(keep_regions[0]))
+    count = int(count)
+    out = np.zeros((max(1, count), max(1, int(ldw))), dtype="<u8")
+    attempts = np.zeros((max(1, count), max(1, int(preparations))), dtype=np.uint32)
+    check(lib().gf2_retry_gate_wait_words_host(*seq, *regions, *sites, *waits, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p1),
+                                               float(p2), float(q_x), float(q_y), float(q_z), int(max_attempts), _ptr(out), int(ldw),
+                                               _ptr(attempts)))
     return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
 
 
@@ -1038,6 +1064,23 @@ class RetryGate(_Handle):
 
 
 
+class RetryGateWait(_Handle):
+    """A block sequence, its regions, their sites and their wait rows on the device (gf2_retry_gate_wait_create)."""
+    _destroy = "gf2_retry_gate_wait_destroy"
+
+    def __init__(self, ctx, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc, site_regions,
+                 wait_eff, wait_count):
+        self.ctx = ctx
+        keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+        keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+        keep_sites, sites = _retry_sites(site_loc, site_regions, len(keep_regions[0]))
+        keep_waits, waits = _retry_waits(wait_eff, wait_count, len(keep_regions[0]))
+        out = ctypes.c_void_p()
+        check(lib().gf2_retry_gate_wait_create(ctx.handle, *seq, *regions, *sites, *waits, ctypes.byref(out)))
+        self.handle = out.value
+
+
+
 class Context(object):
     """One HIP stream on one MI355X (gf2_ctx)."""
 
@@ -1389,6 +1432,24 @@ class Context(object):
         counts = np.zeros(RETRY_RULE.fields, dtype=np.uint64)
         check(lib().gf2_mc_retry_gate_decode(self.handle, retry.handle, *rest, seed & 0xFFFFFFFFFFFFFFFF, first, count, p1, p2, int(max_attempts),
                                              _ptr(counts)))
+        return counts
+
+    def retry_gate_wait_create(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc,
+                               site_regions, wait_eff, wait_count):
+        return RetryGateWait(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc,
+                             site_regions, wait_eff, wait_count)
+
+    def retry_gate_wait_outcomes_dev(self, retry, seed, first, count, p1, p2, q_x, q_y, q_z, max_attempts, out_buf, ldo):
+        check(lib().gf2_retry_gate_wait_outcomes_dev(self.handle, retry.handle, seed & 0xFFFFFFFFFFFFFFFF, first, count, p1, p2, float(q_x),
+                                                     float(q_y), float(q_z), int(max_attempts), out_buf.ptr, ldo))
+
+    def mc_retry_gate_wait_decode(self, retry, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p1, p2, q_x, q_y, q_z, max_attempts):
+        """gf2_mc_retry_gate_wait_decode: the fifteen counts of the repeat-until-success tally under gate-level faults with waiting
+        faults."""
+        keep, rest = _rule_arguments(RETRY_WAIT_RULE, (), (r1, keys1, flips1, r2, keys2, flips2))
+        counts = np.zeros(RETRY_WAIT_RULE.fields, dtype=np.uint64)
+        check(lib().gf2_mc_retry_gate_wait_decode(self.handle, retry.handle, *rest, seed & 0xFFFFFFFFFFFFFFFF, first, count, p1, p2, float(q_x),
+                                                  float(q_y), float(q_z), int(max_attempts), _ptr(counts)))
         return counts
 
     def mc_circuit_decode_strata(self, circ, r1, keys1, flips1, r2, keys2, flips2, seed, first, weights, counts, k_x, k_y, k_z):

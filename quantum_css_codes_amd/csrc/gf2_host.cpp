@@ -1672,14 +1672,22 @@ int gf2_retry_wait_plan(const char* who, const uint64_t* type_eff, const int64_t
     if (int rc = gf2_retry_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
                                 max_attempts, plan, retry))
         return rc;
+    return gf2_retry_wait_rules(who, ntypes, block_type, block_kind, nblocks, wait_eff, wait_count, GF2_RETRY_MAX_SIZES, "GF2_RETRY_MAX_SIZES", plan,
+                                *retry, wait);
+}
+
+int gf2_retry_wait_rules(const char* who, int64_t ntypes, const int32_t* block_type, const int32_t* block_kind, int64_t nblocks,
+                         const uint64_t* wait_eff, const int64_t* wait_count, int max_sizes, const char* max_sizes_name, StreamPlan* plan,
+                         const RetryPlan& retried, RetryWaitPlan* wait) {
+    const RetryPlan* const retry = &retried;
     if (!wait_count || !wait) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
     const int64_t total = retry->type_first[(size_t)ntypes];
-    std::vector<int32_t> sizes;                                                  // a set of at most GF2_RETRY_MAX_SIZES + 1 values
+    std::vector<int32_t> sizes;                                                  // a set of at most max_sizes + 1 values
     try {
         wait->first.assign((size_t)total, 0);
         wait->count.assign((size_t)total, 0);
         wait->size.assign((size_t)total, -1);
-        sizes.reserve(GF2_RETRY_MAX_SIZES + 1);
+        sizes.reserve((size_t)max_sizes + 1);
     } catch (const std::bad_alloc&) {
         GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
     }
@@ -1696,12 +1704,12 @@ int gf2_retry_wait_plan(const char* who, const uint64_t* type_eff, const int64_t
             wait->first[(size_t)q] = rows;
             wait->count[(size_t)q] = (int32_t)w;
             rows += w;
-            if (w > 0 && std::find(sizes.begin(), sizes.end(), (int32_t)w) == sizes.end() && sizes.size() <= (size_t)GF2_RETRY_MAX_SIZES)
+            if (w > 0 && std::find(sizes.begin(), sizes.end(), (int32_t)w) == sizes.end() && sizes.size() <= (size_t)max_sizes)
                 sizes.push_back((int32_t)w);
         }
-    if (sizes.size() > (size_t)GF2_RETRY_MAX_SIZES)
-        GF2_FAIL(GF2_E_ARG, "%s: the regions have more than GF2_RETRY_MAX_SIZES = %d distinct wait sizes, one inverse-CDF table each", who,
-                 GF2_RETRY_MAX_SIZES);
+    if (sizes.size() > (size_t)max_sizes)
+        GF2_FAIL(GF2_E_ARG, "%s: the regions have more than %s = %d distinct wait sizes, one inverse-CDF table each", who, max_sizes_name,
+                 max_sizes);
     if (rows > 0 && !wait_eff) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
     std::sort(sizes.begin(), sizes.end());
     wait->sizes = sizes;
@@ -1972,47 +1980,62 @@ int gf2_retry_gate_plan(const char* who, const uint64_t* type_eff, const int64_t
     return GF2_OK;
 }
 
-extern "C" {
+// ... and with waiting faults on the data block ("Repeat-until-success with waiting faults under gate-level faults")
+#include "gf2_retry_gate_wait_plan.h"
 
+int gf2_retry_gate_wait_plan(const char* who, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                             const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                             const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, const uint64_t* wait_eff,
+                             const int64_t* wait_count, int64_t max_attempts, StreamPlan* plan, RetryPlan* retry, RetryGatePlan* gate,
+                             RetryWaitPlan* wait) {
+    if (int rc = gf2_retry_gate_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
+                                     site_loc, site_regions, max_attempts, plan, retry, gate))
+        return rc;
+    return gf2_retry_wait_rules(who, ntypes, block_type, block_kind, nblocks, wait_eff, wait_count, GF2_RETRY_GATE_WAIT_MAX_SIZES,
+                                "GF2_RETRY_GATE_WAIT_MAX_SIZES", plan, *retry, wait);
+}
+
+namespace {
 // The definition of gf2_retry_gate_outcomes_dev's words (DESIGN.md section 5d "Repeat-until-success under gate-level faults"),
 // serial: gf2_retry_words_host's walk, an attempt drawn as gf2_gate_outcomes_host draws a sample -- the region's one-operand sites,
 // then its CNOT sites, each class with its own slots, rate and radix of kinds -- under the attempt's key.
-int gf2_retry_gate_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
-                              const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
-                              const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, uint64_t seed,
-                              int64_t first_sample, int64_t count, double p1, double p2, int64_t max_attempts, uint64_t* words_out, int64_t ldw,
-                              uint32_t* attempts_out) {
-    const char* who = "gf2_retry_gate_words_host";
-    StreamPlan plan;
-    RetryPlan retry;
-    RetryGatePlan gate;
-    if (int rc = gf2_retry_gate_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
-                                     site_loc, site_regions, max_attempts, &plan, &retry, &gate))
-        return rc;
-    if (int rc = gf2_gate_check_mc(who, p1, p2, first_sample, count)) return rc;
-    const int64_t ldr = plan.nsteps + plan.flag_words + 1;
-    if (ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the sequence's nsteps + F + 1 = %lld words", who, (long long)ldr);
+// With `waits` (gf2_retry_gate_wait_outcomes_dev's words, "Repeat-until-success with waiting faults under gate-level faults") every
+// attempt made of a region with wait rows also draws that region's waiting faults as retry_walk_host does, and a sample has one word
+// more, the waiting faults it drew.
+int retry_gate_walk_host(const char* who, const StreamPlan& plan, const RetryPlan& retry, const RetryGatePlan& gate, const RetryWaitDraw* waits,
+                         const uint64_t* type_eff, const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int32_t* site_loc,
+                         uint64_t seed, int64_t first_sample, int64_t count, double p1, double p2, int64_t max_attempts, uint64_t* words_out,
+                         int64_t ldw, uint32_t* attempts_out) {
+    const int64_t ldr = plan.nsteps + plan.flag_words + (waits ? 2 : 1);
+    if (ldw < ldr)
+        GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the sequence's nsteps + F + %d = %lld words", who, waits ? 2 : 1, (long long)ldr);
     if (count == 0) return GF2_OK;
     if (!words_out) GF2_FAIL(GF2_E_ARG, "%s: null buffer", who);
     const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
     const int SEG = 512;
     const uint64_t radix[2] = {3, 15}, slot_base[2] = {GF2_GATE_MC_SLOT_ONE, GF2_GATE_MC_SLOT_CNOT};
     const uint64_t T[2] = {host_quantise(p1), host_quantise(p2)};
-    std::vector<uint64_t> cdf[2];                                                // per class: [size][SEG + 1]
+    const double q_t = waits ? waits->q_x + waits->q_y + waits->q_z : 0.0;
+    const uint64_t w_any = host_quantise(q_t), w_1 = q_t > 0.0 ? host_quantise(waits->q_x / q_t) : 0,
+                   w_2 = q_t > 0.0 ? host_quantise((waits->q_x + waits->q_y) / q_t) : 0;
+    const size_t wait_sizes = waits ? waits->plan->sizes.size() : 0;
+    std::vector<uint64_t> cdf[2], wait_cdf;                                      // per class, and of the wait sizes: [size][SEG + 1]
     try {
         for (int cl = 0; cl < 2; ++cl) cdf[cl].resize(gate.sizes[cl].size() * (SEG + 1));
+        wait_cdf.resize(wait_sizes * (SEG + 1));
     } catch (const std::bad_alloc&) {
         GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
     }
     for (int cl = 0; cl < 2; ++cl)
         for (size_t k = 0; k < gate.sizes[cl].size(); ++k) host_binomial_cdf_table(T[cl], gate.sizes[cl][k], &cdf[cl][k * (SEG + 1)]);
+    for (size_t k = 0; k < wait_sizes; ++k) host_binomial_cdf_table(w_any, waits->plan->sizes[k], &wait_cdf[k * (SEG + 1)]);
     for (int64_t i = 0; i < count; ++i) {
         uint64_t* const out = words_out + i * ldw;
         for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
         uint32_t* const tries = attempts_out ? attempts_out + i * retry.preparations : nullptr;
         for (int64_t q = 0; tries && q < retry.preparations; ++q) tries[q] = 0;
         const uint64_t ks = host_mix64(seed + golden * ((uint64_t)(first_sample + i) + 1));
-        uint64_t frame = 0, attempts = 0;
+        uint64_t frame = 0, attempts = 0, wait_faults = 0;
         int64_t g = 0, prep = 0;
         bool exhausted = false;
         for (int64_t b = 0; b < nblocks && !exhausted; ++b) {
@@ -2023,7 +2046,9 @@ int gf2_retry_gate_words_host(const uint64_t* type_eff, const int64_t* type_loca
                     const int64_t limit = retry.retried[(size_t)r] ? max_attempts : 1;
                     const uint64_t* const rows = type_eff + (size_t)plan.type_offset[(size_t)t] * 6;   // the type's table: sites are type-local
                     const uint64_t kr = host_mix64(ks + stream * (GF2_RETRY_SLOT_BASE + (uint64_t)g + 1));
-                    uint64_t acc[3] = {0, 0, 0};
+                    const int nw = waits ? waits->plan->count[(size_t)r] : 0;
+                    const uint64_t kw = host_mix64(ks + stream * (GF2_RETRY_WAIT_SLOT_BASE + (uint64_t)g + 1));
+                    uint64_t acc[3] = {0, 0, 0}, waited[2] = {0, 0};
                     int64_t a = 0;
                     do {
                         const uint64_t ka = host_mix64(kr + golden * ((uint64_t)a + 1));
@@ -2055,6 +2080,12 @@ int gf2_retry_gate_words_host(const uint64_t* type_eff, const int64_t* type_loca
                                 }
                             }
                         }
+                        if (nw > 0) {                                            // the data waits through this attempt, passed or not
+                            const uint64_t kwa = host_mix64(kw + golden * ((uint64_t)a + 1));
+                            wait_faults += (uint64_t)retry_segment_host(host_mix64(kwa + stream), nw,
+                                                                        &wait_cdf[(size_t)waits->plan->size[(size_t)r] * (SEG + 1)], w_1, w_2,
+                                                                        waits->eff + (size_t)waits->plan->first[(size_t)r] * 4, 2, waited);
+                        }
                         a += 1;
                     } while (acc[2] != 0 && a < limit);
                     if (retry.retried[(size_t)r]) {
@@ -2068,7 +2099,7 @@ int gf2_retry_gate_words_host(const uint64_t* type_eff, const int64_t* type_loca
                         out[plan.nsteps + (row >> 6)] |= acc[2] << (row & 63);
                         if ((row & 63) && (acc[2] >> (64 - (row & 63)))) out[plan.nsteps + (row >> 6) + 1] |= acc[2] >> (64 - (row & 63));
                     }
-                    local ^= acc[0], tail ^= acc[1];
+                    local ^= acc[0] ^ waited[0], tail ^= acc[1] ^ waited[1];
                 }
             }
             if (exhausted) break;
@@ -2076,8 +2107,49 @@ int gf2_retry_gate_words_host(const uint64_t* type_eff, const int64_t* type_loca
             frame ^= tail;
         }
         out[plan.nsteps + plan.flag_words] = attempts;
+        if (waits) out[plan.nsteps + plan.flag_words + 1] = wait_faults;
     }
     return GF2_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gf2_retry_gate_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                              const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                              const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, uint64_t seed,
+                              int64_t first_sample, int64_t count, double p1, double p2, int64_t max_attempts, uint64_t* words_out, int64_t ldw,
+                              uint32_t* attempts_out) {
+    const char* who = "gf2_retry_gate_words_host";
+    StreamPlan plan;
+    RetryPlan retry;
+    RetryGatePlan gate;
+    if (int rc = gf2_retry_gate_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
+                                     site_loc, site_regions, max_attempts, &plan, &retry, &gate))
+        return rc;
+    if (int rc = gf2_gate_check_mc(who, p1, p2, first_sample, count)) return rc;
+    return retry_gate_walk_host(who, plan, retry, gate, nullptr, type_eff, block_type, block_kind, nblocks, site_loc, seed, first_sample, count, p1,
+                                p2, max_attempts, words_out, ldw, attempts_out);
+}
+
+int gf2_retry_gate_wait_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                                   const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
+                                   const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, const uint64_t* wait_eff,
+                                   const int64_t* wait_count, uint64_t seed, int64_t first_sample, int64_t count, double p1, double p2, double q_x,
+                                   double q_y, double q_z, int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out) {
+    const char* who = "gf2_retry_gate_wait_words_host";
+    StreamPlan plan;
+    RetryPlan retry;
+    RetryGatePlan gate;
+    RetryWaitPlan wait;
+    if (int rc = gf2_retry_gate_wait_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions,
+                                          type_nregions, site_loc, site_regions, wait_eff, wait_count, max_attempts, &plan, &retry, &gate, &wait))
+        return rc;
+    if (int rc = gf2_gate_check_mc(who, p1, p2, first_sample, count)) return rc;
+    if (int rc = gf2_retry_wait_check_rates(who, q_x, q_y, q_z)) return rc;
+    const RetryWaitDraw waits = {&wait, wait_eff, q_x, q_y, q_z};
+    return retry_gate_walk_host(who, plan, retry, gate, &waits, type_eff, block_type, block_kind, nblocks, site_loc, seed, first_sample, count, p1,
+                                p2, max_attempts, words_out, ldw, attempts_out);
 }
 
 }  // extern "C"

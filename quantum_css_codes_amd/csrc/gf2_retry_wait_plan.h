@@ -34,5 +34,12 @@ int gf2_retry_wait_plan(const char* who, const uint64_t* type_eff, const int64_t
                         const int64_t* type_nregions, const uint64_t* wait_eff, const int64_t* wait_count, int64_t max_attempts,
                         StreamPlan* plan, RetryPlan* retry, RetryWaitPlan* wait);
 
+// The wait rules alone, on a plan and regions already checked: what gf2_retry_wait_plan does after gf2_retry_plan, and
+// gf2_retry_gate_wait_plan after gf2_retry_gate_plan.  At most max_sizes distinct non-zero wait sizes; max_sizes_name is the constant
+// the message names.
+int gf2_retry_wait_rules(const char* who, int64_t ntypes, const int32_t* block_type, const int32_t* block_kind, int64_t nblocks,
+                         const uint64_t* wait_eff, const int64_t* wait_count, int max_sizes, const char* max_sizes_name, StreamPlan* plan,
+                         const RetryPlan& retry, RetryWaitPlan* wait);
+
 // The waiting rates of a call: GF2_E_ARG worded as gf2_retry_check_range words the gates' rates.
 int gf2_retry_wait_check_rates(const char* who, double q_x, double q_y, double q_z);

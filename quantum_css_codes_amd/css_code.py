@@ -584,6 +584,27 @@ class CSSCode(QECC):
         gadget = stream_noise.stream_for(self, "program", ft_noise.check_ops(ops))
         return gadget.retry_gate_error_rates(num_samples, p1, p2, seed=seed, first_sample=first_sample, max_attempts=max_attempts)
 
+    def error_correct_retried_gate_wait_error_rates(self, num_samples, p1, p2, q_x, q_y, q_z, rounds, seed=0, first_sample=0, idle_data=False,
+                                                    wait_steps=1, max_attempts=256):
+        """[build-defined]  error_correct_retried_gate_error_rates in which the data block pays for the retries (stream_noise
+        .StreamedGadget.retry_gate_wait_error_rates): while a preparation is attempted, every qubit of the data block has a fault
+        location of its own with the memory error rates (q_x, q_y, q_z), wait_steps of them per attempt, on every attempt made, the
+        failed ones included.  The dict also has 'wait_faults' and 'wait_locations'.  With q = 0 the counts are
+        error_correct_retried_gate_error_rates' of the same seed."""
+        from . import stream_noise
+        gadget = stream_noise.stream_for(self, "cycle", (int(rounds), bool(idle_data)))
+        return gadget.retry_gate_wait_error_rates(num_samples, p1, p2, q_x, q_y, q_z, seed=seed, first_sample=first_sample, wait_steps=wait_steps,
+                                                  max_attempts=max_attempts)
+
+    def logical_program_retried_gate_wait_error_rates(self, ops, num_samples, p1, p2, q_x, q_y, q_z, seed=0, first_sample=0, wait_steps=1,
+                                                      max_attempts=256):
+        """[build-defined]  logical_program_retried_gate_error_rates with waiting faults on the data block, likewise (none while the
+        data block itself is prepared)."""
+        from . import ft_noise, stream_noise
+        gadget = stream_noise.stream_for(self, "program", ft_noise.check_ops(ops))
+        return gadget.retry_gate_wait_error_rates(num_samples, p1, p2, q_x, q_y, q_z, seed=seed, first_sample=first_sample, wait_steps=wait_steps,
+                                                  max_attempts=max_attempts)
+
 
 # -- free functions -----------------------------------------------------------------------------------------
 

@@ -40,6 +40,8 @@ CNOT as one event with probability p2 and one of 15.  Regions are cut at gate bo
 The retry_wait_* methods make the data block pay for the retries (DESIGN.md section 5d "Repeat-until-success with waiting faults"):
 BlockType.waits gives every retried region its wait rows, one per qubit of the data block that no gate of the region touches, and
 every attempt made of the region, the failed ones included, draws them with memory error rates (q_x, q_y, q_z) of their own.
+The retry_gate_wait_* methods do the same under gate-level faults (DESIGN.md section 5d "Repeat-until-success with waiting faults
+under gate-level faults"): retry_gate_*'s walk and draw plus retry_wait_*'s wait draw.
 """
 import numpy as np
 
@@ -243,6 +245,7 @@ class StreamedGadget(object):
         self._retry_gate_device = None
         self._retry_wait = {}                                       # per wait_steps: (wait_eff, wait_count, wait rows of a sample's preparations)
         self._retry_wait_device = {}
+        self._retry_gate_wait_device = {}
 
     @classmethod
     def cycle(cls, code, rounds, idle_data=False):
@@ -519,6 +522,54 @@ class StreamedGadget(object):
         attempts of every preparation in order, 0 for one never reached.  tally_host on words[:, :ldw] completes the statement."""
         return _native.retry_gate_words_host(*self._retry_gate_sequence(), seed, first_sample, num_samples, p1, p2, max_attempts, self.ldw + 1,
                                              self.preparations)
+
+    # -- repeat-until-success with waiting faults under gate-level faults ---------------------------------------------------------
+    def _retry_gate_wait_sequence(self, wait_steps=1):
+        return self._retry_gate_sequence() + self._retry_wait_sequence(wait_steps)[-2:]
+
+    def retry_gate_wait_device(self, wait_steps=1):
+        wait_steps = int(wait_steps)
+        if wait_steps not in self._retry_gate_wait_device:
+            self._retry_gate_wait_device[wait_steps] = _native.default_context().retry_gate_wait_create(*self._retry_gate_wait_sequence(wait_steps))
+        return self._retry_gate_wait_device[wait_steps]
+
+    def retry_gate_wait_outcomes(self, num_samples, p1, p2, q_x, q_y, q_z, seed=0, first_sample=0, wait_steps=1, max_attempts=256):
+        """retry_gate_outcomes with waiting faults (DESIGN.md section 5d "Repeat-until-success with waiting faults under gate-level
+        faults"): every attempt made of a retried region, the failed ones included, also draws the region's wait rows
+        (BlockType.waits) with the memory error rates (q_x, q_y, q_z) into the block's words.  A (num_samples, ldw + 2) uint64 array
+        [steps] [flag words] [attempts] [wait faults drawn over all attempts of the sample] (gf2_retry_gate_wait_outcomes_dev).  With
+        q = 0 the first ldw + 1 words are retry_gate_outcomes'."""
+        ctx = _native.default_context()
+        count = int(num_samples)
+        buf = ctx.alloc(max(1, count) * (self.ldw + 2) * 8)
+        try:
+            ctx.retry_gate_wait_outcomes_dev(self.retry_gate_wait_device(wait_steps), int(seed), int(first_sample), count, float(p1), float(p2),
+                                             float(q_x), float(q_y), float(q_z), int(max_attempts), buf, self.ldw + 2)
+            return buf.download((count, self.ldw + 2), np.uint64)
+        finally:
+            buf.free()
+
+    def retry_gate_wait_counts(self, num_samples, p1, p2, q_x, q_y, q_z, seed=0, first_sample=0, wait_steps=1, max_attempts=256):
+        """The fifteen counts -- the RETRY_FIELDS, then the wait faults of all samples -- of samples [first_sample, first_sample +
+        num_samples) under gate-level faults on the device (gf2_mc_retry_gate_wait_decode)."""
+        return _native.default_context().mc_retry_gate_wait_decode(self.retry_gate_wait_device(wait_steps), *self._tables(), int(seed),
+                                                                    int(first_sample), int(num_samples), float(p1), float(p2), float(q_x),
+                                                                    float(q_y), float(q_z), int(max_attempts))
+
+    def retry_gate_wait_error_rates(self, num_samples, p1, p2, q_x, q_y, q_z, seed=0, first_sample=0, wait_steps=1, max_attempts=256):
+        """retry_gate_error_rates' dict with waiting faults, plus 'wait_faults' (those drawn over all attempts of all samples) and
+        'wait_locations' (the wait rows per attempt summed over the sequence's preparations).  The counts of sample ranges add."""
+        counts = self.retry_gate_wait_counts(num_samples, p1, p2, q_x, q_y, q_z, seed, first_sample, wait_steps, max_attempts)
+        out = self._dict(counts, num_samples)
+        out.update(exhausted=int(counts[12]), attempts=int(counts[13]), preparations=self.preparations, wait_faults=int(counts[14]),
+                   wait_locations=self.wait_locations(wait_steps))
+        return out
+
+    def retry_gate_wait_words_host(self, num_samples, p1, p2, q_x, q_y, q_z, seed=0, first_sample=0, wait_steps=1, max_attempts=256):
+        """retry_gate_wait_outcomes' words on the host (gf2_retry_gate_wait_words_host, no GPU) and the (num_samples, preparations)
+        uint32 attempts of every preparation in order, 0 for one never reached.  tally_host on words[:, :ldw] completes the statement."""
+        return _native.retry_gate_wait_words_host(*self._retry_gate_wait_sequence(wait_steps), seed, first_sample, num_samples, p1, p2, q_x, q_y,
+                                                  q_z, max_attempts, self.ldw + 2, self.preparations)
 
 
 def stream_for(code, what, key):
