@@ -888,6 +888,77 @@ int gf2_mc_stream_decode(gf2_ctx* ctx, const gf2_stream* stream, int64_t r1, con
                          int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed, int64_t first_sample,
                          int64_t count, double p_x, double p_y, double p_z, uint64_t* counts_out);
 
+/* ---- multi-block streamed programs: several logical qubits and the transversal CNOT, block by block ------------
+ * [build-defined, DESIGN.md section 5d "Multi-block programs"]  The streamed route above with one data frame per logical qubit,
+ * T[0 .. nframes - 1], 1 <= nframes <= GF2_MSTREAM_MAX_FRAMES.  A block is (type, kind, a, b): the blocks of the kinds NONE, EC and
+ * MEASURE are the streamed route's, serving data frame a (b = -1), with the same tables -- they do not depend on which data block
+ * they serve.  The new kind is
+ *   GF2_MSTREAM_CNOT    the n physical CNOTs of a transversal CNOT from data block a to data block b != a: 2 n locations, no step
+ *                       word, no flag rows (type_flags = 0, third word zero); a table row's first word is the tail the fault leaves
+ *                       on frame a, its second word the tail it leaves on frame b (gf2_circuit_effects_timed on the block's own gate
+ *                       list over the two data blocks, final-frame rows of block a in word 0 and of block b in word 1)
+ * There is no FINAL step.  Fault locations are numbered through the blocks in order, L <= GF2_CIRCUIT_MAX_LOCATIONS, and sample i has
+ * the faults gf2_circuit_outcomes_dev draws for a circuit of L locations.  With every T = 0, the blocks in order: a CNOT block applies
+ *   T_b ^= T_a & 0x00000000FFFFFFFF  (key_x and z_operator . e_x: X errors copy control -> target)
+ *   T_a ^= T_b & 0xFFFFFFFF00000000  (key_z and x_operator . e_z: Z errors copy target -> control)
+ * then T_a ^= XOR of its faults' first words, T_b ^= XOR of their second words.  Any other block: its step word is
+ * mask_kind(T_a) ^ (XOR of its faults' local words), then T_a ^= XOR of their tails.  The carried words suffice because T is linear in
+ * the frame and both blocks use the same checks and operators.  A sample's words, nsteps + F: [the EC and MEASURE steps in order]
+ * [F >= 1 flag words].  The MEASURE steps of one frame follow one another (EC steps between them) and form one measurement; a frame is
+ * measured at most once, there is at least one measurement, and all have the same odd number of trials <= GF2_MSTREAM_MAX_TRIALS.
+ *
+ * Tally rule per sample: accepted iff every flag word is zero; one record (K, P) per side AND per data frame; an EC or MEASURE step
+ * updates the record of its own frame by the streamed rule, word for word.  `records` says what a CNOT block does to the records:
+ *   GF2_MSTREAM_REFERENCE    nothing (the rewritten program moves no known-error register through a CNOT)
+ *   GF2_MSTREAM_PROPAGATED   the map above on (K, P): the x side a -> b, the z side b -> a
+ * The words do not depend on `records`.  counts[GF2_MSTREAM_FIELDS]: accepted, wrong_any (some measurement's vote is wrong),
+ * unmatched_x, unmatched_z; then per measurement in program order, four of them: wrong, trial_wrong, first_trial_wrong, split_vote
+ * (zero for an absent measurement) -- all but the first among accepted samples.  Counts of sample ranges add. */
+#define GF2_MSTREAM_FIELDS 20
+#define GF2_MSTREAM_MAX_FRAMES 4
+#define GF2_MSTREAM_MAX_TRIALS 255
+#define GF2_MSTREAM_CNOT 4
+#define GF2_MSTREAM_REFERENCE 0
+#define GF2_MSTREAM_PROPAGATED 1
+typedef struct gf2_mstream gf2_mstream;
+
+/* The words on the host, serial, no GPU needed; faults and words_out as gf2_stream_words_host takes them.  GF2_E_ARG, naming the
+ * limit: the type rules of gf2_stream_words_host; nframes outside [1, GF2_MSTREAM_MAX_FRAMES]; a kind that is not NONE, EC, MEASURE or
+ * CNOT (a FINAL step is named); a frame outside [0, nframes); a CNOT block whose frames coincide or whose type has flag rows; another
+ * block whose second frame is not -1; a frame measured twice; no MEASURE step; measurements of different or even numbers of trials;
+ * L > 2^20; a fault outside [0, L) or of no kind. */
+int gf2_mstream_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                           const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                           int64_t nframes, const int64_t* fault_first, const int32_t* fault_location, const uint8_t* fault_kind, int64_t count,
+                           uint64_t* words_out, int64_t ldw);
+
+/* The tally rule on the host over such words (count x ldw, ldw >= nsteps + flag_words), serial, no GPU needed.  Tables as
+ * gf2_ec_tally_host takes them.  class_out (may be null): one byte per sample, bit 0 accepted, bit 1 wrong_any, bits 2 .. 5 wrong of
+ * measurement 0 .. 3, bit 6 an unmatched key, bit 7 a split vote (0 for a rejected sample).  GF2_E_ARG, naming the limit: r > 31,
+ * the block rules above, records neither REFERENCE nor PROPAGATED, flag_words < 1, a key twice in a table. */
+int gf2_mstream_tally_host(const uint64_t* words, int64_t count, int64_t ldw, const int32_t* block_kind, const int32_t* block_a,
+                           const int32_t* block_b, int64_t nblocks, int64_t nframes, int64_t flag_words, int64_t records, int64_t r1,
+                           const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                           const uint8_t* flips2, int64_t entries2, uint64_t* counts_out, uint8_t* class_out);
+
+/* A sequence on the device.  Argument rules as gf2_mstream_words_host's; in addition no 512-location segment of the sampler may
+ * overlap more than GF2_STREAM_MAX_OVERLAP blocks: GF2_E_ARG, naming it.  Destroyed by gf2_mstream_destroy. */
+int gf2_mstream_create(gf2_ctx* ctx, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                       const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                       int64_t nframes, gf2_mstream** mstream_out);
+int gf2_mstream_destroy(gf2_ctx* ctx, gf2_mstream* mstream);
+
+/* The words of samples first_sample .. first_sample + count - 1, rejected ones included: ldo >= nsteps + F words per sample in
+ * device memory; words past nsteps + F are left as they were.  out_dev: any 8-byte-aligned address. */
+int gf2_mstream_outcomes_dev(gf2_ctx* ctx, const gf2_mstream* mstream, uint64_t seed, int64_t first_sample, int64_t count, double p_x,
+                             double p_y, double p_z, uint64_t* out_dev, int64_t ldo);
+
+/* The tally of those samples on the device, no word stored.  GF2_E_ARG when the sequence's effects set a bit outside the layout
+ * given r_1 and r_2, or records is neither value.  counts_out[GF2_MSTREAM_FIELDS] on the host. */
+int gf2_mc_mstream_decode(gf2_ctx* ctx, const gf2_mstream* mstream, int64_t records, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                          int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed,
+                          int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, uint64_t* counts_out);
+
 /* ---- repeat-until-success: every preparation of a streamed gadget retried on its own ------------------------
  * [build-defined, DESIGN.md section 5d "Repeat-until-success"]  The streamed route gives every preparation one attempt and rejects a
  * sample when any verification fires.  Here a block type is cut into REGIONS, consecutive (first location, count, retried) that

@@ -26,6 +26,8 @@ EC_FIELDS_COUNT, EC_MAX_ROUNDS = 8, 6
 FT_FIELDS_COUNT, FT_MAX_LDR = 7, 16
 STREAM_FIELDS_COUNT, STREAM_MAX_TYPES, STREAM_MAX_OVERLAP = 12, 64, 8
 STREAM_NONE, STREAM_EC, STREAM_MEASURE, STREAM_FINAL = 0, 1, 2, 3
+MSTREAM_FIELDS_COUNT, MSTREAM_MAX_FRAMES, MSTREAM_MAX_TRIALS, MSTREAM_CNOT = 20, 4, 255, 4
+MSTREAM_REFERENCE, MSTREAM_PROPAGATED = 0, 1
 RETRY_FIELDS_COUNT, RETRY_MAX_ATTEMPTS, RETRY_MAX_SIZES = 14, 65536, 16
 RETRY_WAIT_FIELDS_COUNT, RETRY_WAIT_MAX_ROWS = 15, 512
 RETRY_GATE_WAIT_MAX_SIZES = 3
@@ -198,6 +200,13 @@ SIGNATURES = {
     "gf2_stream_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p, _c_i64],
     "gf2_mc_stream_decode": [_p, _p, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
                              ctypes.c_double, _p],
+    "gf2_mstream_words_host": [_p, _p, _p, _c_i64, _p, _p, _p, _p, _c_i64, _c_i64, _p, _p, _p, _c_i64, _p, _c_i64],
+    "gf2_mstream_tally_host": [_p, _c_i64, _c_i64, _p, _p, _p, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _p, _p],
+    "gf2_mstream_create": [_p, _p, _p, _p, _c_i64, _p, _p, _p, _p, _c_i64, _c_i64, _pp],
+    "gf2_mstream_destroy": [_p, _p],
+    "gf2_mstream_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p, _c_i64],
+    "gf2_mc_mstream_decode": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
+                              ctypes.c_double, _p],
     "gf2_retry_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                              _c_i64, _p, _c_i64, _p],
     "gf2_retry_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _pp],
@@ -445,6 +454,7 @@ FT_RULE = Rule("ft", FT_FIELDS_COUNT, lambda nsteps, measure_mask: (int(nsteps),
 CIRCUIT_RULE, STREAM_RULE, RETRY_RULE, RETRY_WAIT_RULE = (Rule(name, fields, lambda: ()) for name, fields in
                                                           (("circuit", 5), ("stream", STREAM_FIELDS_COUNT), ("retry", RETRY_FIELDS_COUNT),
                                                            ("retry_wait", RETRY_WAIT_FIELDS_COUNT)))
+MSTREAM_RULE = Rule("mstream", MSTREAM_FIELDS_COUNT, lambda: ())
 
 
 def _enumerate_tables(keys1, flips1, keys2, flips2, null_flips=False):
@@ -544,6 +554,47 @@ def stream_tally_host(words, block_kind, flag_words, r1, keys1, flips1, r2, keys
     words = _tally_words(words)
     kinds = np.ascontiguousarray(block_kind, dtype=np.int32).reshape(-1)
     return _tally_host(lib().gf2_stream_tally_host, STREAM_RULE, words, (_ptr(kinds), len(kinds), int(flag_words)), (),
+                       (r1, keys1, flips1, r2, keys2, flips2), classes)
+
+
+def _mstream_sequence(type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes):
+    """The arrays of a multi-block sequence as the gf2_mstream_* entry points take them, and their pointer arguments."""
+    keep, seq = _stream_sequence(type_eff, type_locations, type_flags, block_type, block_kind)
+    frames_a = np.ascontiguousarray(block_a, dtype=np.int32).reshape(-1)
+    frames_b = np.ascontiguousarray(block_b, dtype=np.int32).reshape(-1)
+    if len(frames_a) != len(keep[3]) or len(frames_b) != len(keep[3]):
+        raise ValueError("one frame a and one frame b per block")
+    return keep + (frames_a, frames_b), seq[:6] + (_ptr(frames_a), _ptr(frames_b), seq[6], int(nframes))
+
+
+def mstream_words_host(type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes, fault_first, fault_location,
+                       fault_kind, ldw):
+    """gf2_mstream_words_host (host code, no GPU): the (samples, ldw) words of samples of a multi-block program given by their faults
+    -- sample i has faults fault_first[i] .. fault_first[i + 1] - 1, each a location and a kind 1 (X), 2 (Z) or 3 (Y)."""
+    keep, seq = _mstream_sequence(type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes)
+    first = np.ascontiguousarray(fault_first, dtype=np.int64).reshape(-1)
+    where = np.ascontiguousarray(fault_location, dtype=np.int32).reshape(-1)
+    kind = np.ascontiguousarray(fault_kind, dtype=np.uint8).reshape(-1)
+    count = len(first) - 1
+    if count < 0 or len(where) != len(kind) or (count >= 0 and len(first) and int(first[-1]) != len(where)):
+        raise ValueError("fault_first has one entry per sample and one more, the last the number of faults")
+    out = np.zeros((max(1, count), max(1, int(ldw))), dtype="<u8")
+    check(lib().gf2_mstream_words_host(*seq, _ptr(first), _ptr(where) if len(where) else None, _ptr(kind) if len(where) else None, count,
+                                       _ptr(out), int(ldw)))
+    return out[:count]
+
+
+def mstream_tally_host(words, block_kind, block_a, block_b, nframes, flag_words, records, r1, keys1, flips1, r2, keys2, flips2, classes=False):
+    """gf2_mstream_tally_host (host code, no GPU): the twenty counts of the multi-block tally rule over words (count, ldw).
+    classes=True also returns the class byte of every sample."""
+    words = _tally_words(words)
+    kinds = np.ascontiguousarray(block_kind, dtype=np.int32).reshape(-1)
+    frames_a = np.ascontiguousarray(block_a, dtype=np.int32).reshape(-1)
+    frames_b = np.ascontiguousarray(block_b, dtype=np.int32).reshape(-1)
+    if len(frames_a) != len(kinds) or len(frames_b) != len(kinds):
+        raise ValueError("one frame a and one frame b per block")
+    return _tally_host(lib().gf2_mstream_tally_host, MSTREAM_RULE, words,
+                       (_ptr(kinds), _ptr(frames_a), _ptr(frames_b), len(kinds), int(nframes), int(flag_words), int(records)), (),
                        (r1, keys1, flips1, r2, keys2, flips2), classes)
 
 
@@ -1020,6 +1071,19 @@ class Stream(_Handle):
 
 
 
+class MStream(_Handle):
+    """A multi-block sequence on the device (gf2_mstream_create): the block types' tables and the blocks (type, kind, a, b)."""
+    _destroy = "gf2_mstream_destroy"
+
+    def __init__(self, ctx, type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes):
+        self.ctx = ctx
+        keep, seq = _mstream_sequence(type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes)
+        out = ctypes.c_void_p()
+        check(lib().gf2_mstream_create(ctx.handle, *seq, ctypes.byref(out)))
+        self.handle = out.value
+
+
+
 class Retry(_Handle):
     """A block sequence and its regions on the device (gf2_retry_create)."""
     _destroy = "gf2_retry_destroy"
@@ -1394,6 +1458,17 @@ class Context(object):
         """gf2_mc_stream_decode: the twelve counts of the streamed tally over samples [first, first + count)."""
         return _decode(lib().gf2_mc_stream_decode, STREAM_RULE, (self.handle, stream.handle), (), (r1, keys1, flips1, r2, keys2, flips2),
                        seed, first, count, p_x, p_y, p_z)
+
+    def mstream_create(self, type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes):
+        return MStream(self, type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes)
+
+    def mstream_outcomes_dev(self, mstream, seed, first, count, p_x, p_y, p_z, out_buf, ldo):
+        check(lib().gf2_mstream_outcomes_dev(self.handle, mstream.handle, seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, out_buf.ptr, ldo))
+
+    def mc_mstream_decode(self, mstream, records, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z):
+        """gf2_mc_mstream_decode: the twenty counts of the multi-block tally over samples [first, first + count)."""
+        return _decode(lib().gf2_mc_mstream_decode, MSTREAM_RULE, (self.handle, mstream.handle, int(records)), (),
+                       (r1, keys1, flips1, r2, keys2, flips2), seed, first, count, p_x, p_y, p_z)
 
     def retry_create(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions):
         return Retry(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions)

@@ -1564,6 +1564,328 @@ int gf2_stream_tally_host(const uint64_t* words, int64_t count, int64_t ldw, con
 
 }  // extern "C"
 
+// ---- multi-block streamed programs (include/gf2hip.h "multi-block streamed programs") ---------------------
+#include "gf2_mstream_plan.h"
+
+int gf2_mstream_check_records(const char* who, int64_t records) {
+    if (records != GF2_MSTREAM_REFERENCE && records != GF2_MSTREAM_PROPAGATED)
+        GF2_FAIL(GF2_E_ARG, "%s: records must be GF2_MSTREAM_REFERENCE (0) or GF2_MSTREAM_PROPAGATED (1), got %lld", who, (long long)records);
+    return GF2_OK;
+}
+
+int gf2_mstream_block_rules(const char* who, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                            int64_t nframes, MStreamPlan* plan) {
+    if (!block_kind || !block_a || !block_b || !plan) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (nframes < 1 || nframes > GF2_MSTREAM_MAX_FRAMES)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= nframes <= %d data frames (logical qubits), got %lld", who, GF2_MSTREAM_MAX_FRAMES, (long long)nframes);
+    if (nblocks < 1 || nblocks > GF2_CIRCUIT_MAX_LOCATIONS)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= nblocks <= %d blocks, got %lld", who, GF2_CIRCUIT_MAX_LOCATIONS, (long long)nblocks);
+    try {
+        plan->measure.assign((size_t)nblocks, -1);
+        plan->first_trial.assign((size_t)nblocks, 0);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    int64_t trials_of[GF2_MSTREAM_MAX_FRAMES] = {0, 0, 0, 0};        // per frame: its MEASURE steps
+    int64_t frame_of[GF2_MSTREAM_MAX_FRAMES] = {-1, -1, -1, -1};     // per measurement: its frame
+    int64_t measurements = 0, steps = 0;
+    for (int64_t b = 0; b < nblocks; ++b) {
+        const int kind = block_kind[b];
+        if (kind == GF2_STREAM_FINAL) GF2_FAIL(GF2_E_ARG, "%s: block %lld is a FINAL step, this route has none (a program ends with its MEASURE steps)", who, (long long)b);
+        if (kind != GF2_STREAM_NONE && kind != GF2_STREAM_EC && kind != GF2_STREAM_MEASURE && kind != GF2_MSTREAM_CNOT)
+            GF2_FAIL(GF2_E_ARG, "%s: block %lld has kind %d, not NONE (0), EC (1), MEASURE (2) or CNOT (4)", who, (long long)b, kind);
+        if (block_a[b] < 0 || block_a[b] >= nframes)
+            GF2_FAIL(GF2_E_ARG, "%s: block %lld has frame %lld outside [0, nframes = %lld)", who, (long long)b, (long long)block_a[b], (long long)nframes);
+        if (kind == GF2_MSTREAM_CNOT) {
+            if (block_b[b] < 0 || block_b[b] >= nframes)
+                GF2_FAIL(GF2_E_ARG, "%s: CNOT block %lld has target frame %lld outside [0, nframes = %lld)", who, (long long)b, (long long)block_b[b], (long long)nframes);
+            if (block_b[b] == block_a[b]) GF2_FAIL(GF2_E_ARG, "%s: CNOT block %lld has frame %lld as control and as target", who, (long long)b, (long long)block_a[b]);
+        } else if (block_b[b] != -1) {
+            GF2_FAIL(GF2_E_ARG, "%s: block %lld is no CNOT block, its second frame must be -1, got %lld", who, (long long)b, (long long)block_b[b]);
+        }
+        steps += kind == GF2_STREAM_EC || kind == GF2_STREAM_MEASURE;
+        if (kind != GF2_STREAM_MEASURE) continue;
+        const int64_t f = block_a[b];
+        if (measurements == 0 || frame_of[measurements - 1] != f) {
+            if (trials_of[f] != 0)
+                GF2_FAIL(GF2_E_ARG, "%s: frame %lld is measured twice (MEASURE block %lld; the MEASURE steps of a frame follow one another)", who, (long long)f, (long long)b);
+            frame_of[measurements++] = f;                             // (at most nframes <= 4 of them: every frame once)
+            plan->first_trial[(size_t)b] = 1;
+        }
+        plan->measure[(size_t)b] = (int32_t)(measurements - 1);
+        trials_of[f] += 1;
+    }
+    if (measurements < 1) GF2_FAIL(GF2_E_ARG, "%s: a sequence needs at least one MEASURE step", who);
+    const int64_t trials = trials_of[frame_of[0]];
+    for (int64_t m = 0; m < measurements; ++m)
+        if (trials_of[frame_of[m]] != trials || trials % 2 == 0 || trials > GF2_MSTREAM_MAX_TRIALS)
+            GF2_FAIL(GF2_E_ARG, "%s: every measurement needs the same odd number of MEASURE steps (a majority vote), at most %d; measurement %lld has %lld, "
+                     "measurement 0 has %lld", who, GF2_MSTREAM_MAX_TRIALS, (long long)m, (long long)trials_of[frame_of[m]], (long long)trials);
+    plan->nframes = nframes;
+    plan->measurements = measurements;
+    plan->seq.trials = trials;
+    plan->seq.nsteps = steps;
+    plan->seq.has_final = false;
+    return GF2_OK;
+}
+
+// The type-table rules, the OR of every type's words, the start / step / flag fill and the flag-bit check below restate
+// gf2_stream_plan's on purpose: that function and its messages keep their text, and this route differs in what a block may be (no FINAL
+// step, CNOT blocks without a step word or flag rows, any_cnot beside any_local / any_tail).  A rule changed in one is changed in the
+// other; tests/test_multi_stream.py pins every message of this copy, tests/test_stream.py those of the original.
+int gf2_mstream_plan(const char* who, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                     const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                     int64_t nframes, MStreamPlan* plan) {
+    if (!type_eff || !type_locations || !type_flags || !block_type || !block_kind || !block_a || !block_b || !plan) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (ntypes < 1 || ntypes > GF2_STREAM_MAX_TYPES)
+        GF2_FAIL(GF2_E_ARG, "%s: needs 1 <= ntypes <= %d block types, got %lld", who, GF2_STREAM_MAX_TYPES, (long long)ntypes);
+    if (int rc = gf2_mstream_block_rules(who, block_kind, block_a, block_b, nblocks, nframes, plan)) return rc;
+    StreamPlan& seq = plan->seq;
+    std::vector<uint64_t> any;
+    try {
+        seq.type_offset.assign((size_t)ntypes, 0);
+        seq.start.assign((size_t)nblocks + 1, 0);
+        seq.step.assign((size_t)nblocks, -1);
+        seq.flag.assign((size_t)nblocks, 0);
+        any.assign((size_t)ntypes * 3, 0);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    int64_t table = 0;
+    for (int64_t t = 0; t < ntypes; ++t) {
+        if (type_locations[t] < 1 || type_locations[t] > GF2_CIRCUIT_MAX_LOCATIONS)
+            GF2_FAIL(GF2_E_ARG, "%s: block type %lld needs 1 <= locations <= %d (2^20), got %lld", who, (long long)t, GF2_CIRCUIT_MAX_LOCATIONS,
+                     (long long)type_locations[t]);
+        if (type_flags[t] < 0 || type_flags[t] > 64)
+            GF2_FAIL(GF2_E_ARG, "%s: block type %lld has %lld flag rows, a block holds at most 64 (one flag word)", who, (long long)t,
+                     (long long)type_flags[t]);
+        seq.type_offset[(size_t)t] = table;
+        table += type_locations[t];
+        if (table > GF2_CIRCUIT_MAX_LOCATIONS)
+            GF2_FAIL(GF2_E_ARG, "%s: the block types have more than %d (2^20) locations in all", who, GF2_CIRCUIT_MAX_LOCATIONS);
+    }
+    for (int64_t t = 0; t < ntypes; ++t)                                 // OR of every type's three words
+        for (int64_t i = 0; i < 2 * type_locations[t]; ++i)
+            for (int q = 0; q < 3; ++q) any[(size_t)(3 * t + q)] |= type_eff[(2 * seq.type_offset[(size_t)t] + i) * 3 + q];
+    seq.any_tail = 0;
+    for (int k = 0; k < 4; ++k) seq.any_local[k] = 0;
+    plan->any_cnot[0] = plan->any_cnot[1] = 0;
+    int64_t at = 0, steps = 0, rows = 0;
+    for (int64_t b = 0; b < nblocks; ++b) {
+        const int kind = block_kind[b];
+        const int64_t t = block_type[b];
+        if (t < 0 || t >= ntypes) GF2_FAIL(GF2_E_ARG, "%s: block %lld has type %lld outside [0, %lld)", who, (long long)b, (long long)t, (long long)ntypes);
+        seq.start[(size_t)b] = (int32_t)at;
+        seq.flag[(size_t)b] = (int32_t)rows;
+        if (kind == GF2_STREAM_EC || kind == GF2_STREAM_MEASURE) seq.step[(size_t)b] = (int32_t)steps++;
+        if (kind == GF2_MSTREAM_CNOT && type_flags[t] != 0)
+            GF2_FAIL(GF2_E_ARG, "%s: CNOT block %lld has a type with %lld flag rows, a CNOT block has none", who, (long long)b, (long long)type_flags[t]);
+        at += type_locations[t];
+        rows += type_flags[t];
+        if (at > GF2_CIRCUIT_MAX_LOCATIONS)
+            GF2_FAIL(GF2_E_ARG, "%s: the sequence has more than L = %d (2^20) fault locations", who, GF2_CIRCUIT_MAX_LOCATIONS);
+        if (kind == GF2_MSTREAM_CNOT) {
+            plan->any_cnot[0] |= any[(size_t)(3 * t)];
+            plan->any_cnot[1] |= any[(size_t)(3 * t + 1)];
+        } else {
+            seq.any_local[kind] |= any[(size_t)(3 * t)];
+            seq.any_tail |= any[(size_t)(3 * t + 1)];
+        }
+        if (type_flags[t] < 64 && (any[(size_t)(3 * t + 2)] >> type_flags[t]) != 0)
+            GF2_FAIL(GF2_E_ARG, "%s: the effects of block type %lld set flag bits at or above its %lld flag rows", who, (long long)t, (long long)type_flags[t]);
+    }
+    seq.start[(size_t)nblocks] = (int32_t)at;
+    seq.locations = at;
+    seq.flag_rows = rows;
+    seq.flag_words = rows > 64 ? (rows + 63) / 64 : 1;
+    return GF2_OK;
+}
+
+int gf2_mstream_check_bits(const char* who, const MStreamPlan& plan, int64_t r1, int64_t r2) {
+    GadgetRule rule;
+    if (int rc = gadget_rule_keys(who, r1, r2, &rule)) return rc;
+    const StreamPlan& seq = plan.seq;
+    const uint64_t key_x = rule.mask[0], keys = key_x | rule.mask[1] << 32, frame = keys | 1ull << 31 | 1ull << 63;
+    if (seq.any_local[GF2_STREAM_NONE] || (seq.any_local[GF2_STREAM_EC] & ~keys) || (seq.any_local[GF2_STREAM_MEASURE] & ~(key_x | 1ull << 31)) ||
+        (seq.any_tail & ~frame) || (plan.any_cnot[0] & ~frame) || (plan.any_cnot[1] & ~frame))
+        GF2_FAIL(GF2_E_ARG, "%s: the effects set bits beyond the layout (a NONE block no local bit, an EC step's r_2 / r_1 key bits, a MEASURE step's r_2 key "
+                 "bits and bit 31, a tail's key bits and the two parity bits)", who);
+    return GF2_OK;
+}
+
+int gf2_mstream_check_overlap(const char* who, const MStreamPlan& plan, int64_t nblocks) {
+    const StreamPlan& seq = plan.seq;
+    for (int64_t seg = 0, lo = 0; seg * 512 < seq.locations; ++seg) {
+        const int64_t seg_start = seg * 512, seg_end = seg_start + 512 < seq.locations ? seg_start + 512 : seq.locations;
+        while (seq.start[(size_t)lo + 1] <= seg_start) lo += 1;
+        int64_t hi = lo;
+        while (hi + 1 < nblocks && seq.start[(size_t)hi + 1] < seg_end) hi += 1;
+        if (hi - lo + 1 > GF2_STREAM_MAX_OVERLAP)
+            GF2_FAIL(GF2_E_ARG, "%s: locations %lld .. %lld (one 512-location segment of the sampler) overlap %lld blocks, more than %d (GF2_STREAM_MAX_OVERLAP)",
+                     who, (long long)seg_start, (long long)seg_end - 1, (long long)(hi - lo + 1), GF2_STREAM_MAX_OVERLAP);
+    }
+    return GF2_OK;
+}
+
+namespace {
+// One sample of the multi-block tally rule: stream_tally_sample's record (K, P) per side, kept per data frame; the blocks in order,
+// because a CNOT block moves the records when `records` says so.  w: the sample's words, [steps] [flag words].
+uint8_t mstream_tally_sample(const uint64_t* w, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                             const MStreamPlan& plan, int64_t flag_words, int64_t records, const uint64_t* mask, const HostTable* tab, uint64_t* counts) {
+    const int64_t nsteps = plan.seq.nsteps, trials = plan.seq.trials;
+    uint64_t flags = 0;
+    for (int64_t q = 0; q < flag_words; ++q) flags |= w[nsteps + q];
+    if (flags) return 0;
+    uint64_t K[GF2_MSTREAM_MAX_FRAMES][2] = {}, P[GF2_MSTREAM_MAX_FRAMES][2] = {}, unmatched[2] = {0, 0};
+    int64_t wrong_trials[GF2_MSTREAM_MAX_FRAMES] = {0, 0, 0, 0};
+    bool first_wrong[GF2_MSTREAM_MAX_FRAMES] = {false, false, false, false};
+    int64_t s = 0;
+    for (int64_t b = 0; b < nblocks; ++b) {
+        const int kind = block_kind[b], fa = block_a[b];
+        if (kind == GF2_MSTREAM_CNOT) {
+            if (records == GF2_MSTREAM_PROPAGATED) {
+                const int fb = block_b[b];
+                K[fb][0] ^= K[fa][0], P[fb][0] ^= P[fa][0];              // the x side goes a -> b
+                K[fa][1] ^= K[fb][1], P[fa][1] ^= P[fb][1];              // the z side goes b -> a
+            }
+            continue;
+        }
+        if (kind == GF2_STREAM_NONE) continue;
+        const bool measure = kind == GF2_STREAM_MEASURE;
+        for (int c = 0; c < (measure ? 1 : 2); ++c) {
+            const uint64_t v = ((w[s] >> (32 * c)) & mask[c]) ^ K[fa][c];
+            const int found = tab[c].find(0, v);
+            if (found < 0)
+                unmatched[c] += 1;                                       // css_code.py:655-657: no match, nothing recorded
+            else
+                K[fa][c] ^= v, P[fa][c] ^= (uint64_t)found;
+        }
+        if (measure) {
+            const int m = plan.measure[(size_t)b];
+            const bool bad = (((w[s] >> 31) & 1ull) ^ P[fa][0]) != 0;
+            if (plan.first_trial[(size_t)b]) first_wrong[m] = bad;
+            wrong_trials[m] += bad;
+        }
+        s += 1;
+    }
+    bool any = false, any_split = false;
+    counts[0] += 1;
+    for (int64_t m = 0; m < plan.measurements; ++m) {
+        const bool wrong = 2 * wrong_trials[m] > trials, split = wrong_trials[m] != 0 && wrong_trials[m] != trials;
+        counts[4 + 4 * m] += wrong;
+        counts[5 + 4 * m] += (uint64_t)wrong_trials[m];
+        counts[6 + 4 * m] += first_wrong[m];
+        counts[7 + 4 * m] += split;
+        any |= wrong, any_split |= split;
+    }
+    counts[1] += any;
+    counts[2] += unmatched[0];
+    counts[3] += unmatched[1];
+    uint8_t cls = (uint8_t)(1 | any << 1 | (unmatched[0] || unmatched[1]) << 6 | any_split << 7);
+    for (int64_t m = 0; m < plan.measurements; ++m) cls |= (uint8_t)((2 * wrong_trials[m] > trials) << (2 + m));
+    return cls;
+}
+}  // namespace
+
+extern "C" {
+
+// The definition of gf2_mstream_outcomes_dev's words given a sample's faults, serial: the faults are XOR-ed
+// into the three words of their blocks, then the blocks are closed in order -- a CNOT block applies the frame map to (T_a, T_b) and
+// XORs its two tails, any other block is gf2_stream_words_host's rule on T_a.
+int gf2_mstream_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                           const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                           int64_t nframes, const int64_t* fault_first, const int32_t* fault_location, const uint8_t* fault_kind, int64_t count,
+                           uint64_t* words_out, int64_t ldw) {
+    const char* who = "gf2_mstream_words_host";
+    MStreamPlan mplan;
+    if (int rc = gf2_mstream_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, block_a, block_b, nblocks, nframes, &mplan)) return rc;
+    const StreamPlan& plan = mplan.seq;
+    const int64_t ldr = plan.nsteps + plan.flag_words;
+    if (count < 0 || ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: needs count >= 0 samples of ldw >= nsteps + F = %lld words", who, (long long)ldr);
+    if (count == 0) return GF2_OK;
+    if (!fault_first || !words_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    if (fault_first[0] != 0) GF2_FAIL(GF2_E_ARG, "%s: fault_first[0] must be 0", who);
+    for (int64_t i = 0; i < count; ++i)
+        if (fault_first[i + 1] < fault_first[i]) GF2_FAIL(GF2_E_ARG, "%s: fault_first must not descend (sample %lld)", who, (long long)i);
+    const int64_t nfaults = fault_first[count];
+    if (nfaults > 0 && (!fault_location || !fault_kind)) GF2_FAIL(GF2_E_ARG, "%s: null fault list", who);
+    for (int64_t f = 0; f < nfaults; ++f) {
+        if (fault_location[f] < 0 || fault_location[f] >= plan.locations)
+            GF2_FAIL(GF2_E_ARG, "%s: fault %lld is at location %lld outside [0, L = %lld)", who, (long long)f, (long long)fault_location[f], (long long)plan.locations);
+        if (fault_kind[f] < 1 || fault_kind[f] > 3) GF2_FAIL(GF2_E_ARG, "%s: fault %lld has kind %d, not 1 (X), 2 (Z) or 3 (Y)", who, (long long)f, (int)fault_kind[f]);
+    }
+    std::vector<uint64_t> acc;
+    try {
+        acc.assign((size_t)nblocks * 3, 0);
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    for (int64_t i = 0; i < count; ++i) {
+        uint64_t* out = words_out + i * ldw;
+        for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
+        for (int64_t f = fault_first[i]; f < fault_first[i + 1]; ++f) {
+            const int32_t g = fault_location[f];
+            const int64_t b = (std::upper_bound(plan.start.begin(), plan.start.end(), g) - plan.start.begin()) - 1;   // start[b] <= g < start[b + 1]
+            const uint64_t* e = type_eff + (size_t)(plan.type_offset[(size_t)block_type[b]] + (g - plan.start[(size_t)b])) * 6;
+            for (int comp = 0; comp < 2; ++comp)
+                if (fault_kind[f] >> comp & 1)
+                    for (int q = 0; q < 3; ++q) acc[(size_t)(3 * b + q)] ^= e[3 * comp + q];
+        }
+        uint64_t T[GF2_MSTREAM_MAX_FRAMES] = {0, 0, 0, 0};
+        for (int64_t b = 0; b < nblocks; ++b) {
+            uint64_t* a = &acc[(size_t)(3 * b)];
+            uint64_t& Ta = T[block_a[b]];
+            if (block_kind[b] == GF2_MSTREAM_CNOT) {
+                uint64_t& Tb = T[block_b[b]];
+                gf2_mstream_cnot_map(&Ta, &Tb);
+                Ta ^= a[0], Tb ^= a[1];                                  // a CNOT block's words: the tail for frame a, the tail for frame b
+            } else {
+                if (plan.step[(size_t)b] >= 0) out[plan.step[(size_t)b]] = (Ta & gf2_stream_frame_mask(block_kind[b])) ^ a[0];
+                if (a[2]) {
+                    const int64_t row = plan.flag[(size_t)b];
+                    out[plan.nsteps + (row >> 6)] |= a[2] << (row & 63);
+                    if (row & 63) {
+                        const uint64_t over = a[2] >> (64 - (row & 63));
+                        if (over) out[plan.nsteps + (row >> 6) + 1] |= over;
+                    }
+                }
+                Ta ^= a[1];
+            }
+            a[0] = a[1] = a[2] = 0;
+        }
+    }
+    return GF2_OK;
+}
+
+// The tally rule of a multi-block program over its words, serial.
+int gf2_mstream_tally_host(const uint64_t* words, int64_t count, int64_t ldw, const int32_t* block_kind, const int32_t* block_a,
+                           const int32_t* block_b, int64_t nblocks, int64_t nframes, int64_t flag_words, int64_t records, int64_t r1,
+                           const uint64_t* keys1, const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2,
+                           const uint8_t* flips2, int64_t entries2, uint64_t* counts_out, uint8_t* class_out) {
+    const char* who = "gf2_mstream_tally_host";
+    if (!counts_out) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
+    GadgetRule rule;
+    if (int rc = gadget_rule_keys(who, r1, r2, &rule)) return rc;
+    if (int rc = gf2_mstream_check_records(who, records)) return rc;
+    MStreamPlan plan;
+    if (int rc = gf2_mstream_block_rules(who, block_kind, block_a, block_b, nblocks, nframes, &plan)) return rc;
+    const int64_t ldr = plan.seq.nsteps + flag_words;
+    if (flag_words < 1) GF2_FAIL(GF2_E_ARG, "%s: needs F >= 1 flag words, got %lld", who, (long long)flag_words);
+    if (count < 0 || ldw < ldr || (count > 0 && !words)) GF2_FAIL(GF2_E_ARG, "%s: needs count >= 0 samples of ldw >= nsteps + F = %lld words", who, (long long)ldr);
+    if (int rc = check_table_args(who, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    for (int k = 0; k < GF2_MSTREAM_FIELDS; ++k) counts_out[k] = 0;
+    if (count == 0) return GF2_OK;
+    HostTable tab[2];
+    if (int rc = make_host_tables(who, tab, keys1, flips1, entries1, keys2, flips2, entries2)) return rc;
+    for (int64_t i = 0; i < count; ++i) {
+        const uint8_t cls = mstream_tally_sample(words + i * ldw, block_kind, block_a, block_b, nblocks, plan, flag_words, records, rule.mask, tab, counts_out);
+        if (class_out) class_out[i] = cls;
+    }
+    return GF2_OK;
+}
+
+}  // extern "C"
+
 // ---- repeat-until-success (include/gf2hip.h "repeat-until-success") -----------------------------------
 #include "gf2_retry_plan.h"
 

@@ -530,6 +530,16 @@ class CSSCode(QECC):
         gadget = stream_noise.stream_for(self, "program", ft_noise.check_ops(ops))
         return gadget.error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample)
 
+    def logical_circuit_error_rates(self, instructions, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, records='reference'):
+        """[build-defined]  How often the bits measured by ftqc.rewrite_program of a program on up to four logical qubits --
+        `instructions`: ('I' | 'X' | 'Y' | 'Z', q) and ('CNOT', a, b), then ('MEASURE', q) on distinct qubits -- are wrong when every
+        fault location of the rewritten program fails independently (stream_noise.MultiProgram.error_rates has the dict).
+        records='propagated' moves the records of known errors through a CNOT as the CNOT moves the errors; the rewritten program
+        does not ('reference').  ft_noise.raw_circuit_error_rate is the bare program's side of the comparison."""
+        from . import stream_noise
+        gadget = stream_noise.multi_program_for(self, instructions)
+        return gadget.error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample, records=records)
+
     def error_correct_retried_error_rates(self, num_samples, p_x, p_y, p_z, rounds, seed=0, first_sample=0, idle_data=False, max_attempts=256):
         """[build-defined]  error_correct_streamed_error_rates with every preparation retried on its own until its verifications
         pass (stream_noise.StreamedGadget.retry_error_rates), as the reference's while_do loops run them: essentially every sample is

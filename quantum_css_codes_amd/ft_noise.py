@@ -22,7 +22,9 @@ quil_classical_correct's (css_code.py:649-685) record of known errors run throug
 data.x_errors -- and a majority vote over the trials; gf2_ft_tally_host is its serial form and gf2_mc_ft_decode the device kernel.
 
 Only the Paulis are accepted.  A Clifford gate that moves the known-error registers (a logical H swaps the roles of x_errors and
-z_errors, which the reference itself does not do) is a different model.
+z_errors, which the reference itself does not do) is a different model.  Programs on several logical qubits with the transversal
+CNOT are stream_noise.MultiProgram's; check_instructions, instructions_of_quil and raw_circuit_error_rate here are its program
+checker, its quil front end and the bare program's side of its comparison.
 """
 import numpy as np
 
@@ -164,6 +166,85 @@ def program_for(code, ops):
     if key not in cache:
         cache[key] = FTProgram(code, key)
     return cache[key]
+
+
+MAX_LOGICAL_QUBITS = _native.MSTREAM_MAX_FRAMES
+
+
+def check_instructions(instructions):
+    """The instructions of a multi-qubit program (stream_noise.MultiProgram) as a tuple of ('I' | 'X' | 'Y' | 'Z', q), ('CNOT', a, b)
+    with a != b and ('MEASURE', q), and the sorted qubit indices that appear: gates first, then one or more MEASUREs on distinct
+    qubits and nothing after them, 1 <= Q <= MAX_LOGICAL_QUBITS qubits.  UnsupportedProgramError, naming the instruction, for
+    anything else."""
+    out, measured, qubits = [], [], set()
+    index = lambda q: isinstance(q, (int, np.integer)) and not isinstance(q, bool) and q >= 0
+    for inst in instructions:
+        inst = tuple(inst) if isinstance(inst, (tuple, list)) else (inst,)
+        name, operands = (inst[0], inst[1:]) if inst else (None, ())
+        if name in PAULIS and len(operands) == 1 and index(operands[0]):
+            shape = "gate"
+        elif name == 'CNOT' and len(operands) == 2 and index(operands[0]) and index(operands[1]) and operands[0] != operands[1]:
+            shape = "gate"
+        elif name == 'MEASURE' and len(operands) == 1 and index(operands[0]):
+            shape = "measure"
+        else:
+            raise UnsupportedProgramError("unsupported instruction: %r (the fault model takes the logical gates I, X, Y, Z and CNOT on "
+                                          "distinct qubits, then MEASUREs)" % (inst,))
+        if shape == "gate" and measured:
+            raise UnsupportedProgramError("unsupported instruction after a MEASURE: %r" % (inst,))
+        if shape == "measure":
+            if int(operands[0]) in measured:
+                raise UnsupportedProgramError("unsupported instruction: %r (qubit %d is measured twice)" % (inst, operands[0]))
+            measured.append(int(operands[0]))
+        qubits.update(int(q) for q in operands)
+        if len(qubits) > MAX_LOGICAL_QUBITS:
+            raise UnsupportedProgramError("unsupported instruction: %r (the fault model takes at most %d logical qubits)"
+                                          % (inst, MAX_LOGICAL_QUBITS))
+        out.append((name,) + tuple(int(q) for q in operands))
+    if not measured:
+        raise UnsupportedProgramError("unsupported program: it must end with a MEASURE")
+    return tuple(out), sorted(qubits)
+
+
+def instructions_of_quil(raw_prog):
+    """The instructions of a quil.Program of the accepted shape (DECLAREs; I, X, Y, Z and CNOT; then MEASUREs) as check_instructions
+    takes them; UnsupportedProgramError, naming the instruction, for anything else."""
+    out = []
+    for inst in raw_prog.instructions:
+        if inst[0] == "DECLARE":
+            continue
+        if inst[0] == "GATE" and (inst[1] in PAULIS or inst[1] == "CNOT") and all(isinstance(q, (int, np.integer)) for q in inst[2]):
+            out.append((inst[1],) + tuple(inst[2]))
+        elif inst[0] == "MEASURE" and isinstance(inst[1], (int, np.integer)):
+            out.append(("MEASURE", inst[1]))
+        else:
+            raise UnsupportedProgramError("unsupported instruction: {}".format(inst))
+    return check_instructions(out)[0]
+
+
+def raw_circuit_error_rate(instructions, p_x, p_y, p_z):
+    """Per MEASURE of the bare program, in program order, the probability that its bit is wrong under the same fault model:
+    raw_program_error_rate with one location per Pauli other than I, one per operand of a CNOT (a fault follows its gate) and one
+    before every measurement.  An X component copies from control to target through every later CNOT; the bit is wrong iff an odd
+    number of the m locations whose X component reaches the measured qubit carry an X or a Y: (1 - (1 - 2 (p_x + p_y))^m) / 2.  p_z
+    does not enter."""
+    instructions, qubits = check_instructions(instructions)
+    reach = {q: set() for q in qubits}                              # the locations whose X component sits on q, modulo 2
+    locations, out = 0, []
+    for inst in instructions:
+        if inst[0] == 'CNOT':
+            a, b = inst[1:]
+            reach[b] ^= reach[a]
+            reach[a] ^= {locations}
+            reach[b] ^= {locations + 1}
+            locations += 2
+        elif inst[0] == 'MEASURE':
+            out.append(0.5 * (1.0 - (1.0 - 2.0 * (float(p_x) + float(p_y))) ** (len(reach[inst[1]]) + 1)))
+            locations += 1
+        elif inst[0] != 'I':
+            reach[inst[1]] ^= {locations}
+            locations += 1
+    return out
 
 
 def raw_program_error_rate(ops, p_x, p_y, p_z):

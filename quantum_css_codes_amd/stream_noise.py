@@ -42,6 +42,11 @@ BlockType.waits gives every retried region its wait rows, one per qubit of the d
 every attempt made of the region, the failed ones included, draws them with memory error rates (q_x, q_y, q_z) of their own.
 The retry_gate_wait_* methods do the same under gate-level faults (DESIGN.md section 5d "Repeat-until-success with waiting faults
 under gate-level faults"): retry_gate_*'s walk and draw plus retry_wait_*'s wait draw.
+
+MultiProgram is the same walk for rewritten programs on up to four logical qubits with the transversal CNOT (DESIGN.md section 5d
+"Multi-block programs"): one data frame T per logical qubit, the existing block types serving frame a, and one new block type and
+kind, CNOT, whose closing applies T_b ^= T_a & 0x00000000FFFFFFFF, T_a ^= T_b & 0xFFFFFFFF00000000 to the two carried words and then
+XORs its faults' two tails.  Post-selected only: the retried, gate-level and waiting variants are those of one qubit.
 """
 import numpy as np
 
@@ -570,6 +575,286 @@ class StreamedGadget(object):
         uint32 attempts of every preparation in order, 0 for one never reached.  tally_host on words[:, :ldw] completes the statement."""
         return _native.retry_gate_wait_words_host(*self._retry_gate_wait_sequence(wait_steps), seed, first_sample, num_samples, p1, p2, q_x, q_y,
                                                   q_z, max_attempts, self.ldw + 2, self.preparations)
+
+
+CNOT = _native.MSTREAM_CNOT
+MULTI_FIELDS = ('accepted', 'wrong_any', 'unmatched_x', 'unmatched_z')
+MEASUREMENT_FIELDS = ('wrong', 'trial_wrong', 'first_trial_wrong', 'split_vote')
+RECORDS = {'reference': _native.MSTREAM_REFERENCE, 'propagated': _native.MSTREAM_PROPAGATED}
+_LOW, _HIGH = np.uint64(0x00000000FFFFFFFF), np.uint64(0xFFFFFFFF00000000)
+
+
+def _emit_pauli(qubits):
+    """The physical Paulis of a logical gate alone, one IDLE location each (a block of kind NONE)."""
+    def emit(build):
+        build.gates.extend((GATE_IDLE, build.data[q], 0) for q in qubits)
+    return emit
+
+
+class CnotBlockType(object):
+    """The block type of a transversal CNOT: `gates`, n rows (GATE_CNOT, i, n + i) on the 2n qubits of the data blocks a (0 .. n-1)
+    and b (n .. 2n-1); `locations` (2n, 2); no flag rows; `effects` (2n, 2, 3) uint64: (the tail the fault leaves on frame a, the
+    tail it leaves on frame b, 0) of an X and of a Z fault, from gf2_circuit_effects_timed on this gate list with the final-frame
+    rows of block a in word 0 and of block b in word 1."""
+
+    def __init__(self, code):
+        n, r_1, r_2 = int(code.n), int(code.r_1), int(code.r_2)
+        h_1, h_2 = np.asarray(code.parity_check_c1), np.asarray(code.parity_check_c2)
+        z_op, x_op = np.asarray(code.z_operator_matrix())[0], np.asarray(code.x_operator_matrix())[0]
+        self.name, self.kind, self.num_flags = "CNOT", CNOT, 0
+        self.gates = np.array([(GATE_CNOT, i, n + i) for i in range(n)], dtype=np.int32).reshape(-1, 3)
+        rows_x = np.zeros((64 * 3, 2 * n), dtype=np.uint8)
+        rows_z = np.zeros_like(rows_x)
+        for word in range(2):                                       # the tail's layout (BlockType's word 1), once per data block
+            block = slice(word * n, (word + 1) * n)
+            for i in range(r_2):
+                rows_x[64 * word + r_2 - 1 - i, block] = h_2[i] & 1
+            rows_x[64 * word + 31, block] = z_op & 1
+            for i in range(r_1):
+                rows_z[64 * word + 32 + r_1 - 1 - i, block] = h_1[i] & 1
+            rows_z[64 * word + 63, block] = x_op & 1
+        self._rows = (2 * n, list(range(n)), _native.pack_rows(rows_x), _native.pack_rows(rows_z), np.full(64 * 3, n, dtype=np.int64))
+        self.effects, self.locations = _native.circuit_effects_timed(self.gates, 2 * n, *self._rows[2:], ldr=3)
+
+    @property
+    def num_locations(self):
+        return len(self.locations)
+
+
+class MultiProgram(object):
+    """A rewritten program on 1 <= Q <= 4 logical qubits with the transversal CNOT, prepared for the Monte-Carlo (DESIGN.md section
+    5d "Multi-block programs").  `instructions` as ft_noise.check_instructions takes them; `qubits`, the sorted logical qubit
+    indices (data frame f serves qubits[f]).  The block sequence mirrors ftqc.rewrite_program step for step:
+        prep(D_q, zero) verified by A1 for every block in index order                 -- NONE blocks
+        per gate: a Pauli's IDLE locations on its block, or the n physical CNOTs D_a[i] -> D_b[i] (a CNOT block), then one round of
+        error_correct on every block in index order                                   -- EC blocks
+        per MEASURE, 2t + 1 times: the MEASURE trial on D_q, then a round of error_correct on every block in index order
+    The data blocks wait at no cost while another block is served: the project's standing convention (ec_noise's docstring).
+    A Pauli on the first block shares StreamedGadget.program's type "logical P, EC" with the round that follows it; on another
+    block its IDLE locations are a block of kind NONE of their own, so that the locations keep the emitted program's order.
+
+    `types`, `block_type`, `block_kind`, `block_a`, `block_b` (-1 unless a CNOT block), `block_start`, `block_step`, `block_flag`,
+    `nsteps`, `flag_words`, `ldw` as StreamedGadget's; `measured`, the measured qubits in program order."""
+
+    def __init__(self, code, instructions):
+        self.code = code
+        self.instructions, self.qubits = ft_noise.check_instructions(instructions)
+        frame = {q: f for f, q in enumerate(self.qubits)}
+        self.nframes = len(self.qubits)
+        types, index = [], {}
+
+        def use(name, kind, emit):
+            if name not in index:
+                index[name] = len(types)
+                types.append(CnotBlockType(code) if kind == CNOT else BlockType(code, name, kind, emit))
+            return index[name]
+
+        blocks = []                                                 # (type, kind, a, b)
+
+        def correct_all(first="EC", emit=_emit_ec(())):             # ftqc.py:112-114: every block, in index order
+            for f in range(self.nframes):
+                blocks.append((use(first, EC, emit) if f == 0 else use("EC", EC, _emit_ec(())), EC, f, -1))
+
+        for f in range(self.nframes):                               # ftqc.py:50-51
+            blocks.append((use("prepare data", NONE, _emit_prepare), NONE, f, -1))
+        self.measured = []
+        for inst in self.instructions:                              # ftqc.py:53-61
+            name = inst[0]
+            if name == 'CNOT':
+                blocks.append((use("CNOT", CNOT, None), CNOT, frame[inst[1]], frame[inst[2]]))
+                correct_all()
+            elif name == 'MEASURE':
+                self.measured.append(inst[1])
+                for _ in range(2 * int(code.t) + 1):                # css_code.py:576-579
+                    blocks.append((use("MEASURE trial", MEASURE, _emit_measure), MEASURE, frame[inst[1]], -1))
+                    correct_all()
+            else:
+                paulis = ft_noise.logical_pauli_qubits(code, name)
+                if paulis and frame[inst[1]] == 0:
+                    correct_all("logical %s, EC" % name, _emit_ec(paulis))
+                else:
+                    if paulis:
+                        blocks.append((use("logical %s" % name, NONE, _emit_pauli(paulis)), NONE, frame[inst[1]], -1))
+                    correct_all()
+        self.types = types
+        self.block_type, self.block_kind, self.block_a, self.block_b = (np.array(col, dtype=np.int32) for col in zip(*blocks))
+        sizes = np.array([types[t].num_locations for t in self.block_type], dtype=np.int64)
+        flags = np.array([types[t].num_flags for t in self.block_type], dtype=np.int64)
+        self.block_start = np.concatenate([[0], np.cumsum(sizes)])
+        self.block_flag = np.concatenate([[0], np.cumsum(flags)])[:-1]
+        has_step = (self.block_kind == EC) | (self.block_kind == MEASURE)
+        self.block_step = np.where(has_step, np.cumsum(has_step) - 1, -1)
+        self.num_locations = int(self.block_start[-1])
+        self.nsteps = int(has_step.sum())
+        self.flag_rows = int(flags.sum())
+        self.flag_words = max(1, (self.flag_rows + 63) // 64)
+        self.ldw = self.nsteps + self.flag_words
+        self.trials = 2 * int(code.t) + 1
+        if not 1 <= self.num_locations <= circuit_noise.MAX_LOCATIONS:
+            raise ValueError("the Monte-Carlo needs 1 <= L <= %d (2^20) fault locations, the program has %d"
+                             % (circuit_noise.MAX_LOCATIONS, self.num_locations))
+        self.type_eff = np.ascontiguousarray(np.concatenate([t.effects for t in types]))
+        self.type_locations = np.array([t.num_locations for t in types], dtype=np.int64)
+        self.type_flags = np.array([t.num_flags for t in types], dtype=np.int64)
+        self._device = None
+
+    @classmethod
+    def from_quil(cls, raw_prog, code):
+        """The model of ftqc.rewrite_program(raw_prog, code) for a quil.Program of the accepted shape (ft_noise.instructions_of_quil)."""
+        return cls(code, ft_noise.instructions_of_quil(raw_prog))
+
+    # -- the whole program ----------------------------------------------------------------------------------------------------
+    def _block_qubits(self, b):
+        """The program's qubit of every qubit of block b's gate list: D_f = f n .., A1 = Q n .., A2 = (Q + 1) n .. (the order in which
+        rewrite_program allocates them)."""
+        n, q = int(self.code.n), self.nframes
+        bases = [self.block_a[b], self.block_b[b]] if self.block_kind[b] == CNOT else [self.block_a[b], q, q + 1]
+        return np.concatenate([np.arange(n) + int(base) * n for base in bases])
+
+    def gates(self):
+        """The gate list of the whole program on (Q + 2) n qubits: the quantum instructions ftqc.rewrite_program emits, one pass
+        through every loop body."""
+        parts = []
+        for b, t in enumerate(self.block_type):
+            qubit_of = self._block_qubits(b)
+            g = self.types[t].gates.copy()
+            two = g[:, 0] == GATE_CNOT
+            g[:, 1] = qubit_of[g[:, 1]]
+            g[two, 2] = qubit_of[g[two, 2]]
+            parts.append(g)
+        return np.concatenate(parts)
+
+    def locations(self):
+        """(L, 2) rows (gate, qubit) of the whole program's fault locations, the blocks' one after the other."""
+        parts, first_gate = [], 0
+        for b, t in enumerate(self.block_type):
+            loc = self.types[t].locations.copy()
+            loc[:, 1] = self._block_qubits(b)[loc[:, 1]]
+            loc[:, 0] += first_gate
+            parts.append(loc)
+            first_gate += len(self.types[t].gates)
+        return np.concatenate(parts)
+
+    def outcome_rows(self):
+        """(rows_x, rows_z, row_time) of the whole program as gf2_circuit_effects_timed takes them, (64 ldw, (Q + 2) n) uint8 each: a
+        block's local rows at its step word, its flag rows among the flag words; row r is bit r & 63 of word r >> 6."""
+        width = (self.nframes + 2) * int(self.code.n)
+        rows = [np.zeros((64 * self.ldw, width), dtype=np.uint8) for _ in range(2)]
+        row_time = np.zeros(64 * self.ldw, dtype=np.int64)
+        first_gate = 0
+        for b, t in enumerate(self.block_type):
+            kind = self.types[t]
+            if self.block_kind[b] != CNOT:
+                qubits, _, packed_x, packed_z, times = kind._rows
+                qubit_of = self._block_qubits(b)
+                local = slice(0, 64) if self.block_step[b] >= 0 else slice(0, 0)
+                moves = [(local, 64 * int(self.block_step[b])), (slice(128, 128 + kind.num_flags), 64 * self.nsteps + int(self.block_flag[b]))]
+                for packed, out in zip((packed_x, packed_z), rows):
+                    dense = _native.unpack_rows(packed, qubits, dtype=np.uint8)
+                    for src, at in moves:
+                        out[at:at + (src.stop - src.start)][:, qubit_of] |= dense[src]
+                for src, at in moves:
+                    row_time[at:at + (src.stop - src.start)] = times[src] + first_gate
+            first_gate += len(kind.gates)
+        return rows[0], rows[1], row_time
+
+    def dense_effects(self):
+        """The dense effect table (L, 2, ldw) of the whole program, rebuilt from the block tables: a fault's local word in its own
+        step, its flags among its block's flag rows, and its tails -- pushed through the frame map of every later CNOT block --
+        under the mask of every later step of the frame they sit on."""
+        out = np.zeros((self.num_locations, 2, self.ldw), dtype=np.uint64)
+        for b, t in enumerate(self.block_type):
+            eff = self.types[t].effects
+            rows = slice(int(self.block_start[b]), int(self.block_start[b + 1]))
+            tails = [np.zeros(eff.shape[:2], dtype=np.uint64) for _ in range(self.nframes)]
+            if self.block_kind[b] == CNOT:
+                tails[self.block_a[b]], tails[self.block_b[b]] = eff[:, :, 0].copy(), eff[:, :, 1].copy()
+            else:
+                tails[self.block_a[b]] = eff[:, :, 1].copy()
+                if self.block_step[b] >= 0:
+                    out[rows, :, self.block_step[b]] = eff[:, :, 0]
+                word, shift = divmod(int(self.block_flag[b]), 64)
+                out[rows, :, self.nsteps + word] |= eff[:, :, 2] << np.uint64(shift)
+                if shift and word + 1 < self.flag_words:
+                    out[rows, :, self.nsteps + word + 1] |= eff[:, :, 2] >> np.uint64(64 - shift)
+            for c in range(b + 1, len(self.block_type)):
+                fa, fb = int(self.block_a[c]), int(self.block_b[c])
+                if self.block_kind[c] == CNOT:
+                    tails[fb] = tails[fb] ^ (tails[fa] & _LOW)
+                    tails[fa] = tails[fa] ^ (tails[fb] & _HIGH)
+                elif self.block_step[c] >= 0:
+                    out[rows, :, self.block_step[c]] = tails[fa] & FRAME_MASK[int(self.block_kind[c])]
+        return out
+
+    # -- the Monte-Carlo -----------------------------------------------------------------------------------------------------
+    def _sequence(self):
+        return (self.type_eff, self.type_locations, self.type_flags, self.block_type, self.block_kind, self.block_a, self.block_b,
+                self.nframes)
+
+    def device(self):
+        if self._device is None:
+            self._device = _native.default_context().mstream_create(*self._sequence())
+        return self._device
+
+    def _tables(self):
+        keys1, flips1, keys2, flips2 = circuit_noise.code_tables(self.code)
+        return self.code.r_1, keys1, flips1, self.code.r_2, keys2, flips2
+
+    @staticmethod
+    def _records(records):
+        if records not in RECORDS:
+            raise ValueError("records must be 'reference' or 'propagated', got %r" % (records,))
+        return RECORDS[records]
+
+    def _dict(self, counts, samples):
+        out = {name: int(counts[k]) for k, name in enumerate(MULTI_FIELDS)}
+        out['measurements'] = [dict({name: int(counts[4 + 4 * m + k]) for k, name in enumerate(MEASUREMENT_FIELDS)}, qubit=q)
+                               for m, q in enumerate(self.measured)]
+        out['samples'] = int(samples)
+        return out
+
+    def outcomes(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0):
+        """The words [steps] [flag words] of samples [first_sample, first_sample + num_samples), rejected ones included: a
+        (num_samples, ldw) uint64 array (gf2_mstream_outcomes_dev).  They do not depend on `records`."""
+        ctx = _native.default_context()
+        return ctx.outcomes(ctx.mstream_outcomes_dev, self.device(), seed, first_sample, num_samples, p_x, p_y, p_z, self.ldw)
+
+    def counts(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, records='reference'):
+        """The twenty counts of samples [first_sample, first_sample + num_samples) on the device (gf2_mc_mstream_decode): the
+        MULTI_FIELDS, then the MEASUREMENT_FIELDS of every MEASURE in program order, zero for the absent ones."""
+        return _native.default_context().mc_mstream_decode(self.device(), self._records(records), *self._tables(), int(seed), int(first_sample),
+                                                           int(num_samples), float(p_x), float(p_y), float(p_z))
+
+    def error_rates(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, records='reference'):
+        """The tally of samples [first_sample, first_sample + num_samples) on the device: a dict of the MULTI_FIELDS, 'samples' and
+        'measurements', per MEASURE in program order a dict of its qubit and the MEASUREMENT_FIELDS.  records='reference' leaves
+        the records of known errors alone at a CNOT, as the rewritten program does; 'propagated' moves them as the CNOT moves the
+        errors.  Every field but 'accepted' counts among accepted samples; the counts of sample ranges add."""
+        return self._dict(self.counts(num_samples, p_x, p_y, p_z, seed, first_sample, records), num_samples)
+
+    def words_of_faults(self, fault_first, fault_location, fault_kind):
+        """The words of samples given by their faults, on the host (gf2_mstream_words_host, no GPU): sample i has faults
+        fault_first[i] .. fault_first[i + 1] - 1, each a location and a kind 1 (X), 2 (Z) or 3 (Y)."""
+        return _native.mstream_words_host(*self._sequence(), fault_first, fault_location, fault_kind, self.ldw)
+
+    def tally_host(self, words, records='reference', classes=False, fields=False):
+        """The tally rule over words (samples, ldw) on the host (gf2_mstream_tally_host, no GPU): error_rates' dict; fields=True gives
+        the twenty counts instead, classes=True (result, class byte per sample)."""
+        words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, self.ldw)
+        got = _native.mstream_tally_host(words, self.block_kind, self.block_a, self.block_b, self.nframes, self.flag_words,
+                                         self._records(records), *self._tables(), classes=classes)
+        counts = got[0] if classes else got
+        out = counts if fields else self._dict(counts, len(words))
+        return (out, got[1]) if classes else out
+
+
+def multi_program_for(code, instructions):
+    """MultiProgram(code, instructions), cached on the code object."""
+    cache = code.__dict__.setdefault("_multi_programs", {})
+    key = ft_noise.check_instructions(instructions)[0]
+    if key not in cache:
+        cache[key] = MultiProgram(code, key)
+    return cache[key]
 
 
 def stream_for(code, what, key):
