@@ -1161,6 +1161,57 @@ int gf2_mc_retry_gate_wait_decode(gf2_ctx* ctx, const gf2_retry_gate_wait* retry
                                   int64_t first_sample, int64_t count, double p1, double p2, double q_x, double q_y, double q_z,
                                   int64_t max_attempts, uint64_t* counts_out);
 
+/* ---- repeat-until-success of multi-block programs -----------------------------------------------------
+ * [build-defined, DESIGN.md section 5d "Repeat-until-success of multi-block programs"]  "repeat-until-success" and "multi-block
+ * streamed programs" above, composed; no new randomness.  Blocks are (type, kind, a, b) as gf2_mstream_words_host takes them, the
+ * block types are cut into regions (first, count, retried) as gf2_retry_words_host takes them.  The type of a CNOT block is one
+ * region (0, 2 n, 0): it has no flag rows, so nothing of it is retried.  Region g is counted through the whole sequence, the blocks
+ * in order, and its keys, segments, draws and attempts are gf2_retry_words_host's:
+ *   kr = segment_draw(sample_key(seed, i), 2^32 + g),  ka = mix64(kr + G (a + 1)),
+ * a region that is not retried uses a = 0, a retried one the first a < max_attempts whose flags are zero.  A block is closed by
+ * gf2_mstream_words_host's rule on the XOR of its regions' words: a CNOT block applies the frame map to (T_a, T_b), then XORs its two
+ * tails; any other block gives word = mask_kind(T_a) ^ local, then T_a ^= tail.  An exhausted sample stops its walk: later step words
+ * stay 0 and the flag words hold the last attempt's flags at that block's flag rows.  A flag row depends on one region only and a
+ * CNOT block has none, so the accepted samples have the distribution post-selection gives.  The other data blocks wait at no cost
+ * while a preparation is repeated (the standing convention).  The overlap rule of gf2_mstream_create does not apply: regions end at
+ * block boundaries.  Layout of a sample, nsteps + F + 1 words: [step words] [F flag words] [attempts].
+ * Argument rules, GF2_E_ARG naming the rule: those of gf2_mstream_words_host, then the region rules and the max_attempts rule of
+ * gf2_retry_words_host (at most GF2_RETRY_MAX_SIZES distinct segment sizes), then a CNOT block whose type is not one region that is
+ * not retried.
+ * counts[GF2_MRETRY_FIELDS]: the twenty GF2_MSTREAM_FIELDS with accepted = not exhausted, then exhausted, then the attempts of all
+ * samples of the call, summed in 64 bits at every level.  Counts of sample ranges add. */
+#define GF2_MRETRY_FIELDS 22
+typedef struct gf2_mretry gf2_mretry;
+
+/* The words on the host, serial, no GPU needed: words_out is count x ldw (ldw >= nsteps + F + 1), the words past those left as
+ * they were.  attempts_out (may be null): uint32 [count][retried regions of the sequence], the attempts of every preparation in
+ * order, 0 for one never reached.  gf2_mstream_tally_host on the first nsteps + F words completes the statement under either setting
+ * of `records`: an exhausted sample has a non-zero flag word and is rejected there. */
+int gf2_mretry_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                          const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                          int64_t nframes, const int64_t* type_regions, const int64_t* type_nregions, uint64_t seed, int64_t first_sample,
+                          int64_t count, double p_x, double p_y, double p_z, int64_t max_attempts, uint64_t* words_out, int64_t ldw,
+                          uint32_t* attempts_out);
+
+/* A sequence and its regions on the device.  Argument rules as gf2_mretry_words_host's (max_attempts belongs to the calls).
+ * Destroyed by gf2_mretry_destroy. */
+int gf2_mretry_create(gf2_ctx* ctx, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                      const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                      int64_t nframes, const int64_t* type_regions, const int64_t* type_nregions, gf2_mretry** mretry_out);
+int gf2_mretry_destroy(gf2_ctx* ctx, gf2_mretry* mretry);
+
+/* The words of samples first_sample .. first_sample + count - 1 in device memory, ldo >= nsteps + F + 1 words per sample; words past
+ * those are left as they were.  out_dev: any 8-byte-aligned address. */
+int gf2_mretry_outcomes_dev(gf2_ctx* ctx, const gf2_mretry* mretry, uint64_t seed, int64_t first_sample, int64_t count, double p_x,
+                            double p_y, double p_z, int64_t max_attempts, uint64_t* out_dev, int64_t ldo);
+
+/* The tally of those samples on the device, no word stored; `records` and the bit rules as gf2_mc_mstream_decode's.
+ * counts_out[GF2_MRETRY_FIELDS] on the host.  The inverse-CDF tables are made per call and freed with it: the calls keep no state
+ * beyond the handle. */
+int gf2_mc_mretry_decode(gf2_ctx* ctx, const gf2_mretry* mretry, int64_t records, int64_t r1, const uint64_t* keys1, const uint8_t* flips1,
+                         int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed,
+                         int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, int64_t max_attempts, uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

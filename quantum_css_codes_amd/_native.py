@@ -31,6 +31,7 @@ MSTREAM_REFERENCE, MSTREAM_PROPAGATED = 0, 1
 RETRY_FIELDS_COUNT, RETRY_MAX_ATTEMPTS, RETRY_MAX_SIZES = 14, 65536, 16
 RETRY_WAIT_FIELDS_COUNT, RETRY_WAIT_MAX_ROWS = 15, 512
 RETRY_GATE_WAIT_MAX_SIZES = 3
+MRETRY_FIELDS_COUNT = 22                            # GF2_MRETRY_FIELDS
 CIRCUIT_MAX_N, CIRCUIT_MAX_ROWS, CIRCUIT_MAX_LOCATIONS, CIRCUIT_MAX_LDR = 8192, 16384, 1 << 20, 8
 STRATA_MAX, STRATUM_MAX_POSITIONS, CIRCUIT_STRATUM_MAX_WEIGHT = 256, 1 << 20, 16
 ENUMERATE_MAX_WEIGHT = 8
@@ -207,6 +208,13 @@ SIGNATURES = {
     "gf2_mstream_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _p, _c_i64],
     "gf2_mc_mstream_decode": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
                               ctypes.c_double, _p],
+    "gf2_mretry_words_host": [_p, _p, _p, _c_i64, _p, _p, _p, _p, _c_i64, _c_i64, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
+                              ctypes.c_double, _c_i64, _p, _c_i64, _p],
+    "gf2_mretry_create": [_p, _p, _p, _p, _c_i64, _p, _p, _p, _p, _c_i64, _c_i64, _p, _p, _pp],
+    "gf2_mretry_destroy": [_p, _p],
+    "gf2_mretry_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_i64, _p, _c_i64],
+    "gf2_mc_mretry_decode": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
+                             ctypes.c_double, _c_i64, _p],
     "gf2_retry_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                              _c_i64, _p, _c_i64, _p],
     "gf2_retry_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _pp],
@@ -455,6 +463,7 @@ CIRCUIT_RULE, STREAM_RULE, RETRY_RULE, RETRY_WAIT_RULE = (Rule(name, fields, lam
                                                           (("circuit", 5), ("stream", STREAM_FIELDS_COUNT), ("retry", RETRY_FIELDS_COUNT),
                                                            ("retry_wait", RETRY_WAIT_FIELDS_COUNT)))
 MSTREAM_RULE = Rule("mstream", MSTREAM_FIELDS_COUNT, lambda: ())
+MRETRY_RULE = Rule("mretry", MRETRY_FIELDS_COUNT, lambda: ())
 
 
 def _enumerate_tables(keys1, flips1, keys2, flips2, null_flips=False):
@@ -618,6 +627,21 @@ def retry_words_host(type_eff, type_locations, type_flags, block_type, block_kin
     attempts = np.zeros((max(1, count), max(1, int(preparations))), dtype=np.uint32)
     check(lib().gf2_retry_words_host(*seq, *regions, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p_x), float(p_y), float(p_z),
                                      int(max_attempts), _ptr(out), int(ldw), _ptr(attempts)))
+    return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
+
+
+def mretry_words_host(type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes, type_regions, type_nregions, seed,
+                      first, count, p_x, p_y, p_z, max_attempts, ldw, preparations):
+    """gf2_mretry_words_host (host code, no GPU): the (count, ldw) words [steps] [flag words] [attempts] of samples [first, first +
+    count) of the repeat-until-success sampler of a multi-block program and the (count, preparations) uint32 attempts of every
+    retried region."""
+    keep, seq = _mstream_sequence(type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes)
+    keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+    count = int(count)
+    out = np.zeros((max(1, count), max(1, int(ldw))), dtype="<u8")
+    attempts = np.zeros((max(1, count), max(1, int(preparations))), dtype=np.uint32)
+    check(lib().gf2_mretry_words_host(*seq, *regions, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p_x), float(p_y), float(p_z),
+                                      int(max_attempts), _ptr(out), int(ldw), _ptr(attempts)))
     return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
 
 
@@ -1098,6 +1122,20 @@ class Retry(_Handle):
 
 
 
+class MRetry(_Handle):
+    """A multi-block sequence and its regions on the device (gf2_mretry_create)."""
+    _destroy = "gf2_mretry_destroy"
+
+    def __init__(self, ctx, type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes, type_regions, type_nregions):
+        self.ctx = ctx
+        keep, seq = _mstream_sequence(type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes)
+        keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+        out = ctypes.c_void_p()
+        check(lib().gf2_mretry_create(ctx.handle, *seq, *regions, ctypes.byref(out)))
+        self.handle = out.value
+
+
+
 class RetryWait(_Handle):
     """A block sequence, its regions and their wait rows on the device (gf2_retry_wait_create)."""
     _destroy = "gf2_retry_wait_destroy"
@@ -1481,6 +1519,18 @@ class Context(object):
         """gf2_mc_retry_decode: the fourteen counts of the repeat-until-success tally over samples [first, first + count)."""
         return _decode(lib().gf2_mc_retry_decode, RETRY_RULE, (self.handle, retry.handle), (), (r1, keys1, flips1, r2, keys2, flips2),
                        seed, first, count, p_x, p_y, p_z, int(max_attempts))
+
+    def mretry_create(self, type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes, type_regions, type_nregions):
+        return MRetry(self, type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes, type_regions, type_nregions)
+
+    def mretry_outcomes_dev(self, mretry, seed, first, count, p_x, p_y, p_z, max_attempts, out_buf, ldo):
+        check(lib().gf2_mretry_outcomes_dev(self.handle, mretry.handle, seed & 0xFFFFFFFFFFFFFFFF, first, count, p_x, p_y, p_z, int(max_attempts),
+                                            out_buf.ptr, ldo))
+
+    def mc_mretry_decode(self, mretry, records, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p_x, p_y, p_z, max_attempts):
+        """gf2_mc_mretry_decode: the twenty-two counts of the repeat-until-success tally of a multi-block program."""
+        return _decode(lib().gf2_mc_mretry_decode, MRETRY_RULE, (self.handle, mretry.handle, int(records)), (),
+                       (r1, keys1, flips1, r2, keys2, flips2), seed, first, count, p_x, p_y, p_z, int(max_attempts))
 
     def retry_wait_create(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, wait_eff, wait_count):
         return RetryWait(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, wait_eff, wait_count)

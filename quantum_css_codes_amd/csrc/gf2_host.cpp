@@ -1893,6 +1893,14 @@ int gf2_retry_plan(const char* who, const uint64_t* type_eff, const int64_t* typ
                    const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
                    const int64_t* type_nregions, int64_t max_attempts, StreamPlan* plan, RetryPlan* retry) {
     if (int rc = gf2_stream_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, plan)) return rc;
+    return gf2_retry_region_rules(who, type_eff, type_locations, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions, max_attempts,
+                                  *plan, retry);
+}
+
+int gf2_retry_region_rules(const char* who, const uint64_t* type_eff, const int64_t* type_locations, int64_t ntypes, const int32_t* block_type,
+                           const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions, const int64_t* type_nregions,
+                           int64_t max_attempts, const StreamPlan& checked, RetryPlan* retry) {
+    const StreamPlan* const plan = &checked;
     if (!type_regions || !type_nregions || !retry) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
     int64_t total = 0;
     for (int64_t t = 0; t < ntypes; ++t) {
@@ -2221,6 +2229,121 @@ int gf2_retry_wait_words_host(const uint64_t* type_eff, const int64_t* type_loca
     const RetryWaitDraw waits = {&wait, wait_eff, q_x, q_y, q_z};
     return retry_walk_host(who, plan, retry, &waits, type_eff, block_type, block_kind, nblocks, seed, first_sample, count, p_x, p_y, p_z, max_attempts,
                            words_out, ldw, attempts_out);
+}
+
+}  // extern "C"
+
+// ---- repeat-until-success of multi-block programs (include/gf2hip.h) --------------------------------------
+#include "gf2_mretry_plan.h"
+
+int gf2_mretry_plan(const char* who, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                    const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                    int64_t nframes, const int64_t* type_regions, const int64_t* type_nregions, int64_t max_attempts, MStreamPlan* plan,
+                    RetryPlan* retry) {
+    if (int rc = gf2_mstream_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, block_a, block_b, nblocks, nframes, plan))
+        return rc;
+    if (int rc = gf2_retry_region_rules(who, type_eff, type_locations, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
+                                        max_attempts, plan->seq, retry))
+        return rc;
+    for (int64_t b = 0; b < nblocks; ++b) {
+        if (block_kind[b] != GF2_MSTREAM_CNOT) continue;
+        const int64_t t = block_type[b], q = retry->type_first[(size_t)t];
+        if (type_nregions[t] != 1 || retry->retried[(size_t)q])
+            GF2_FAIL(GF2_E_ARG, "%s: the type of CNOT block %lld has %lld regions, the first retried %d: a CNOT block has no flag rows, its type is one "
+                     "region that is not retried", who, (long long)b, (long long)type_nregions[t], (int)retry->retried[(size_t)q]);
+    }
+    return GF2_OK;
+}
+
+extern "C" {
+
+// The definition of gf2_mretry_outcomes_dev's words (DESIGN.md section 5d "Repeat-until-success of multi-block programs"), serial:
+// retry_walk_host's draw per (region, attempt) with gf2_mstream_words_host's closing of a block.
+int gf2_mretry_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                          const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                          int64_t nframes, const int64_t* type_regions, const int64_t* type_nregions, uint64_t seed, int64_t first_sample,
+                          int64_t count, double p_x, double p_y, double p_z, int64_t max_attempts, uint64_t* words_out, int64_t ldw,
+                          uint32_t* attempts_out) {
+    const char* who = "gf2_mretry_words_host";
+    MStreamPlan mplan;
+    RetryPlan retry;
+    if (int rc = gf2_mretry_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, block_a, block_b, nblocks, nframes,
+                                 type_regions, type_nregions, max_attempts, &mplan, &retry))
+        return rc;
+    if (int rc = gf2_retry_check_range(who, p_x, p_y, p_z, first_sample, count)) return rc;
+    const StreamPlan& plan = mplan.seq;
+    const int64_t ldr = plan.nsteps + plan.flag_words + 1;
+    if (ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the sequence's nsteps + F + 1 = %lld words", who, (long long)ldr);
+    if (count == 0) return GF2_OK;
+    if (!words_out) GF2_FAIL(GF2_E_ARG, "%s: null buffer", who);
+    const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
+    const int SEG = 512;
+    const double p_t = p_x + p_y + p_z, p_xy = p_x + p_y;
+    const uint64_t t_any = host_quantise(p_t), t_1 = p_t > 0.0 ? host_quantise(p_x / p_t) : 0, t_2 = p_t > 0.0 ? host_quantise(p_xy / p_t) : 0;
+    std::vector<uint64_t> cdf;                                                   // [size][SEG + 1]
+    try {
+        cdf.resize(retry.sizes.size() * (SEG + 1));
+    } catch (const std::bad_alloc&) {
+        GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+    }
+    for (size_t k = 0; k < retry.sizes.size(); ++k) host_binomial_cdf_table(t_any, retry.sizes[k], &cdf[k * (SEG + 1)]);
+    for (int64_t i = 0; i < count; ++i) {
+        uint64_t* const out = words_out + i * ldw;
+        for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
+        uint32_t* const tries = attempts_out ? attempts_out + i * retry.preparations : nullptr;
+        for (int64_t q = 0; tries && q < retry.preparations; ++q) tries[q] = 0;
+        const uint64_t ks = host_mix64(seed + golden * ((uint64_t)(first_sample + i) + 1));
+        uint64_t T[GF2_MSTREAM_MAX_FRAMES] = {0, 0, 0, 0}, attempts = 0;
+        int64_t g = 0, prep = 0;
+        bool exhausted = false;
+        for (int64_t b = 0; b < nblocks && !exhausted; ++b) {
+            const int64_t t = block_type[b];
+            uint64_t first = 0, second = 0;                                      // local and tail; a CNOT block's: tail for a, tail for b
+            for (int64_t r = retry.type_first[(size_t)t]; r < retry.type_first[(size_t)t + 1] && !exhausted; ++r, ++g) {
+                const int64_t rows = plan.type_offset[(size_t)t] + retry.first[(size_t)r], m = retry.count[(size_t)r];
+                const int64_t nseg = (m + SEG - 1) / SEG, limit = retry.retried[(size_t)r] ? max_attempts : 1;
+                const uint64_t kr = host_mix64(ks + stream * (GF2_RETRY_SLOT_BASE + (uint64_t)g + 1));
+                uint64_t acc[3] = {0, 0, 0};
+                int64_t a = 0;
+                do {
+                    const uint64_t ka = host_mix64(kr + golden * ((uint64_t)a + 1));
+                    acc[0] = acc[1] = acc[2] = 0;
+                    for (int64_t s = 0; s < nseg; ++s) {
+                        const bool last = s == nseg - 1;
+                        const int nb = last ? (int)(m - SEG * s) : SEG;
+                        const uint64_t* table = &cdf[(size_t)(last ? retry.last_size[(size_t)r] : retry.full_size) * (SEG + 1)];
+                        (void)retry_segment_host(host_mix64(ka + stream * ((uint64_t)s + 1)), nb, table, t_1, t_2, type_eff + (size_t)(rows + SEG * s) * 6, 3,
+                                                 acc);
+                    }
+                    a += 1;
+                } while (acc[2] != 0 && a < limit);
+                if (retry.retried[(size_t)r]) {
+                    attempts += (uint64_t)a;
+                    if (tries) tries[prep] = (uint32_t)a;
+                    prep += 1;
+                }
+                if (acc[2] != 0) {                                               // no attempt passed: the walk stops here
+                    exhausted = true;
+                    const int64_t row = plan.flag[(size_t)b];
+                    out[plan.nsteps + (row >> 6)] |= acc[2] << (row & 63);
+                    if ((row & 63) && (acc[2] >> (64 - (row & 63)))) out[plan.nsteps + (row >> 6) + 1] |= acc[2] >> (64 - (row & 63));
+                }
+                first ^= acc[0], second ^= acc[1];
+            }
+            if (exhausted) break;
+            uint64_t& Ta = T[block_a[b]];
+            if (block_kind[b] == GF2_MSTREAM_CNOT) {
+                uint64_t& Tb = T[block_b[b]];
+                gf2_mstream_cnot_map(&Ta, &Tb);
+                Ta ^= first, Tb ^= second;
+            } else {
+                if (plan.step[(size_t)b] >= 0) out[plan.step[(size_t)b]] = (Ta & gf2_stream_frame_mask(block_kind[b])) ^ first;
+                Ta ^= second;
+            }
+        }
+        out[plan.nsteps + plan.flag_words] = attempts;
+    }
+    return GF2_OK;
 }
 
 }  // extern "C"

@@ -30,5 +30,11 @@ int gf2_retry_plan(const char* who, const uint64_t* type_eff, const int64_t* typ
                    const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
                    const int64_t* type_nregions, int64_t max_attempts, StreamPlan* plan, RetryPlan* retry);
 
+// The second half of gf2_retry_plan alone, over a sequence plan that is already checked and filled (type_offset is read): the region
+// rules, the max_attempts rule and the segment sizes; fills *retry.  gf2_mretry_plan lays it over a multi-block sequence's plan.
+int gf2_retry_region_rules(const char* who, const uint64_t* type_eff, const int64_t* type_locations, int64_t ntypes, const int32_t* block_type,
+                           const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions, const int64_t* type_nregions,
+                           int64_t max_attempts, const StreamPlan& checked, RetryPlan* retry);
+
 // The rates and the sample range of a call: GF2_E_ARG as the streamed route words them.
 int gf2_retry_check_range(const char* who, double p_x, double p_y, double p_z, int64_t first_sample, int64_t count);

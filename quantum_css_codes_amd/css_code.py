@@ -540,6 +540,18 @@ class CSSCode(QECC):
         gadget = stream_noise.multi_program_for(self, instructions)
         return gadget.error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample, records=records)
 
+    def logical_circuit_retried_error_rates(self, instructions, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, records='reference',
+                                            max_attempts=256):
+        """[build-defined]  logical_circuit_error_rates with every preparation retried on its own until its verifications pass
+        (stream_noise.MultiProgram.retry_error_rates), as the reference's while_do loops run them: essentially every sample is
+        accepted, whatever p and the program's length.  The rates are those of the post-selected route at every p; the samples are
+        different samples.  The dict also has 'exhausted', 'attempts' and 'preparations'.  The other data blocks wait at no cost
+        while a preparation is repeated."""
+        from . import stream_noise
+        gadget = stream_noise.multi_program_for(self, instructions)
+        return gadget.retry_error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample, records=records,
+                                        max_attempts=max_attempts)
+
     def error_correct_retried_error_rates(self, num_samples, p_x, p_y, p_z, rounds, seed=0, first_sample=0, idle_data=False, max_attempts=256):
         """[build-defined]  error_correct_streamed_error_rates with every preparation retried on its own until its verifications
         pass (stream_noise.StreamedGadget.retry_error_rates), as the reference's while_do loops run them: essentially every sample is

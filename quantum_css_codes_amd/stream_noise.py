@@ -46,7 +46,9 @@ under gate-level faults"): retry_gate_*'s walk and draw plus retry_wait_*'s wait
 MultiProgram is the same walk for rewritten programs on up to four logical qubits with the transversal CNOT (DESIGN.md section 5d
 "Multi-block programs"): one data frame T per logical qubit, the existing block types serving frame a, and one new block type and
 kind, CNOT, whose closing applies T_b ^= T_a & 0x00000000FFFFFFFF, T_a ^= T_b & 0xFFFFFFFF00000000 to the two carried words and then
-XORs its faults' two tails.  Post-selected only: the retried, gate-level and waiting variants are those of one qubit.
+XORs its faults' two tails.  Its retry_* methods are the repeat-until-success sampler of such programs (DESIGN.md section 5d
+"Repeat-until-success of multi-block programs"): the regions of the block types as above, a CNOT block one region that is not
+retried.  The gate-level and waiting variants are those of one qubit.
 """
 import numpy as np
 
@@ -595,7 +597,7 @@ class CnotBlockType(object):
     """The block type of a transversal CNOT: `gates`, n rows (GATE_CNOT, i, n + i) on the 2n qubits of the data blocks a (0 .. n-1)
     and b (n .. 2n-1); `locations` (2n, 2); no flag rows; `effects` (2n, 2, 3) uint64: (the tail the fault leaves on frame a, the
     tail it leaves on frame b, 0) of an X and of a Z fault, from gf2_circuit_effects_timed on this gate list with the final-frame
-    rows of block a in word 0 and of block b in word 1."""
+    rows of block a in word 0 and of block b in word 1; `regions`, the one region (0, 2n, 0): nothing of a CNOT block is retried."""
 
     def __init__(self, code):
         n, r_1, r_2 = int(code.n), int(code.r_1), int(code.r_2)
@@ -615,6 +617,7 @@ class CnotBlockType(object):
             rows_z[64 * word + 63, block] = x_op & 1
         self._rows = (2 * n, list(range(n)), _native.pack_rows(rows_x), _native.pack_rows(rows_z), np.full(64 * 3, n, dtype=np.int64))
         self.effects, self.locations = _native.circuit_effects_timed(self.gates, 2 * n, *self._rows[2:], ldr=3)
+        self.regions = np.array([[0, 2 * n, 0]], dtype=np.int64)
 
     @property
     def num_locations(self):
@@ -634,7 +637,8 @@ class MultiProgram(object):
     block its IDLE locations are a block of kind NONE of their own, so that the locations keep the emitted program's order.
 
     `types`, `block_type`, `block_kind`, `block_a`, `block_b` (-1 unless a CNOT block), `block_start`, `block_step`, `block_flag`,
-    `nsteps`, `flag_words`, `ldw` as StreamedGadget's; `measured`, the measured qubits in program order."""
+    `nsteps`, `flag_words`, `ldw` as StreamedGadget's; `measured`, the measured qubits in program order; `preparations`, the
+    retried regions of the whole sequence."""
 
     def __init__(self, code, instructions):
         self.code = code
@@ -696,7 +700,11 @@ class MultiProgram(object):
         self.type_eff = np.ascontiguousarray(np.concatenate([t.effects for t in types]))
         self.type_locations = np.array([t.num_locations for t in types], dtype=np.int64)
         self.type_flags = np.array([t.num_flags for t in types], dtype=np.int64)
+        self.type_regions = np.ascontiguousarray(np.concatenate([t.regions for t in types]))
+        self.type_nregions = np.array([len(t.regions) for t in types], dtype=np.int64)
+        self.preparations = int(sum(int(types[t].regions[:, 2].sum()) for t in self.block_type))
         self._device = None
+        self._retry_device = None
 
     @classmethod
     def from_quil(cls, raw_prog, code):
@@ -846,6 +854,46 @@ class MultiProgram(object):
         counts = got[0] if classes else got
         out = counts if fields else self._dict(counts, len(words))
         return (out, got[1]) if classes else out
+
+    # -- repeat-until-success ----------------------------------------------------------------------------------------------------
+    def _retry_sequence(self):
+        return self._sequence() + (self.type_regions, self.type_nregions)
+
+    def retry_device(self):
+        if self._retry_device is None:
+            self._retry_device = _native.default_context().mretry_create(*self._retry_sequence())
+        return self._retry_device
+
+    def retry_outcomes(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, max_attempts=256):
+        """The words of samples [first_sample, first_sample + num_samples) of the repeat-until-success sampler, every preparation
+        retried until its verifications pass or max_attempts are used up: a (num_samples, ldw + 1) uint64 array [steps] [flag words,
+        zero unless the sample is exhausted] [attempts of the sample] (gf2_mretry_outcomes_dev).  The other data blocks wait at no
+        cost while a preparation is repeated.  The rates are those of the post-selected route; the samples are different samples."""
+        ctx = _native.default_context()
+        return ctx.outcomes(ctx.mretry_outcomes_dev, self.retry_device(), seed, first_sample, num_samples, p_x, p_y, p_z, self.ldw + 1,
+                            int(max_attempts))
+
+    def retry_counts(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, records='reference', max_attempts=256):
+        """The twenty-two counts of samples [first_sample, first_sample + num_samples) on the device (gf2_mc_mretry_decode): counts'
+        twenty with accepted = not exhausted, the exhausted samples, the attempts of all samples."""
+        records = self._records(records)
+        return _native.default_context().mc_mretry_decode(self.retry_device(), records, *self._tables(), int(seed), int(first_sample),
+                                                          int(num_samples), float(p_x), float(p_y), float(p_z), int(max_attempts))
+
+    def retry_error_rates(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, records='reference', max_attempts=256):
+        """error_rates' dict from the repeat-until-success sampler, plus 'exhausted', 'attempts' and 'preparations' (the retried
+        regions per sample: attempts / (samples * preparations) is the mean number of attempts per preparation).  The counts of
+        sample ranges add."""
+        counts = self.retry_counts(num_samples, p_x, p_y, p_z, seed, first_sample, records, max_attempts)
+        out = self._dict(counts, num_samples)
+        out.update(exhausted=int(counts[20]), attempts=int(counts[21]), preparations=self.preparations)
+        return out
+
+    def retry_words_host(self, num_samples, p_x, p_y, p_z, seed=0, first_sample=0, max_attempts=256):
+        """retry_outcomes' words on the host (gf2_mretry_words_host, no GPU) and the (num_samples, preparations) uint32 attempts of
+        every preparation in order, 0 for one never reached.  tally_host on words[:, :ldw] completes the statement."""
+        return _native.mretry_words_host(*self._retry_sequence(), seed, first_sample, num_samples, p_x, p_y, p_z, max_attempts, self.ldw + 1,
+                                         self.preparations)
 
 
 def multi_program_for(code, instructions):
