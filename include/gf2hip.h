@@ -1212,6 +1212,59 @@ int gf2_mc_mretry_decode(gf2_ctx* ctx, const gf2_mretry* mretry, int64_t records
                          int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2, uint64_t seed,
                          int64_t first_sample, int64_t count, double p_x, double p_y, double p_z, int64_t max_attempts, uint64_t* counts_out);
 
+/* ---- repeat-until-success of multi-block programs under gate-level faults ------------------------------
+ * [build-defined, DESIGN.md section 5d "Repeat-until-success of multi-block programs under gate-level faults"]  "repeat-until-success
+ * of multi-block programs" and "repeat-until-success under gate-level faults" above, composed; no new randomness.  The blocks, frames,
+ * records, frame map, closing of a block, exhaustion, layout of a sample and the counts are those of the former; the keys and the
+ * draw those of the latter: ks, the region number g counted through the whole sequence with the CNOT blocks' regions included,
+ * kr = segment_draw(ks, GF2_RETRY_SLOT_BASE + g), ka = mix64(kr + G (a + 1)), and under ka the region's one-operand sites (radix 3,
+ * T = quantise(p_1), slots GF2_GATE_MC_SLOT_ONE + s) and then its CNOT sites (radix 15, T = quantise(p_2), slots GF2_GATE_MC_SLOT_CNOT
+ * + s) in segments of 512 sites, Floyd's rule, kappa = 1 + ((lo radix) >> 32).  site_loc and site_regions as
+ * gf2_retry_gate_words_host takes them, over the regions of all types.
+ * A CNOT block is one region that is never retried, with (n_1, n_2) = (0, n): site i is location 2 i, the control of the physical
+ * CNOT D_a[i] -> D_b[i] on frame a, and location 2 i + 1 its target on frame b.  Bits 0-1 of kappa pick the control's X / Z rows,
+ * bits 2-3 the target's; the rows hold (tail for a, tail for b, 0), so the XOR over the picked rows is the one event's correlated
+ * effect on both frames.
+ * Sites fail independently, no site straddles two regions and a CNOT block has no flag row, so the accepted samples have the
+ * distribution post-selection gives; max_attempts = 1 is gate-level post-selection of a multi-block program.  A program on one
+ * logical qubit gives gf2_retry_gate_outcomes_dev's words and gf2_mc_retry_gate_decode's counts bit for bit; the inner slots are
+ * disjoint from the location route's, so a seed's samples are other samples than gf2_mretry_*'s.
+ * Argument rules, GF2_E_ARG naming the rule: those of gf2_mretry_words_host, then the site rules of gf2_retry_gate_words_host, then a
+ * CNOT block whose type has a one-operand site; p_1 or p_2 outside [0, 1].
+ * counts[GF2_MRETRY_FIELDS] as gf2_mc_mretry_decode's.  Counts of sample ranges add. */
+typedef struct gf2_mretry_gate gf2_mretry_gate;
+
+/* Replaces gf2_mretry_words_host under gate-level faults.  The words on the host, serial, no GPU needed; words_out, ldw and
+ * attempts_out as gf2_mretry_words_host's.  gf2_mstream_tally_host on the first nsteps + F words completes the statement under either
+ * setting of `records`. */
+int gf2_mretry_gate_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                               const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b,
+                               int64_t nblocks, int64_t nframes, const int64_t* type_regions, const int64_t* type_nregions,
+                               const int32_t* site_loc, const int64_t* site_regions, uint64_t seed, int64_t first_sample, int64_t count, double p1,
+                               double p2, int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out);
+
+/* Replaces gf2_mretry_create / gf2_mretry_destroy: a sequence, its regions and their sites on the device.  Argument rules as
+ * gf2_mretry_gate_words_host's (max_attempts, the rates and the range belong to the calls). */
+int gf2_mretry_gate_create(gf2_ctx* ctx, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                           const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                           int64_t nframes, const int64_t* type_regions, const int64_t* type_nregions, const int32_t* site_loc,
+                           const int64_t* site_regions, gf2_mretry_gate** mretry_out);
+int gf2_mretry_gate_destroy(gf2_ctx* ctx, gf2_mretry_gate* mretry);
+
+/* Replaces gf2_mretry_outcomes_dev (and, on one logical qubit, equals gf2_retry_gate_outcomes_dev): the words of samples first_sample
+ * .. first_sample + count - 1 in device memory, ldo >= nsteps + F + 1 words per sample; words past those are left as they were.
+ * out_dev: any 8-byte-aligned address. */
+int gf2_mretry_gate_outcomes_dev(gf2_ctx* ctx, const gf2_mretry_gate* mretry, uint64_t seed, int64_t first_sample, int64_t count, double p1,
+                                 double p2, int64_t max_attempts, uint64_t* out_dev, int64_t ldo);
+
+/* Replaces gf2_mc_mretry_decode: the tally of those samples on the device, no word stored; `records` and the bit rules as
+ * gf2_mc_mstream_decode's.  counts_out[GF2_MRETRY_FIELDS] on the host.  The inverse-CDF tables are made per call and freed with it: the
+ * calls keep no state beyond the handle. */
+int gf2_mc_mretry_gate_decode(gf2_ctx* ctx, const gf2_mretry_gate* mretry, int64_t records, int64_t r1, const uint64_t* keys1,
+                              const uint8_t* flips1, int64_t entries1, int64_t r2, const uint64_t* keys2, const uint8_t* flips2, int64_t entries2,
+                              uint64_t seed, int64_t first_sample, int64_t count, double p1, double p2, int64_t max_attempts,
+                              uint64_t* counts_out);
+
 /* ---- multi-GPU: the histogram all-reduce -------------------------------------------------------------
  * [build-defined, SURVEY.md 8e]  The Monte-Carlo run shards by sample range (sample i = f(seed, i)); ranks never exchange
  * anything on the data path.  The one collective is the sum of the histograms -- keys as css_code.py:729, X errors against

@@ -215,6 +215,13 @@ SIGNATURES = {
     "gf2_mretry_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_i64, _p, _c_i64],
     "gf2_mc_mretry_decode": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double,
                              ctypes.c_double, _c_i64, _p],
+    "gf2_mretry_gate_words_host": [_p, _p, _p, _c_i64, _p, _p, _p, _p, _c_i64, _c_i64, _p, _p, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double,
+                                   ctypes.c_double, _c_i64, _p, _c_i64, _p],
+    "gf2_mretry_gate_create": [_p, _p, _p, _p, _c_i64, _p, _p, _p, _p, _c_i64, _c_i64, _p, _p, _p, _p, _pp],
+    "gf2_mretry_gate_destroy": [_p, _p],
+    "gf2_mretry_gate_outcomes_dev": [_p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, _c_i64, _p, _c_i64],
+    "gf2_mc_mretry_gate_decode": [_p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_i64, _p, _p, _c_i64, _c_u64, _c_i64, _c_i64, ctypes.c_double,
+                                  ctypes.c_double, _c_i64, _p],
     "gf2_retry_words_host": [_p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _c_u64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                              _c_i64, _p, _c_i64, _p],
     "gf2_retry_create": [_p, _p, _p, _p, _c_i64, _p, _p, _c_i64, _p, _p, _pp],
@@ -696,6 +703,22 @@ def retry_gate_words_host(type_eff, type_locations, type_flags, block_type, bloc
     return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
 
 
+def mretry_gate_words_host(type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes, type_regions, type_nregions,
+                           site_loc, site_regions, seed, first, count, p1, p2, max_attempts, ldw, preparations):
+    """gf2_mretry_gate_words_host (host code, no GPU): the (count, ldw) words [steps] [flag words] [attempts] of samples [first, first
+    + count) of the repeat-until-success sampler of a multi-block program under gate-level faults and the (count, preparations)
+    uint32 attempts of every retried region."""
+    keep, seq = _mstream_sequence(type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes)
+    keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+    keep_sites, sites = _retry_sites(site_loc, site_regions, len(keep_regions[0]))
+    count = int(count)
+    out = np.zeros((max(1, count), max(1, int(ldw))), dtype="<u8")
+    attempts = np.zeros((max(1, count), max(1, int(preparations))), dtype=np.uint32)
+    check(lib().gf2_mretry_gate_words_host(*seq, *regions, *sites, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first), count, float(p1), float(p2),
+                                           int(max_attempts), _ptr(out), int(ldw), _ptr(attempts)))
+    return out[:max(0, count)], attempts[:max(0, count), :int(preparations)]
+
+
 def retry_gate_wait_words_host(type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, site_loc, site_regions,
                                wait_eff, wait_count, seed, first, count, p1, p2, q_x, q_y, q_z, max_attempts, ldw, preparations):
     """gf2_retry_gate_wait_words_host (host code, no GPU): the (count, ldw) words [steps] [flag words] [attempts] [wait faults] of
@@ -1136,6 +1159,22 @@ class MRetry(_Handle):
 
 
 
+class MRetryGate(_Handle):
+    """A multi-block sequence, its regions and their sites on the device (gf2_mretry_gate_create)."""
+    _destroy = "gf2_mretry_gate_destroy"
+
+    def __init__(self, ctx, type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes, type_regions, type_nregions,
+                 site_loc, site_regions):
+        self.ctx = ctx
+        keep, seq = _mstream_sequence(type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes)
+        keep_regions, regions = _retry_regions(type_regions, type_nregions, len(keep[1]))
+        keep_sites, sites = _retry_sites(site_loc, site_regions, len(keep_regions[0]))
+        out = ctypes.c_void_p()
+        check(lib().gf2_mretry_gate_create(ctx.handle, *seq, *regions, *sites, ctypes.byref(out)))
+        self.handle = out.value
+
+
+
 class RetryWait(_Handle):
     """A block sequence, its regions and their wait rows on the device (gf2_retry_wait_create)."""
     _destroy = "gf2_retry_wait_destroy"
@@ -1531,6 +1570,24 @@ class Context(object):
         """gf2_mc_mretry_decode: the twenty-two counts of the repeat-until-success tally of a multi-block program."""
         return _decode(lib().gf2_mc_mretry_decode, MRETRY_RULE, (self.handle, mretry.handle, int(records)), (),
                        (r1, keys1, flips1, r2, keys2, flips2), seed, first, count, p_x, p_y, p_z, int(max_attempts))
+
+    def mretry_gate_create(self, type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes, type_regions,
+                           type_nregions, site_loc, site_regions):
+        return MRetryGate(self, type_eff, type_locations, type_flags, block_type, block_kind, block_a, block_b, nframes, type_regions,
+                          type_nregions, site_loc, site_regions)
+
+    def mretry_gate_outcomes_dev(self, mretry, seed, first, count, p1, p2, max_attempts, out_buf, ldo):
+        check(lib().gf2_mretry_gate_outcomes_dev(self.handle, mretry.handle, seed & 0xFFFFFFFFFFFFFFFF, first, count, p1, p2, int(max_attempts),
+                                                 out_buf.ptr, ldo))
+
+    def mc_mretry_gate_decode(self, mretry, records, r1, keys1, flips1, r2, keys2, flips2, seed, first, count, p1, p2, max_attempts):
+        """gf2_mc_mretry_gate_decode: the twenty-two counts of the repeat-until-success tally of a multi-block program under
+        gate-level faults."""
+        keep, rest = _rule_arguments(MRETRY_RULE, (), (r1, keys1, flips1, r2, keys2, flips2))
+        counts = np.zeros(MRETRY_RULE.fields, dtype=np.uint64)
+        check(lib().gf2_mc_mretry_gate_decode(self.handle, mretry.handle, int(records), *rest, seed & 0xFFFFFFFFFFFFFFFF, first, count, p1, p2,
+                                              int(max_attempts), _ptr(counts)))
+        return counts
 
     def retry_wait_create(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, wait_eff, wait_count):
         return RetryWait(self, type_eff, type_locations, type_flags, block_type, block_kind, type_regions, type_nregions, wait_eff, wait_count)

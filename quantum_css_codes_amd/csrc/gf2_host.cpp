@@ -2358,6 +2358,12 @@ int gf2_retry_gate_plan(const char* who, const uint64_t* type_eff, const int64_t
     if (int rc = gf2_retry_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, nblocks, type_regions, type_nregions,
                                 max_attempts, plan, retry))
         return rc;
+    return gf2_retry_gate_site_rules(who, type_locations, ntypes, site_loc, site_regions, *retry, gate);
+}
+
+int gf2_retry_gate_site_rules(const char* who, const int64_t* type_locations, int64_t ntypes, const int32_t* site_loc, const int64_t* site_regions,
+                              const RetryPlan& checked, RetryGatePlan* gate) {
+    const RetryPlan* const retry = &checked;
     if (!site_loc || !site_regions || !gate) GF2_FAIL(GF2_E_ARG, "%s: null argument", who);
     const int64_t total = retry->type_first[(size_t)ntypes];
     std::vector<uint8_t> seen;
@@ -2441,6 +2447,59 @@ int gf2_retry_gate_wait_plan(const char* who, const uint64_t* type_eff, const in
 }
 
 namespace {
+// The inverse-CDF tables of a call's two classes, [size][512 + 1] per class ...
+struct RetryGateTables {
+    std::vector<uint64_t> cdf[2];
+    int make(const char* who, const RetryGatePlan& gate, double p1, double p2) {
+        const uint64_t T[2] = {host_quantise(p1), host_quantise(p2)};
+        try {
+            for (int cl = 0; cl < 2; ++cl) cdf[cl].resize(gate.sizes[cl].size() * (512 + 1));
+        } catch (const std::bad_alloc&) {
+            GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
+        }
+        for (int cl = 0; cl < 2; ++cl)
+            for (size_t k = 0; k < gate.sizes[cl].size(); ++k) host_binomial_cdf_table(T[cl], gate.sizes[cl][k], &cdf[cl][k * (512 + 1)]);
+        return GF2_OK;
+    }
+};
+
+// ... and the draw of one attempt of region r (RetryPlan's numbering) under its key ka, XOR-ed into acc = (local, tail, flags): the
+// region's one-operand sites, then its CNOT sites, as gf2_gate_outcomes_host draws a sample's.  `rows` is the table of the region's
+// type: sites are type-local.  Shared by the one-qubit walk below and gf2_mretry_gate_words_host.
+void retry_gate_attempt_host(const RetryGatePlan& gate, const RetryGateTables& tables, const uint64_t* rows, const int32_t* site_loc, int64_t r,
+                             uint64_t ka, uint64_t* acc) {
+    const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
+    const int SEG = 512;
+    const uint64_t radix[2] = {3, 15}, slot_base[2] = {GF2_GATE_MC_SLOT_ONE, GF2_GATE_MC_SLOT_CNOT};
+    int64_t site_base = gate.site_first[(size_t)r];
+    for (int cl = 0; cl < 2; site_base += gate.n[cl][(size_t)r], ++cl) {
+        const int64_t m = gate.n[cl][(size_t)r], nseg = (m + SEG - 1) / SEG;      // (none for an empty class)
+        for (int64_t s = 0; s < nseg; ++s) {
+            const bool last = s == nseg - 1;
+            const int nb = last ? (int)(m - SEG * s) : SEG;
+            const uint64_t* table = &tables.cdf[cl][(size_t)(last ? gate.last_size[cl][(size_t)r] : gate.full_size[cl]) * (SEG + 1)];
+            const uint64_t d = host_mix64(ka + stream * (slot_base[cl] + (uint64_t)s + 1));
+            const uint64_t u = d >> 32;
+            int K = 0;
+            while (K < nb && u >= table[K]) K += 1;
+            uint64_t taken[SEG / 64] = {0, 0, 0, 0, 0, 0, 0, 0};
+            for (int k = 0; k < K; ++k) {
+                const uint64_t v = host_mix64(d + golden * (uint64_t)(k + 1));
+                const uint64_t hi = v >> 32, lo = v & 0xFFFFFFFFull;
+                const uint64_t j = (uint64_t)(nb - K + k);
+                const uint64_t pick = (hi * (j + 1)) >> 32;          // Floyd: a candidate in [0, j]
+                const uint64_t pos = ((taken[pick >> 6] >> (pick & 63)) & 1ull) ? j : pick;
+                taken[pos >> 6] |= 1ull << (pos & 63);
+                const uint64_t kappa = 1 + ((lo * radix[cl]) >> 32);
+                const uint64_t* e = rows + (size_t)site_loc[site_base + SEG * s + (int64_t)pos] * 6;
+                for (int bit = 0; bit < 4; ++bit)                     // bits 2, 3: the CNOT's second location
+                    if ((kappa >> bit) & 1)
+                        for (int q = 0; q < 3; ++q) acc[q] ^= e[3 * bit + q];
+            }
+        }
+    }
+}
+
 // The definition of gf2_retry_gate_outcomes_dev's words (DESIGN.md section 5d "Repeat-until-success under gate-level faults"),
 // serial: gf2_retry_words_host's walk, an attempt drawn as gf2_gate_outcomes_host draws a sample -- the region's one-operand sites,
 // then its CNOT sites, each class with its own slots, rate and radix of kinds -- under the attempt's key.
@@ -2458,21 +2517,18 @@ int retry_gate_walk_host(const char* who, const StreamPlan& plan, const RetryPla
     if (!words_out) GF2_FAIL(GF2_E_ARG, "%s: null buffer", who);
     const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
     const int SEG = 512;
-    const uint64_t radix[2] = {3, 15}, slot_base[2] = {GF2_GATE_MC_SLOT_ONE, GF2_GATE_MC_SLOT_CNOT};
-    const uint64_t T[2] = {host_quantise(p1), host_quantise(p2)};
     const double q_t = waits ? waits->q_x + waits->q_y + waits->q_z : 0.0;
     const uint64_t w_any = host_quantise(q_t), w_1 = q_t > 0.0 ? host_quantise(waits->q_x / q_t) : 0,
                    w_2 = q_t > 0.0 ? host_quantise((waits->q_x + waits->q_y) / q_t) : 0;
     const size_t wait_sizes = waits ? waits->plan->sizes.size() : 0;
-    std::vector<uint64_t> cdf[2], wait_cdf;                                      // per class, and of the wait sizes: [size][SEG + 1]
+    RetryGateTables tables;
+    if (int rc = tables.make(who, gate, p1, p2)) return rc;
+    std::vector<uint64_t> wait_cdf;                                              // of the wait sizes: [size][SEG + 1]
     try {
-        for (int cl = 0; cl < 2; ++cl) cdf[cl].resize(gate.sizes[cl].size() * (SEG + 1));
         wait_cdf.resize(wait_sizes * (SEG + 1));
     } catch (const std::bad_alloc&) {
         GF2_FAIL(GF2_E_NOMEM, "%s: out of host memory", who);
     }
-    for (int cl = 0; cl < 2; ++cl)
-        for (size_t k = 0; k < gate.sizes[cl].size(); ++k) host_binomial_cdf_table(T[cl], gate.sizes[cl][k], &cdf[cl][k * (SEG + 1)]);
     for (size_t k = 0; k < wait_sizes; ++k) host_binomial_cdf_table(w_any, waits->plan->sizes[k], &wait_cdf[k * (SEG + 1)]);
     for (int64_t i = 0; i < count; ++i) {
         uint64_t* const out = words_out + i * ldw;
@@ -2498,33 +2554,7 @@ int retry_gate_walk_host(const char* who, const StreamPlan& plan, const RetryPla
                     do {
                         const uint64_t ka = host_mix64(kr + golden * ((uint64_t)a + 1));
                         acc[0] = acc[1] = acc[2] = 0;
-                        int64_t site_base = gate.site_first[(size_t)r];
-                        for (int cl = 0; cl < 2; site_base += gate.n[cl][(size_t)r], ++cl) {
-                            const int64_t m = gate.n[cl][(size_t)r], nseg = (m + SEG - 1) / SEG;      // (none for an empty class)
-                            for (int64_t s = 0; s < nseg; ++s) {
-                                const bool last = s == nseg - 1;
-                                const int nb = last ? (int)(m - SEG * s) : SEG;
-                                const uint64_t* table = &cdf[cl][(size_t)(last ? gate.last_size[cl][(size_t)r] : gate.full_size[cl]) * (SEG + 1)];
-                                const uint64_t d = host_mix64(ka + stream * (slot_base[cl] + (uint64_t)s + 1));
-                                const uint64_t u = d >> 32;
-                                int K = 0;
-                                while (K < nb && u >= table[K]) K += 1;
-                                uint64_t taken[SEG / 64] = {0, 0, 0, 0, 0, 0, 0, 0};
-                                for (int k = 0; k < K; ++k) {
-                                    const uint64_t v = host_mix64(d + golden * (uint64_t)(k + 1));
-                                    const uint64_t hi = v >> 32, lo = v & 0xFFFFFFFFull;
-                                    const uint64_t j = (uint64_t)(nb - K + k);
-                                    const uint64_t pick = (hi * (j + 1)) >> 32;          // Floyd: a candidate in [0, j]
-                                    const uint64_t pos = ((taken[pick >> 6] >> (pick & 63)) & 1ull) ? j : pick;
-                                    taken[pos >> 6] |= 1ull << (pos & 63);
-                                    const uint64_t kappa = 1 + ((lo * radix[cl]) >> 32);
-                                    const uint64_t* e = rows + (size_t)site_loc[site_base + SEG * s + (int64_t)pos] * 6;
-                                    for (int bit = 0; bit < 4; ++bit)                     // bits 2, 3: the CNOT's second location
-                                        if ((kappa >> bit) & 1)
-                                            for (int q = 0; q < 3; ++q) acc[q] ^= e[3 * bit + q];
-                                }
-                            }
-                        }
+                        retry_gate_attempt_host(gate, tables, rows, site_loc, r, ka, acc);
                         if (nw > 0) {                                            // the data waits through this attempt, passed or not
                             const uint64_t kwa = host_mix64(kw + golden * ((uint64_t)a + 1));
                             wait_faults += (uint64_t)retry_segment_host(host_mix64(kwa + stream), nw,
@@ -2595,6 +2625,107 @@ int gf2_retry_gate_wait_words_host(const uint64_t* type_eff, const int64_t* type
     const RetryWaitDraw waits = {&wait, wait_eff, q_x, q_y, q_z};
     return retry_gate_walk_host(who, plan, retry, gate, &waits, type_eff, block_type, block_kind, nblocks, site_loc, seed, first_sample, count, p1,
                                 p2, max_attempts, words_out, ldw, attempts_out);
+}
+
+}  // extern "C"
+
+// ---- repeat-until-success of multi-block programs under gate-level faults (include/gf2hip.h) ---------------
+#include "gf2_mretry_gate_plan.h"
+
+int gf2_mretry_gate_plan(const char* who, const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                         const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b, int64_t nblocks,
+                         int64_t nframes, const int64_t* type_regions, const int64_t* type_nregions, const int32_t* site_loc,
+                         const int64_t* site_regions, int64_t max_attempts, MStreamPlan* plan, RetryPlan* retry, RetryGatePlan* gate) {
+    if (int rc = gf2_mretry_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, block_a, block_b, nblocks, nframes,
+                                 type_regions, type_nregions, max_attempts, plan, retry))
+        return rc;
+    if (int rc = gf2_retry_gate_site_rules(who, type_locations, ntypes, site_loc, site_regions, *retry, gate)) return rc;
+    for (int64_t b = 0; b < nblocks; ++b) {
+        if (block_kind[b] != GF2_MSTREAM_CNOT) continue;
+        const int64_t q = retry->type_first[(size_t)block_type[b]];
+        if (gate->n[0][(size_t)q] != 0)
+            GF2_FAIL(GF2_E_ARG, "%s: the type of CNOT block %lld has %d one-operand sites: every site of a CNOT block is a physical CNOT, its "
+                     "control on frame a and its target on frame b", who, (long long)b, (int)gate->n[0][(size_t)q]);
+    }
+    return GF2_OK;
+}
+
+extern "C" {
+
+// The definition of gf2_mretry_gate_outcomes_dev's words (DESIGN.md section 5d "Repeat-until-success of multi-block programs under
+// gate-level faults"), serial: gf2_mretry_words_host's walk and closing of a block, an attempt drawn by retry_gate_attempt_host.
+int gf2_mretry_gate_words_host(const uint64_t* type_eff, const int64_t* type_locations, const int64_t* type_flags, int64_t ntypes,
+                               const int32_t* block_type, const int32_t* block_kind, const int32_t* block_a, const int32_t* block_b,
+                               int64_t nblocks, int64_t nframes, const int64_t* type_regions, const int64_t* type_nregions,
+                               const int32_t* site_loc, const int64_t* site_regions, uint64_t seed, int64_t first_sample, int64_t count, double p1,
+                               double p2, int64_t max_attempts, uint64_t* words_out, int64_t ldw, uint32_t* attempts_out) {
+    const char* who = "gf2_mretry_gate_words_host";
+    MStreamPlan mplan;
+    RetryPlan retry;
+    RetryGatePlan gate;
+    if (int rc = gf2_mretry_gate_plan(who, type_eff, type_locations, type_flags, ntypes, block_type, block_kind, block_a, block_b, nblocks, nframes,
+                                      type_regions, type_nregions, site_loc, site_regions, max_attempts, &mplan, &retry, &gate))
+        return rc;
+    if (int rc = gf2_gate_check_mc(who, p1, p2, first_sample, count)) return rc;
+    const StreamPlan& plan = mplan.seq;
+    const int64_t ldr = plan.nsteps + plan.flag_words + 1;
+    if (ldw < ldr) GF2_FAIL(GF2_E_ARG, "%s: ldw must be at least the sequence's nsteps + F + 1 = %lld words", who, (long long)ldr);
+    if (count == 0) return GF2_OK;
+    if (!words_out) GF2_FAIL(GF2_E_ARG, "%s: null buffer", who);
+    const uint64_t golden = 0x9E3779B97F4A7C15ull, stream = 0xD1B54A32D192ED03ull;
+    RetryGateTables tables;
+    if (int rc = tables.make(who, gate, p1, p2)) return rc;
+    for (int64_t i = 0; i < count; ++i) {
+        uint64_t* const out = words_out + i * ldw;
+        for (int64_t q = 0; q < ldr; ++q) out[q] = 0;
+        uint32_t* const tries = attempts_out ? attempts_out + i * retry.preparations : nullptr;
+        for (int64_t q = 0; tries && q < retry.preparations; ++q) tries[q] = 0;
+        const uint64_t ks = host_mix64(seed + golden * ((uint64_t)(first_sample + i) + 1));
+        uint64_t T[GF2_MSTREAM_MAX_FRAMES] = {0, 0, 0, 0}, attempts = 0;
+        int64_t g = 0, prep = 0;
+        bool exhausted = false;
+        for (int64_t b = 0; b < nblocks && !exhausted; ++b) {
+            const int64_t t = block_type[b];
+            const uint64_t* const rows = type_eff + (size_t)plan.type_offset[(size_t)t] * 6;   // the type's table: sites are type-local
+            uint64_t first = 0, second = 0;                                      // local and tail; a CNOT block's: tail for a, tail for b
+            for (int64_t r = retry.type_first[(size_t)t]; r < retry.type_first[(size_t)t + 1] && !exhausted; ++r, ++g) {
+                const int64_t limit = retry.retried[(size_t)r] ? max_attempts : 1;
+                const uint64_t kr = host_mix64(ks + stream * (GF2_RETRY_SLOT_BASE + (uint64_t)g + 1));
+                uint64_t acc[3] = {0, 0, 0};
+                int64_t a = 0;
+                do {
+                    const uint64_t ka = host_mix64(kr + golden * ((uint64_t)a + 1));
+                    acc[0] = acc[1] = acc[2] = 0;
+                    retry_gate_attempt_host(gate, tables, rows, site_loc, r, ka, acc);
+                    a += 1;
+                } while (acc[2] != 0 && a < limit);
+                if (retry.retried[(size_t)r]) {
+                    attempts += (uint64_t)a;
+                    if (tries) tries[prep] = (uint32_t)a;
+                    prep += 1;
+                }
+                if (acc[2] != 0) {                                               // no attempt passed: the walk stops here
+                    exhausted = true;
+                    const int64_t row = plan.flag[(size_t)b];
+                    out[plan.nsteps + (row >> 6)] |= acc[2] << (row & 63);
+                    if ((row & 63) && (acc[2] >> (64 - (row & 63)))) out[plan.nsteps + (row >> 6) + 1] |= acc[2] >> (64 - (row & 63));
+                }
+                first ^= acc[0], second ^= acc[1];
+            }
+            if (exhausted) break;
+            uint64_t& Ta = T[block_a[b]];
+            if (block_kind[b] == GF2_MSTREAM_CNOT) {
+                uint64_t& Tb = T[block_b[b]];
+                gf2_mstream_cnot_map(&Ta, &Tb);
+                Ta ^= first, Tb ^= second;
+            } else {
+                if (plan.step[(size_t)b] >= 0) out[plan.step[(size_t)b]] = (Ta & gf2_stream_frame_mask(block_kind[b])) ^ first;
+                Ta ^= second;
+            }
+        }
+        out[plan.nsteps + plan.flag_words] = attempts;
+    }
+    return GF2_OK;
 }
 
 }  // extern "C"

@@ -32,3 +32,8 @@ int gf2_retry_gate_plan(const char* who, const uint64_t* type_eff, const int64_t
                         const int32_t* block_type, const int32_t* block_kind, int64_t nblocks, const int64_t* type_regions,
                         const int64_t* type_nregions, const int32_t* site_loc, const int64_t* site_regions, int64_t max_attempts,
                         StreamPlan* plan, RetryPlan* retry, RetryGatePlan* gate);
+
+// The second half of gf2_retry_gate_plan alone, over regions that are already checked and filled: the site rules and the segment
+// sizes of the two classes; fills *gate.  gf2_mretry_gate_plan lays it over a multi-block sequence's regions.
+int gf2_retry_gate_site_rules(const char* who, const int64_t* type_locations, int64_t ntypes, const int32_t* site_loc, const int64_t* site_regions,
+                              const RetryPlan& checked, RetryGatePlan* gate);

@@ -552,6 +552,18 @@ class CSSCode(QECC):
         return gadget.retry_error_rates(num_samples, p_x, p_y, p_z, seed=seed, first_sample=first_sample, records=records,
                                         max_attempts=max_attempts)
 
+    def logical_circuit_retried_gate_error_rates(self, instructions, num_samples, p1, p2, seed=0, first_sample=0, records='reference',
+                                                 max_attempts=256):
+        """[build-defined]  logical_circuit_retried_error_rates under gate-level faults (stream_noise.MultiProgram
+        .retry_gate_error_rates): a one-operand gate fails with probability p1 and one of 3 kinds, a CNOT -- a physical CNOT of a
+        transversal logical CNOT included -- as one event with probability p2 and one of 15.  retry_error_rates' dict;
+        max_attempts=1 is gate-level post-selection.  ft_noise.raw_circuit_gate_error_rate is the bare program under the same
+        model."""
+        from . import stream_noise
+        gadget = stream_noise.multi_program_for(self, instructions)
+        return gadget.retry_gate_error_rates(num_samples, p1, p2, seed=seed, first_sample=first_sample, records=records,
+                                             max_attempts=max_attempts)
+
     def error_correct_retried_error_rates(self, num_samples, p_x, p_y, p_z, rounds, seed=0, first_sample=0, idle_data=False, max_attempts=256):
         """[build-defined]  error_correct_streamed_error_rates with every preparation retried on its own until its verifications
         pass (stream_noise.StreamedGadget.retry_error_rates), as the reference's while_do loops run them: essentially every sample is

@@ -247,6 +247,38 @@ def raw_circuit_error_rate(instructions, p_x, p_y, p_z):
     return out
 
 
+def raw_circuit_gate_error_rate(instructions, p1, p2):
+    """raw_circuit_error_rate under gate-level faults: a Pauli other than I and a measurement are one-operand
+    locations that fail with probability p1 and one of 3 Paulis, a CNOT fails as one event with probability p2 and one of the 15
+    two-qubit Paulis (a fault follows its gate).  With raw_circuit_error_rate's reach sets, a one-operand fault that reaches the
+    measured qubit flips the bit for 2 of its 3 kinds; a CNOT event of which at least one operand reaches it flips the bit when
+    the XOR of the reaching operands' X components is 1, which holds for 8 of the 15 kinds whether one operand reaches or both.
+    The events are independent, so per MEASURE in program order the bit is wrong with probability
+    (1 - (1 - 4 p1 / 3)^m1 (1 - 16 p2 / 15)^m2) / 2, m1 the reaching one-operand locations with the measurement's own, m2 the
+    CNOTs with a reaching operand."""
+    instructions, qubits = check_instructions(instructions)
+    reach = {q: set() for q in qubits}                              # raw_circuit_error_rate's, with its location numbers
+    locations, out, cnot_of = 0, [], {}                             # a CNOT operand's location -> its CNOT's first location
+    for inst in instructions:
+        if inst[0] == 'CNOT':
+            a, b = inst[1:]
+            reach[b] ^= reach[a]
+            reach[a] ^= {locations}
+            reach[b] ^= {locations + 1}
+            cnot_of[locations] = cnot_of[locations + 1] = locations
+            locations += 2
+        elif inst[0] == 'MEASURE':
+            mine = reach[inst[1]]
+            m_1 = sum(1 for l in mine if l not in cnot_of) + 1
+            m_2 = len({cnot_of[l] for l in mine if l in cnot_of})
+            out.append(0.5 * (1.0 - (1.0 - 4.0 * float(p1) / 3.0) ** m_1 * (1.0 - 16.0 * float(p2) / 15.0) ** m_2))
+            locations += 1
+        elif inst[0] != 'I':
+            reach[inst[1]] ^= {locations}
+            locations += 1
+    return out
+
+
 def raw_program_error_rate(ops, p_x, p_y, p_z):
     """The probability that the bare program `ops; MEASURE` on one physical qubit gives the wrong bit under the same fault model: one
     location per gate other than I plus one before the measurement, the bit wrong iff an odd number of them carry an X or a Y:

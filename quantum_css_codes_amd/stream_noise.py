@@ -48,7 +48,9 @@ MultiProgram is the same walk for rewritten programs on up to four logical qubit
 kind, CNOT, whose closing applies T_b ^= T_a & 0x00000000FFFFFFFF, T_a ^= T_b & 0xFFFFFFFF00000000 to the two carried words and then
 XORs its faults' two tails.  Its retry_* methods are the repeat-until-success sampler of such programs (DESIGN.md section 5d
 "Repeat-until-success of multi-block programs"): the regions of the block types as above, a CNOT block one region that is not
-retried.  The gate-level and waiting variants are those of one qubit.
+retried.  Its retry_gate_* methods run that walk under gate-level faults (DESIGN.md section 5d "Repeat-until-success of multi-block
+programs under gate-level faults"): a physical CNOT of a CNOT block fails as one event that puts a correlated Pauli on both data
+frames.  The waiting variants are those of one qubit.
 """
 import numpy as np
 
@@ -623,6 +625,12 @@ class CnotBlockType(object):
     def num_locations(self):
         return len(self.locations)
 
+    def gate_regions(self):
+        """The sites of the gate-level fault model (BlockType.gate_regions): (site_loc, [[0, n]]) with site_loc = 0, 2, ..., 2 n - 2.
+        Site i is the physical CNOT D_a[i] -> D_b[i]: location 2 i is its control on frame a, 2 i + 1 its target on frame b."""
+        loc, n1, n2, _ = circuit_noise.gate_sites(self.gates, self.locations)
+        return loc.astype(np.int32), np.array([[n1, n2]], dtype=np.int64)
+
 
 class MultiProgram(object):
     """A rewritten program on 1 <= Q <= 4 logical qubits with the transversal CNOT, prepared for the Monte-Carlo (DESIGN.md section
@@ -703,8 +711,12 @@ class MultiProgram(object):
         self.type_regions = np.ascontiguousarray(np.concatenate([t.regions for t in types]))
         self.type_nregions = np.array([len(t.regions) for t in types], dtype=np.int64)
         self.preparations = int(sum(int(types[t].regions[:, 2].sum()) for t in self.block_type))
+        sites = [t.gate_regions() for t in types]
+        self.type_site_loc = np.ascontiguousarray(np.concatenate([loc for loc, _ in sites]), dtype=np.int32)
+        self.type_site_regions = np.ascontiguousarray(np.concatenate([counts for _, counts in sites]), dtype=np.int64)
         self._device = None
         self._retry_device = None
+        self._retry_gate_device = None
 
     @classmethod
     def from_quil(cls, raw_prog, code):
@@ -894,6 +906,51 @@ class MultiProgram(object):
         every preparation in order, 0 for one never reached.  tally_host on words[:, :ldw] completes the statement."""
         return _native.mretry_words_host(*self._retry_sequence(), seed, first_sample, num_samples, p_x, p_y, p_z, max_attempts, self.ldw + 1,
                                          self.preparations)
+
+    # -- repeat-until-success under gate-level faults ----------------------------------------------------------------------------
+    def _retry_gate_sequence(self):
+        return self._retry_sequence() + (self.type_site_loc, self.type_site_regions)
+
+    def retry_gate_device(self):
+        if self._retry_gate_device is None:
+            self._retry_gate_device = _native.default_context().mretry_gate_create(*self._retry_gate_sequence())
+        return self._retry_gate_device
+
+    def retry_gate_outcomes(self, num_samples, p1, p2, seed=0, first_sample=0, max_attempts=256):
+        """retry_outcomes under gate-level faults (DESIGN.md section 5d "Repeat-until-success of multi-block programs under gate-level
+        faults"): every one-operand gate fails with probability p1 and one of 3 kinds, every CNOT -- those of a CNOT block
+        included, where the event acts on both data frames -- as one event with probability p2 and one of 15; a (num_samples, ldw
+        + 1) uint64 array [steps] [flag words, zero unless the sample is exhausted] [attempts of the sample]
+        (gf2_mretry_gate_outcomes_dev).  max_attempts = 1 is gate-level post-selection."""
+        ctx = _native.default_context()
+        count = int(num_samples)
+        buf = ctx.alloc(max(1, count) * (self.ldw + 1) * 8)
+        try:
+            ctx.mretry_gate_outcomes_dev(self.retry_gate_device(), int(seed), int(first_sample), count, float(p1), float(p2), int(max_attempts),
+                                         buf, self.ldw + 1)
+            return buf.download((count, self.ldw + 1), np.uint64)
+        finally:
+            buf.free()
+
+    def retry_gate_counts(self, num_samples, p1, p2, seed=0, first_sample=0, records='reference', max_attempts=256):
+        """retry_counts' twenty-two counts of samples [first_sample, first_sample + num_samples) under gate-level faults on the
+        device (gf2_mc_mretry_gate_decode)."""
+        records = self._records(records)
+        return _native.default_context().mc_mretry_gate_decode(self.retry_gate_device(), records, *self._tables(), int(seed), int(first_sample),
+                                                                int(num_samples), float(p1), float(p2), int(max_attempts))
+
+    def retry_gate_error_rates(self, num_samples, p1, p2, seed=0, first_sample=0, records='reference', max_attempts=256):
+        """retry_error_rates' dict under gate-level faults.  The counts of sample ranges add."""
+        counts = self.retry_gate_counts(num_samples, p1, p2, seed, first_sample, records, max_attempts)
+        out = self._dict(counts, num_samples)
+        out.update(exhausted=int(counts[20]), attempts=int(counts[21]), preparations=self.preparations)
+        return out
+
+    def retry_gate_words_host(self, num_samples, p1, p2, seed=0, first_sample=0, max_attempts=256):
+        """retry_gate_outcomes' words on the host (gf2_mretry_gate_words_host, no GPU) and the (num_samples, preparations) uint32
+        attempts of every preparation in order, 0 for one never reached.  tally_host on words[:, :ldw] completes the statement."""
+        return _native.mretry_gate_words_host(*self._retry_gate_sequence(), seed, first_sample, num_samples, p1, p2, max_attempts, self.ldw + 1,
+                                              self.preparations)
 
 
 def multi_program_for(code, instructions):
